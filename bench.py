@@ -31,6 +31,20 @@ itself under torch.distributed.run before touching a GPU):
 * cfg2 / cfg3: each rank serves its own suggestion (replicas) -- weak.
 
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the headline
+figures (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` and the workload description).  ``--full`` adds everything
+that takes runs of its own: the CPU baseline (before any GPU call), the
+profiled and census passes behind ``evaluated_pairs_per_s`` and ``roofline``
+(with its microkernel peaks), and the end-to-end ``tpe.suggest`` latencies.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+-- rank 0's winner records [suggestions, hyperparameters] -- as float64
+``DIR/score.npy``, ``value.npy``, ``index.npy`` and ``active.npy`` (score and
+value of an inactive hyperparameter, NaN in the record, are written as 0).
+History and seeds depend on the arguments alone, so two runs with the same
+arguments dump the same suggestions.
 """
 from __future__ import annotations
 
@@ -318,13 +332,20 @@ def main():
     ap.add_argument('--cpu-seconds', type=float, default=10.0)
     ap.add_argument('--prune', type=int, default=3, choices=[0, 1, 2, 3],
                     help='log-sum-exp prune mode of large draws (tpe_plan_set_prune; A/B)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-e2e', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the CPU baseline, the profiled / census passes (roofline, '
+                         'evaluated pairs) and the end-to-end latencies')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's winner records as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip that leg')
+    ap.add_argument('--no-e2e', action='store_true', help='with --full: skip that leg')
     ap.add_argument('--parallelism', default='auto', choices=['auto', 'single', 'sharded'],
                     help="auto: the config's multi-GPU mode when N > 1; 'sharded' forces the "
                          "candidate-sharded path (RCCL all-gather + device merge) even at N = 1")
     ap.add_argument('--traffic-json', default=os.path.join(ROOT, 'traffic.json'))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -339,7 +360,7 @@ def main():
 
     # CPU baseline first (rank 0, N = 1): host processes only, before any GPU call
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.config, n_cand, args.cpu_seconds, host_cores())
         if not args.no_e2e:
             cpu['cfg1'] = cpu_cfg1()
@@ -382,17 +403,28 @@ def main():
     else:
         mine = [0]
 
+    # --dump-outputs: device room for the last timed step's records (rank 0)
+    rec = E.RESULT_DTYPE.itemsize
+    kept = None
+    if args.dump_outputs and rank == 0:
+        kept = torch.zeros((len(mine), plan.n_hp * rec), dtype=torch.uint8, device='cuda')
+    last = args.warmup + args.steps - 1
+
     def step(i):
         if sharded is not None:
             sharded.fit()      # on the sharded stream: ordered before its suggest
-            sharded.suggest([7 + 4099 * i], n_cand, fetch=False)
-            return
+            return sharded.suggest([7 + 4099 * i], n_cand, fetch=False)
         if args.config == 'cfg5':
             for b0 in range(0, len(mine), args.batch):
                 seeds = [1_000_003 * (i + 1) + s for s in mine[b0:b0 + args.batch]]
                 plan.fit_suggest(seeds, n_cand, fetch=False)
-            return
+                if kept is not None and i == last:
+                    # (each call's records, before the next call overwrites
+                    # them: a device copy on the engine's stream)
+                    plan.get_results(kept[b0].data_ptr())
+            return None
         plan.fit_suggest([1_000_003 * rank + 4099 * i + 7], n_cand, fetch=False)
+        return None
 
     for i in range(args.warmup):
         step(i)
@@ -402,7 +434,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        records = step(args.warmup + i)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -427,8 +459,48 @@ def main():
     pairs_step = pairs_suggest * sug_step
     value = pairs_step * args.steps / elapsed
 
-    # ---- profiled pass (after the timed region): HIP events on the engine
-    # stream around every scoring / lattice launch, and the pair census
+    if kept is not None:
+        if records is not None:            # sharded: the merged records, on the device
+            kept.view(-1)[:records.numel()].copy_(records)
+        elif args.config != 'cfg5':        # one engine call per step: its records
+            plan.get_results(kept.data_ptr())
+            plan.engine.synchronize()
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs,
+                     kept.cpu().numpy().view(E.RESULT_DTYPE).reshape(len(mine), plan.n_hp))
+
+    full = None
+    if args.full:
+        full = full_passes(args, plan, step, rank, world)
+
+    if rank != 0:
+        if dist:
+            dist.destroy_process_group()
+        return
+    line = report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest,
+                  sug_step, n_cand, cpu, full)
+    print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, res):
+    """The winner records [suggestions, hyperparameters] as one float64 array
+    per field; an inactive hyperparameter's score and value (NaN in the
+    record) are written as 0 so that two dumps compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    on = res['active'] != 0
+    for name in ('score', 'value'):
+        np.save(os.path.join(path, name + '.npy'), np.where(on, res[name], 0.0))
+    np.save(os.path.join(path, 'index.npy'), res['index'].astype(np.float64))
+    np.save(os.path.join(path, 'active.npy'), res['active'].astype(np.float64))
+
+
+def full_passes(args, plan, step, rank, world):
+    """--full, after the timed region: the profiled pass (HIP events on the
+    engine stream around every scoring / lattice launch), the pair census and
+    the end-to-end latencies."""
+    from hyperopt_amd import _engine as E
     n_prof = 1 if args.config in ('cfg4', 'cfg5') else max(1, min(args.steps, 20))
     plan.profile(n_prof * 4096)
     for i in range(n_prof):
@@ -450,17 +522,8 @@ def main():
     e2e = None
     if rank == 0 and world == 1 and not args.no_e2e:
         e2e = dict(cfg1=e2e_cfg1(), cfg2=e2e_latency('cfg2', 30), cfg3=e2e_latency('cfg3', 10))
-
-    if rank != 0:
-        if dist:
-            dist.destroy_process_group()
-        return
-    line = report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest,
-                  sug_step, n_cand, kinds, score_ms, launches, n_prof, lat_ms, lat_launches,
-                  lat_pairs, census, cpu, e2e)
-    print(json.dumps(line))
-    if dist:
-        dist.destroy_process_group()
+    return dict(kinds=kinds, score_ms=score_ms, launches=launches, n_prof=n_prof, lat_ms=lat_ms,
+                lat_launches=lat_launches, lat_pairs=lat_pairs, census=census, e2e=e2e)
 
 
 def plan_last_cand(plan):
@@ -469,10 +532,13 @@ def plan_last_cand(plan):
     return int(getattr(plan, '_last_ncand', 0)) or 1
 
 
-def report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest, sug_step,
-           n_cand, kinds, score_ms, launches, n_prof, lat_ms, lat_launches, lat_pairs, census,
-           cpu, e2e):
-    from hyperopt_amd import _engine as E
+def roofline(args, eng, full):
+    """(roofline dict, this rank's evaluated pairs per step) from the --full
+    passes; the peaks are microkernel runs of their own."""
+    kinds, score_ms, launches, n_prof = (full[k] for k in ('kinds', 'score_ms', 'launches',
+                                                           'n_prof'))
+    lat_ms, lat_launches, lat_pairs, census = (full[k] for k in ('lat_ms', 'lat_launches',
+                                                                 'lat_pairs', 'census'))
     # roofline of the dominant kernel, k_score (every lpdf kind of a level
     # in one launch), priced at the measured register-only rate of exactly
     # its pair arithmetic (k_micro): log-sum-exp pairs and evaluated
@@ -581,8 +647,16 @@ def report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest,
                    'so its time includes the draw',
             avg_launch_ms=lat_ms, launches_per_step=lat_launches / n_prof,
             pairs_per_launch=lat_pairs)
+    return roof, eval_step
+
+
+def report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest, sug_step,
+           n_cand, cpu, full):
+    """The result line: the headline figures of the timed steps and, from the
+    --full passes (``full`` is not None), evaluated pairs, roofline, end-to-end
+    latencies and the CPU baseline."""
     ms_step = 1e3 * elapsed / args.steps
-    return {
+    line = {
         'metric': 'EI candidates scored/sec (x components)',
         'value': value,
         'unit': 'pairs/s',
@@ -610,6 +684,12 @@ def report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest,
             'pairs_per_suggest': pairs_suggest,
             'suggest_latency_ms': ms_step / sug_step if mode != 'replicas' else ms_step,
         },
+        'full': full is not None,
+    }
+    if full is None:
+        return line
+    roof, eval_step = roofline(args, eng, full)
+    line.update({
         # eval_step: this rank's evaluated pairs per step (census per launch x
         # launches per step); every rank does the same share of the job
         'evaluated_pairs_per_s': eval_step * world / (ms_step * 1e-3) if ms_step else None,
@@ -621,9 +701,10 @@ def report(args, C, eng, world, mode, elapsed, value, pairs_step, pairs_suggest,
                                 'zeros (both erf saturated), and value-lattice points x '
                                 'components; value credits every reference pair',
         'roofline': roof,
-        'e2e': e2e,
+        'e2e': full['e2e'],
         'cpu_baseline': cpu,
-    }
+    })
+    return line
 
 
 if __name__ == '__main__':

@@ -43,6 +43,30 @@ def opt(v):
     return NONE if v is None else float(v)
 
 
+PART_BYTES = 900 * 1024     # every committed fixture file stays under 1 MiB
+
+
+def save_parts(name, d):
+    """Write the arrays of ``d`` as name.npz, name.part2.npz, ...: whole
+    arrays, in key order, a new part whenever the next array would take the
+    file past PART_BYTES (golden_io.load reads the parts back as one dict)."""
+    import io
+    parts, size = [{}], 0
+    for key in sorted(d):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{key: d[key]})
+        n = buf.tell()
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][key] = d[key]
+        size += n
+    for k, part in enumerate(parts):
+        fn = name + ('.npz' if k == 0 else '.part%d.npz' % (k + 1))
+        np.savez_compressed(os.path.join(HERE, fn), **part)
+        assert os.path.getsize(os.path.join(HERE, fn)) < (1 << 20), fn
+
+
 # ---------------------------------------------------------------- split
 def gen_split():
     rng = np.random.RandomState(11)
@@ -69,7 +93,7 @@ def gen_split():
     pack(d, 'o_vals', [c[4] for c in cases])
     pack(d, 'below', [c[5] for c in cases])
     pack(d, 'above', [c[6] for c in cases])
-    np.savez_compressed(os.path.join(HERE, 'split.npz'), **d)
+    save_parts('split', d)
     print('split cases', len(cases))
 
 
@@ -337,7 +361,7 @@ def gen_suggest():
         pack(d, 'samples', [p['samples'] for p in per])
         pack(d, 'llik_b', [p['llik_b'] for p in per])
         pack(d, 'llik_a', [p['llik_a'] for p in per])
-        np.savez_compressed(os.path.join(HERE, 'suggest_%s.npz' % name), **d)
+        save_parts('suggest_%s' % name, d)
         meta[name] = dict(labels=labels, n=n, hist_seed=hseed, loss_seed=lseed,
                           suggest_seed=sseed, kw=kw, new_id=n,
                           n_best_calls=len(per))

@@ -8,7 +8,18 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def load(name):
-    return dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+    """The arrays of fixture ``name`` (x.npz) and of its further parts
+    x.part2.npz, x.part3.npz, ... (make_golden.py keeps every file under
+    1 MiB by spreading a fixture's arrays over several)."""
+    d = dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+    stem = name[:-len('.npz')]
+    k = 2
+    while os.path.exists(os.path.join(GOLDEN, '%s.part%d.npz' % (stem, k))):
+        part = np.load(os.path.join(GOLDEN, '%s.part%d.npz' % (stem, k)), allow_pickle=False)
+        assert not set(part.files) & set(d), (name, k)
+        d.update(part)
+        k += 1
+    return d
 
 
 def load_json(name):

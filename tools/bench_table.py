@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One line per bench.py JSON file of a gpurun output directory: ms per step,
+"""One line per `bench.py --full` JSON file of a directory: ms per step,
 scoring launch time, roofline fraction, v_exp_f32 issue fraction and the
 moment-form pair counts.  usage: bench_table.py <dir> [name ...]"""
 import glob

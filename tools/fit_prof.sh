@@ -10,5 +10,5 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
     tests/test_gpu_ops.py -k "parzen or fit or split or categorical" > $O/tests.log 2>&1
 timeout -k 10 120 python -u tools/fit_stamps.py cfg2 > $O/stamps.txt 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- \
-    python -u bench.py --config cfg2 --steps 20 --warmup 5 --no-cpu-baseline --no-e2e > $O/trace.log 2>&1
+    python -u bench.py --full --config cfg2 --steps 20 --warmup 5 --no-cpu-baseline --no-e2e > $O/trace.log 2>&1
 echo done
