@@ -525,7 +525,8 @@ class Plan(object):
         the fitted mixtures.  sorted_mode None: each candidate scored on its
         own (exact sums); 0 / 1 / 2 / 3: the large-draw production form
         (tpe_plan_score_candidates_sorted: value-bucketed blocks, log-sum-exp
-        prune mode 0 / 1 / 2 / 3).  want_llik False: no lpdf outputs -- the
+        prune mode 0 / 1 / 2 / 3; 4: mode 3's tiles scored from the hp's
+        certified Chebyshev tables, an error if either is not).  want_llik False: no lpdf outputs -- the
         scorer then takes the suggest's EI-only finalize (one log2 of the
         ratio of the two sums) and (None, None, index, score) is returned."""
         e = self.engine
@@ -576,12 +577,13 @@ class Plan(object):
         one-exponent pairs re-evaluated by a wave's second attempt,
         one-exponent pairs of wide blocks (mode 3's fp64 loop), one-exponent
         pairs evaluated in the moment form of their chunk, of those the
-        8-wide form, of those the 16-wide degree-15 form]) -- the first
-        ``n`` (7 .. 12); enable it for the following suggests."""
-        if not 0 <= n <= 12:
-            raise ValueError('the census has 12 counters')
+        8-wide form, of those the 16-wide degree-15 form, pairs credited to
+        candidates scored from the Chebyshev tables]) -- the first
+        ``n`` (7 .. 13); enable it for the following suggests."""
+        if not 0 <= n <= 13:
+            raise ValueError('the census has 13 counters')
         e = self.engine
-        out = (C.c_int64 * 12)()
+        out = (C.c_int64 * 13)()
         with e.lock:
             e.check(e.lib.tpe_plan_census_n(self.p, int(bool(enable)), out, int(n)))
         return tuple(int(v) for v in out[:n])

@@ -104,6 +104,7 @@ static bool side_streams_on() {
   return on;
 }
 static bool moment_on();
+static bool table_on();
 // TPE_MOMENT_H=0: 16-wide plans without the degree-15 chunk table (A/B)
 static bool moment_h_on() {
   static const bool on = [] {
@@ -152,6 +153,15 @@ struct tpe_plan {
   CoefM8 *d_coefm8 = nullptr;  // [2P][kcap / kCoefBlock] moment form of 8-component blocks
   float4 *d_coefe = nullptr;   // [2P][kcap / kCoefBlock] compact log-sum-exp block envelopes
   CoefM8 *d_coefmh = nullptr;  // [2P][mom_stride(kcap)] degree-15 form of 16-component chunks
+  // Chebyshev tables of the bounded continuous hps' mixtures (k_table_build):
+  // built lazily, once per fit epoch, by the first scoring launch that takes
+  // them (tab_built: the tables are those of the current mixtures)
+  TabHdr *d_tab_hdr = nullptr;  // [2P]
+  TabPanel *d_tab = nullptr;    // [2P][kTabMaxPanels]
+  double *d_tab_max = nullptr;  // [s_cap][P] best table score per slot (ScoreArgs::tab_max)
+  double *d_tab_wmax = nullptr; // [partial_cap][8] ... per wave tile
+  bool tab_built = false;
+  bool graph_tab = false;       // the captured graph holds the build
   std::vector<double> act_frac;  // per hp: expected share of the trials it is active in
   int64_t n = 0;  // history length
   // suggestion state
@@ -212,10 +222,13 @@ struct tpe_plan {
     bool table = false;  // below mixtures fit the LDS draw table (kTabCap)
     bool fuse = false;   // ... and the fused k_lattice draw rows' table (kFuseTab)
     bool small = false;  // k_fit<true> serves the history (fit_small)
+    int32_t mom_w = 0;   // the moment table the step's fit writes (mom_width grows with
+                         // the history: a replay must not keep the captured width)
+    bool tab = false;    // the step builds and scores from the Chebyshev tables
     bool operator==(const StepKey &o) const {
       return prior_weight == o.prior_weight && lf == o.lf && n_sug == o.n_sug &&
              n_cand == o.n_cand && stream == o.stream && table == o.table && fuse == o.fuse &&
-             small == o.small;
+             small == o.small && mom_w == o.mom_w && tab == o.tab;
     }
   };
   StepKey graph_key, pending_key;
@@ -284,7 +297,8 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_msig, p->d_scratch, p->d_info, p->d_coef, p->d_results, p->d_seeds,
                   p->d_partial, p->d_ext, p->d_lb, p->d_la, p->d_cand, p->d_cpos,
                   p->d_ticket, p->d_sortbuf, p->d_census, p->d_lat_info, p->d_lat, p->d_coef32, p->d_coefm,
-                  p->d_coefm8, p->d_coefe, p->d_coefmh};
+                  p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
+                  p->d_tab_max, p->d_tab_wmax};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -468,6 +482,9 @@ int plan_build(tpe_engine *h, const tpe_space *sp, int64_t max_trials, tpe_plan 
   CKH(dalloc(&p->d_coefm8, (size_t)slots * (kcap / kCoefBlock)));
   CKH(dalloc(&p->d_coefe, (size_t)slots * (kcap / kCoefBlock)));
   CKH(dalloc(&p->d_coefmh, (size_t)slots * mom_stride(kcap)));
+  CKH(dalloc(&p->d_tab_hdr, (size_t)slots));
+  CKH(hipMemset(p->d_tab_hdr, 0, (size_t)slots * sizeof(TabHdr)));
+  CKH(dalloc(&p->d_tab, (size_t)slots * kTabMaxPanels));
   // expected activity of every hp (mom_width): an hp conditioned on branch b
   // of a categorical parent is active in ~1 / upper of the parent's trials
   // (levels are in dependency order: parents first)
@@ -525,12 +542,18 @@ int ensure_suggest_state(tpe_engine *h, tpe_plan *p, int64_t n_sug, size_t parti
     // (+1: the launch-wide arrival counter of a publishing launch, pub_ticket)
     CKH(dalloc(&p->d_ticket, (size_t)n_sug * p->P + 1));
     CKH(hipMemset(p->d_ticket, 0, ((size_t)n_sug * p->P + 1) * sizeof(uint32_t)));
+    dfree(p->d_tab_max);
+    p->d_tab_max = nullptr;
+    CKH(dalloc(&p->d_tab_max, (size_t)n_sug * p->P));
     p->s_cap = n_sug;
   }
   if (partials > p->partial_cap) {
     dfree(p->d_partial);
     p->d_partial = nullptr;
     CKH(dalloc(&p->d_partial, partials));
+    dfree(p->d_tab_wmax);
+    p->d_tab_wmax = nullptr;
+    CKH(dalloc(&p->d_tab_wmax, partials * 8));  // (one per wave of a tile)
     p->partial_cap = partials;
   }
   return TPE_OK;
@@ -694,6 +717,10 @@ ScoreArgs base_args(tpe_plan *p, int64_t n_sug) {
   a.lse_momh = p->mom_w == 16 && p->mom_h ? 1 : 0;
   a.l2_warm = l2_warm_on() ? 1 : 0;
   a.lse_tight = tighten_on() ? 1 : 0;
+  a.tab_hdr = p->d_tab_hdr;
+  a.tab = p->d_tab;
+  a.tab_max = p->d_tab_max;
+  a.tab_wmax = p->d_tab_wmax;
   return a;
 }
 
@@ -730,6 +757,7 @@ int32_t mom_width(const tpe_plan *p) {
 // hold (the scoring launches read that one: base_args)
 FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf, bool mom = true) {
   p->mom_w = mom ? mom_width(p) : 0;
+  p->tab_built = false;  // a new fit epoch
   FitArgs a{};
   a.hps = p->d_hps;
   a.vals = p->d_vals;
@@ -776,6 +804,17 @@ int fit_launch(tpe_engine *h, tpe_plan *p, const FitArgs &a, int32_t n_hp, hipSt
   return TPE_OK;
 }
 
+// the Chebyshev tables of the current mixtures, if this fit epoch has none yet
+int table_build(tpe_engine *h, tpe_plan *p, hipStream_t st) {
+  if (p->tab_built) return TPE_OK;
+  CKH(launch_table_build(p->d_hps, p->P, p->d_info, p->d_coef, p->kcap, p->d_tab_hdr, p->d_tab,
+                         p->census ? p->d_census : nullptr, st));
+  p->tab_built = true;
+  return TPE_OK;
+}
+
+// (a launch that takes the tables, tab_on, builds them first if need be --
+// inside the profile bracket, so plan.profile times the build with it)
 int score_launch(tpe_engine *h, tpe_plan *p, ScoreArgs a, bool has_erf, int64_t cn,
                  hipStream_t sg, bool record, int classes = 7) {
   tpe_plan::Prof *pr = nullptr;
@@ -784,6 +823,10 @@ int score_launch(tpe_engine *h, tpe_plan *p, ScoreArgs a, bool has_erf, int64_t 
     if (pr->n >= p->prof_cap) pr = nullptr;  // ring full: stop recording
   }
   if (pr) CKH(hipEventRecord(pr->a[pr->n], sg));
+  if (a.tab_on == 1 && (classes & 1)) {
+    const int rc = table_build(h, p, sg);
+    if (rc) return rc;
+  }
   // (a level mixing wave-tile log-sum-exp slots with other kinds: those run
   // beside it on an auxiliary stream; the events are free at scoring time)
   CKH(launch_score(a, has_erf, sg, side_streams_on() ? h->aux[1] : nullptr, p->ev_join[1],
@@ -1027,6 +1070,19 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
     // suggest, pruned (large draws) or not (small draws: every pair, 8-wave
     // component-split tiles)
     a.lse_f32 = p->prune_mode == 3 ? 1 : 0;
+    // Chebyshev tables (TabHdr): suggests of > kWaveRowSplitMax candidates
+    // (n_total: shards agree) in prune mode 3 whose mixtures are in the
+    // 16-wide moment class, for the level's bounded continuous hps -- the
+    // slots whose two tables are certified go through k_score_table, and
+    // k_score_wave_tie scores directly only the waves near the best table
+    // score (TPE_TABLE=0: off)
+    {
+      bool any = false;
+      for (int i = 0; i < n_level; ++i)
+        any |= (ck[i] == KIND_LSE_GW || ck[i] == KIND_LSE_LW) && table_hp(p->hps[hl[i]]);
+      a.tab_on = any && sorted_draw && p->prune_mode == 3 && n_total > kWaveRowSplitMax &&
+                         a.lse_mom == 16 && table_on() ? 1 : 0;
+    }
     // lookup tiles drawing their own candidates need nothing from this
     // chunk's draw: forked onto an auxiliary stream, they run beside the draw
     // and the log-sum-exp scoring, and st waits for them before the next
@@ -1131,13 +1187,28 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
 // sorted_mode < 0: every candidate scored on its own (exact sums, any
 // tiling); >= 0: the large-draw production form -- value-bucketed in
 // kSortedBlock blocks as k_draw_sorted writes them, log-sum-exp prune mode
-// sorted_mode on the tiles run_level picks for it.
+// sorted_mode on the tiles run_level picks for it (4: those tiles scored from
+// the hp's certified Chebyshev tables alone).
 int run_external(tpe_engine *h, tpe_plan *p, int32_t hp, const double *ext, int64_t n,
                  double *lb, double *la, hipStream_t st, int32_t sorted_mode = -1) {
   int kind = score_kind(p->hps[hp]);
   const bool sorted = sorted_mode >= 0;
   if (sorted && sorted_mode > 1)
     kind = kind == KIND_LSE_G ? KIND_LSE_GW : kind == KIND_LSE_L ? KIND_LSE_LW : kind;
+  // mode 4: prune mode 3's tiles scored from the hp's Chebyshev tables only
+  const bool tab = sorted_mode == 4;
+  if (tab) {
+    sorted_mode = 3;
+    if (!table_hp(p->hps[hp])) return fail(h, TPE_E_INVALID, "hp has no Chebyshev table");
+    const int rc = table_build(h, p, st);
+    if (rc) return rc;
+    TabHdr th[2];
+    CKH(hipMemcpyAsync(th, p->d_tab_hdr + 2 * (int64_t)hp, sizeof(th), hipMemcpyDeviceToHost, st));
+    CKH(hipStreamSynchronize(st));
+    for (const TabHdr &t : th)
+      if (!(t.P > 0 && t.ncert == (uint32_t)t.P))
+        return fail(h, TPE_E_INVALID, "Chebyshev table not certified");
+  }
   ScoreArgs grid{};
   const int32_t pstride = set_score_groups(grid, &kind, 1, n);
   int rc = ensure_suggest_state(h, p, 1, (size_t)p->P * pstride);
@@ -1166,6 +1237,7 @@ int run_external(tpe_engine *h, tpe_plan *p, int32_t hp, const double *ext, int6
     a.lse_pos = 1;
     a.lse_prune = sorted_mode;
     a.lse_shift_min = lse_shift_min();
+    a.tab_on = tab ? 2 : 0;
   }
   return score_launch(h, p, a, kind == KIND_ERF_G || kind == KIND_ERF_L, n, st, false);
 }
@@ -1291,6 +1363,7 @@ int put_mixture(tpe_engine *h, tpe_plan *p, int slot, const double *w, const dou
   mi.kind = kind;
   CKH(hipMemcpyAsync(p->d_info + slot, &mi, sizeof(MixInfo), hipMemcpyHostToDevice, st));
   CKH(hipStreamSynchronize(st));  // mi lives on this frame
+  p->tab_built = false;
   return TPE_OK;
 }
 
@@ -1785,6 +1858,7 @@ int capture_step(tpe_engine *h, tpe_plan *p, int32_t nb, double prior_weight, in
   p->graph = g;
   p->graph_mom_w = p->mom_w;  // the table the captured fit writes (its args are fixed)
   p->graph_mom_h = p->mom_h;
+  p->graph_tab = p->tab_built;  // (the build node, if the step has one)
   CKH(hipGraphInstantiate(&p->graph_exec, g, nullptr, nullptr, 0));
   size_t nn = 0;
   CKH(hipGraphGetNodes(g, nullptr, &nn));
@@ -1854,6 +1928,7 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
   p->last_nb = nb;
   p->mom_w = p->graph_mom_w;  // (no fit_args on replay: the captured fit's table)
   p->mom_h = p->graph_mom_h;
+  p->tab_built = p->graph_tab;
   return TPE_OK;
 }
 
@@ -1883,6 +1958,13 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
   key.table = (int64_t)nb + 1 <= kTabCap;
   key.fuse = (int64_t)nb + 1 <= kFuseTab;
   key.small = fit_small(p->n);
+  {
+    bool sorted = false;  // (enqueue_step's condition for the moment table)
+    for (const auto &l : p->levels)
+      sorted |= n_cand * n_sug * (int64_t)l.size() >= ((int64_t)1 << 22);
+    key.mom_w = sorted && n_cand > kWaveRowSplitMax ? mom_width(p) : 0;
+    key.tab = key.mom_w == 16 && p->prune_mode == 3 && table_on();
+  }
   int rc = ensure_suggest_state(h, p, n_sug, 1);
   if (rc) return rc;
   p->h_seeds.assign(seeds, seeds + n_sug);
@@ -1983,7 +2065,7 @@ int tpe_plan_score_candidates_sorted(tpe_plan_t p, int32_t hp, int32_t mode, con
                                      int64_t *best_index, double *best_score) {
   if (!p) return TPE_E_INVALID;
   tpe_engine *h = p->eng;
-  if (hp < 0 || hp >= p->P || n < 0 || (n > 0 && !x) || mode < -1 || mode > 3)
+  if (hp < 0 || hp >= p->P || n < 0 || (n > 0 && !x) || mode < -1 || mode > 4)
     return fail(h, TPE_E_INVALID, "bad args");
   if (n > (int64_t)INT32_MAX) return fail(h, TPE_E_INVALID, "too many candidates");
   if (best_index) *best_index = -1;
@@ -2167,6 +2249,17 @@ static bool small_sort_on() {
 static bool moment_on() {
   static const bool v = [] {
     const char *e = std::getenv("TPE_MOMENT");
+    return !(e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+
+// large draws scored from certified Chebyshev tables of both mixtures
+// (k_table_build / k_score_table; TPE_TABLE=0 switches them off: A/B and the
+// parity tests' child processes)
+static bool table_on() {
+  static const bool v = [] {
+    const char *e = std::getenv("TPE_TABLE");
     return !(e && std::atoi(e) == 0);
   }();
   return v;

@@ -116,8 +116,10 @@ constexpr float kLseDeadBase = 26.0f;
 // second attempt (re-centred exponent) / one-exponent pairs of wide blocks
 // (the fp64 loop of mode 3) / one-exponent pairs evaluated in the moment
 // form of their chunk (CoefM, 16-wide, or CoefM8, 8-wide) / of those, the
-// 8-wide ones / of those, the 16-wide degree-15 ones (CoefMH)
-constexpr int kCensus = 12;
+// 8-wide ones / of those, the 16-wide degree-15 ones (CoefMH) / pairs
+// credited to candidates scored from the Chebyshev tables (k_score_table;
+// also counted in the log-sum-exp total)
+constexpr int kCensus = 13;
 
 // Per-component scoring coefficients (make_coef, tpe_device.hpp), 4 fields:
 //   LSE: x = alpha, y = beta, z = gamma (t = alpha + y'(beta + gamma y'))
@@ -238,6 +240,38 @@ static_assert(sizeof(CoefM8) == 128, "two 64-B scalar loads");
 // block-local pair form (3.3 VALU per pair against ~0.9 for a degree-15
 // chunk of 16)
 
+// Chebyshev table of one (hp, side) mixture (bounded, non-quantized GMM / LGMM
+// hps of 16-wide moment plans, large draws; k_table_build, k_score_table).
+// g(y') = sum_k 2^(t_k(y')) is a smooth function of the centred candidate y'
+// whose bandwidth is bounded below by the mixture's smallest sigma, so over
+// [y_lo, y_hi] it is kept as P = ceil((y_hi - y_lo) / (2 H)) equal panels of
+// half-width <= H = sigma_min, each a degree-15 Chebyshev interpolant (16
+// first-kind nodes) of g * 2^-M with M the panel's integer exponent.  A panel
+// is certified when its rigorous interpolation bound is below
+// 2^-28 of a lower bound of g on it; a slot is used only when every panel is
+// (ncert == P > 0).  ncert is zeroed before each build and counted up by the
+// certified panels' blocks.
+constexpr int kTabNodes = 16;
+constexpr int kTabMaxPanels = 64;
+struct __attribute__((aligned(16))) TabHdr {
+  double y_lo;     // y' of the hp's low
+  double inv_w;    // 1 / panel width
+  int32_t P;       // panels (0: no table)
+  uint32_t ncert;  // certified panels
+  double pad;
+};
+struct __attribute__((aligned(16))) TabPanel {
+  double c[kTabNodes];  // Chebyshev coefficients of g * 2^-M (c[0] already halved)
+  double M;             // integer-valued exponent
+  double pad;
+};
+static_assert(sizeof(TabHdr) == 32 && sizeof(TabPanel) == 144, "table layout");
+// the hps a table is built for
+__host__ __device__ inline bool table_hp(const tpe_hp &h) {
+  return (h.family == TPE_GMM || h.family == TPE_LGMM) && !(h.flags & TPE_HAS_Q) &&
+         (h.flags & TPE_HAS_LOW) && (h.flags & TPE_HAS_HIGH);
+}
+
 struct Partial {  // == tpe_result layout
   double score;
   double value;
@@ -333,6 +367,16 @@ struct ScoreArgs {
                              // (k_score_tdraw; no k_draw launch, nothing written)
   const LatInfo *lat_info;   // [P] value lattices (KIND_LAT slots)
   const double2 *lat;        // lattice (lpdf below, lpdf above) pairs
+  // Chebyshev tables (k_table_build): tab_on 1 -- a two-row wave-tile slot
+  // whose two tables are certified is scored by k_score_table, and
+  // k_score_wave scores again only the waves within the sums' own error of the
+  // slot's best table score, so the winner is the one its sums alone give; 2 -- the operator form (k_score_table alone, the host has
+  // checked the slot's tables); 0 -- no tables
+  const TabHdr *tab_hdr;     // [2*P]
+  const TabPanel *tab;       // [2*P][kTabMaxPanels]
+  int32_t tab_on;
+  double *tab_max;           // [S][P] tab_on 1: the slot's best table score of this launch
+  double *tab_wmax;          // [S][P][pstride][8] ... and every wave tile's
   // a tile_draw launch that ends its call (pub_flag non-null): the last of its
   // pub_events final records copies all pub_words words of results into the
   // pinned pub_dst and then stores pub_seq into *pub_flag -- k_publish's
@@ -480,6 +524,11 @@ hipError_t launch_sample(const tpe_hp *hp_dev, const double *mw,
                          hipStream_t st);
 
 hipError_t launch_micro(int which, int blocks, int iters, double *sink, hipStream_t st);
+// Chebyshev tables of both mixtures of every table_hp of the plan (headers
+// zeroed first); census: optional pair counters ([3] and [5] += node pairs)
+hipError_t launch_table_build(const tpe_hp *hps, int32_t n_hp, const MixInfo *info,
+                              const Coef *coef, int64_t kcap, TabHdr *hdr, TabPanel *tab,
+                              unsigned long long *census, hipStream_t st);
 
 // small history updates travel as kernel arguments (tpe_plan_update_history):
 // one launch, no staging copy and no host synchronisation

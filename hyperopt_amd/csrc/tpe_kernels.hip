@@ -786,4 +786,197 @@ hipError_t launch_sample(const tpe_hp *hp_dev, const double *mw, const double *m
   return hipGetLastError();
 }
 
+// ---- Chebyshev tables of the fitted mixtures (tpe_internal.hpp TabHdr) ----
+// One block per (panel, slot): 256 threads = 16 nodes x 16 component lanes.
+// Lane l of node j sums the coefficient blocks l, l + 16, ... at the node in
+// the exact per-group-lift form (fp64 terms, integer exponent lifts, fp64
+// exp2), skipping the blocks whose envelope bound over the panel lies 64
+// binades under the probe component's smallest term on it (each skipped term
+// < 2^-64 of the sum); the 16 lanes' sums merge in lane order, so a table is
+// the same bits wherever and whenever it is built.  Then the fixed 16 x 16
+// cosine transform, and the panel's certificate over every
+// component in the log2 domain, where nothing overflows.
+constexpr int kTabThreads = 256;
+constexpr double kTabSkip = 64.0;
+
+struct TabAcc {
+  double m, s;  // value = 2^m * s, m integer-valued or -inf
+};
+__device__ __forceinline__ void tab_add(TabAcc &a, double t) {
+  const double mn = fmax(a.m, ceil(t));
+  a.s = ldexp(a.s, (int)fmax(a.m - mn, -2100.0));
+  a.m = mn;
+  a.s += exp2(t - (mn == -INFINITY ? 0.0 : mn));
+}
+__device__ __forceinline__ void tab_merge(TabAcc &a, const TabAcc &b) {
+  const double M = fmax(a.m, b.m);
+  const double ms = M == -INFINITY ? 0.0 : M;
+  a.s = ldexp(a.s, (int)fmax(a.m - ms, -2100.0)) + ldexp(b.s, (int)fmax(b.m - ms, -2100.0));
+  a.m = M;
+}
+__device__ __forceinline__ TabAcc tab_wave_sum(TabAcc a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const TabAcc b{__shfl_xor(a.m, o, 64), __shfl_xor(a.s, o, 64)};
+    tab_merge(a, b);
+  }
+  return a;
+}
+
+__global__ __launch_bounds__(kTabThreads) void k_table_build(
+    const tpe_hp *__restrict__ hps, const MixInfo *__restrict__ info,
+    const Coef *__restrict__ coef, int64_t kcap, TabHdr *__restrict__ hdr,
+    TabPanel *__restrict__ tab, unsigned long long *__restrict__ census) {
+  const int slot = blockIdx.y, p = blockIdx.x, tid = threadIdx.x;
+  const tpe_hp H = hps[slot >> 1];
+  if (!table_hp(H)) return;
+  const MixInfo mi = info[slot];
+  const int K = mi.K;
+  if (K < 1 || K > kcap) return;
+  const double *__restrict__ cf = reinterpret_cast<const double *>(coef + (int64_t)slot * kcap);
+  __shared__ double red[4];
+  __shared__ TabAcc acc[16][16];
+  __shared__ TabAcc cert[2][4];
+  __shared__ double fn[kTabNodes], cn[kTabNodes];
+  __shared__ unsigned live_n;
+  // the mixture's largest a^2 (its smallest sigma)
+  double a2 = 0.0;
+  for (int k = tid; k < K; k += kTabThreads) a2 = fmax(a2, -cf[coef_off(k, 2)]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a2 = fmax(a2, __shfl_xor(a2, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = a2;
+  if (tid == 0) live_n = 0u;
+  __syncthreads();
+  a2 = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  const double L2E = 1.4426950408889634;
+  const double y_lo = H.low - H.prior_mu, y_hi = H.high - H.prior_mu;
+  const double sig = sqrt(0.5 * L2E / a2);
+  const double Pd = ceil((y_hi - y_lo) / (2.0 * sig));
+  if (!(Pd >= 1.0 && Pd <= (double)kTabMaxPanels)) return;  // (block-uniform: no table)
+  const int P = (int)Pd;
+  if (p >= P) return;
+  const double w = (y_hi - y_lo) / Pd, Hh = 0.5 * w;
+  if (p == 0 && tid == 0) {
+    hdr[slot].y_lo = y_lo;
+    hdr[slot].inv_w = 1.0 / w;
+    hdr[slot].P = P;
+  }
+  const double pl = y_lo + w * (double)p, ph = y_lo + w * (double)(p + 1), pc = pl + Hh;
+  // skip threshold from the probe (the widest component): its term is concave
+  // in y', so its minimum over the panel is at an end
+  double thr = -INFINITY;
+  if (mi.probe >= 0 && mi.probe < K) {
+    const double x = cf[coef_off(mi.probe, 0)], y = cf[coef_off(mi.probe, 1)],
+                 z = cf[coef_off(mi.probe, 2)];
+    const double t0 = fma(z, pl * pl, fma(y, pl, x)), t1 = fma(z, ph * ph, fma(y, ph, x));
+    const double tm = fmin(t0, t1);
+    if (tm == tm) thr = tm - kTabSkip;
+  }
+  // node sums
+  const int j = tid & 15, l = tid >> 4;
+  const double yn = pc + Hh * cospi((double)(2 * j + 1) / 32.0), yn2 = yn * yn;
+  TabAcc a{-INFINITY, 0.0};
+  unsigned nlive = 0;
+  const int nb = (K + kCoefBlock - 1) / kCoefBlock;
+  for (int b = l; b < nb; b += 16) {
+    const float4 e = reinterpret_cast<const float4 *>(cf)[(int64_t)b * 16 + 12];
+    const double d = fmax(0.0, fmax((double)e.x - ph, pl - (double)e.y));
+    const double bound = (double)e.z - (double)fabsf(e.w) * d * d;
+    if (bound < thr) continue;
+    const double *__restrict__ blk = cf + (int64_t)b * (4 * kCoefBlock);
+    double t[kCoefBlock], mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < kCoefBlock; ++i) {
+      t[i] = b * kCoefBlock + i < K
+                 ? fma(blk[2 * kCoefBlock + i], yn2, fma(blk[kCoefBlock + i], yn, blk[i]))
+                 : -INFINITY;
+      mx = fmax(mx, t[i]);
+    }
+    nlive += (unsigned)min(kCoefBlock, K - b * kCoefBlock);
+    const double mn = fmax(a.m, ceil(mx));
+    a.s = ldexp(a.s, (int)fmax(a.m - mn, -2100.0));
+    a.m = mn;
+    const double ms = mn == -INFINITY ? 0.0 : mn;
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < kCoefBlock; ++i) sum += exp2(t[i] - ms);
+    a.s += sum;
+  }
+  acc[l][j] = a;
+  if (census && j == 0 && nlive) atomicAdd(&live_n, nlive);
+  // certificate sums: E = sum c_k sigma_k^-16 exp(-d_k^2 / 4 sigma_k^2) (log2:
+  // cc + 8 log2(2 a^2 / log2 e) - a^2 d^2 / 2), G = sum c_k exp(-dfar_k^2 / 2 sigma_k^2)
+  TabAcc ce{-INFINITY, 0.0}, cg{-INFINITY, 0.0};
+  for (int k = tid; k < K; k += kTabThreads) {
+    const double x = cf[coef_off(k, 0)], y = cf[coef_off(k, 1)], z = cf[coef_off(k, 2)];
+    const double ak = -z, mu = y / (2.0 * ak), cc = x + ak * mu * mu;
+    const double d = fmax(0.0, fmax(pl - mu, mu - ph)), df = fmax(mu - pl, ph - mu);
+    tab_add(ce, cc + 8.0 * log2(2.0 * ak / L2E) - 0.5 * ak * d * d);
+    tab_add(cg, cc - ak * df * df);
+  }
+  ce = tab_wave_sum(ce);
+  cg = tab_wave_sum(cg);
+  if ((tid & 63) == 0) { cert[0][tid >> 6] = ce; cert[1][tid >> 6] = cg; }
+  __syncthreads();
+  // node values: the 16 lanes' sums in lane order, then the common exponent
+  double nm = -INFINITY, ns = 0.0;
+  if (tid < kTabNodes) {
+    TabAcc v = acc[0][tid];
+    for (int q = 1; q < 16; ++q) tab_merge(v, acc[q][tid]);
+    nm = v.m;
+    ns = v.s;
+    double M = nm;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o, 64));
+    fn[tid] = ldexp(ns, (int)fmax(nm - (M == -INFINITY ? 0.0 : M), -2100.0));
+    if (tid == 0) red[0] = M;
+  }
+  __syncthreads();
+  const double M = red[0];
+  if (tid < kTabNodes) {
+    double c = 0.0;
+    for (int q = 0; q < kTabNodes; ++q)
+      c = fma(fn[q], cospi((double)(tid * (2 * q + 1)) / 32.0), c);
+    c *= tid == 0 ? 1.0 / 16.0 : 2.0 / 16.0;
+    cn[tid] = c;
+    tab[(int64_t)slot * kTabMaxPanels + p].c[tid] = c;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  tab[(int64_t)slot * kTabMaxPanels + p].M = M;
+  tab[(int64_t)slot * kTabMaxPanels + p].pad = 0.0;
+  if (census) {
+    atomicAdd(census + 3, (unsigned long long)kTabNodes * (unsigned long long)K);
+    atomicAdd(census + 5, (unsigned long long)kTabNodes * (unsigned long long)live_n);
+  }
+  bool ok = M > -INFINITY && M < INFINITY;
+  double ca = 0.0;
+  for (int q = 0; q < kTabNodes; ++q) {
+    ok = ok && fn[q] > 0.0 && fn[q] < INFINITY;
+    ca += fabs(cn[q]);
+  }
+  TabAcc E = cert[0][0], G = cert[1][0];
+  for (int q = 1; q < 4; ++q) { tab_merge(E, cert[0][q]); tab_merge(G, cert[1][q]); }
+  // log2 of: Cramer's bound x H^16 / (2^15 16!), the Clenshaw sum's rounding
+  // (64 ulp of the coefficients' absolute sum), and the lower bound of g
+  const double kL16 = 44.25014046988262;  // log2(16!)
+  const double le = 0.11960158 + 0.5 * kL16 + (E.m + log2(E.s)) + 16.0 * log2(Hh) - 15.0 - kL16;
+  const double lr = M + log2(ca) - 46.0;
+  const double lg = G.m + log2(G.s);
+  ok = ok && le == le && le < INFINITY && lg > -INFINITY && lg < INFINITY &&
+       fmax(le, lr) + 1.0 <= lg - 28.0;
+  if (ok) atomicAdd(&hdr[slot].ncert, 1u);
+}
+
+hipError_t launch_table_build(const tpe_hp *hps, int32_t n_hp, const MixInfo *info,
+                              const Coef *coef, int64_t kcap, TabHdr *hdr, TabPanel *tab,
+                              unsigned long long *census, hipStream_t st) {
+  if (n_hp <= 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(hdr, 0, (size_t)2 * n_hp * sizeof(TabHdr), st);
+  if (e != hipSuccess) return e;
+  k_table_build<<<dim3(kTabMaxPanels, 2 * n_hp), kTabThreads, 0, st>>>(hps, info, coef, kcap, hdr,
+                                                                       tab, census);
+  return hipGetLastError();
+}
+
 }  // namespace tpe

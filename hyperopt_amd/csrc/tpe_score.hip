@@ -1594,9 +1594,58 @@ __device__ __forceinline__ void publish_arrive(const ScoreArgs &A) {
 
 // (SM: ScoreSmem, or ScoreSmem1 for the one-row wave tiles, whose
 // workgroup stages both mixtures' tables in LDS when they fit kStageBlocks)
-template <int KIND, bool CENSUS, typename SM, bool LDRAW = false, bool TDRAW = false, int MW = 16>
+// Both mixtures of the lane's candidates from the slots' Chebyshev tables
+// (TabHdr, k_table_build): panel p = floor((y' - y_lo) / width) clamped to
+// the table, local coordinate t in [-1, 1], a 16-term fp64 Clenshaw sum of the
+// panel's coefficients (per-lane vector loads: a wave's bucketed candidates
+// share one or two panels).  The result is the LseAcc{M_p, s} the component
+// loops would leave; a NaN candidate gives NaN.
+__device__ __forceinline__ bool tab_valid(const TabHdr &h) {
+  return h.P > 0 && h.ncert == (uint32_t)h.P;
+}
+template <int KR>
+__device__ __forceinline__ void tab_eval(const TabHdr *__restrict__ hdr,
+                                         const TabPanel *__restrict__ tab, int64_t slot,
+                                         const double (&y)[KR], LseAcc (&out)[KR]) {
+  const TabHdr h = hdr[slot];
+  const TabPanel *__restrict__ base = tab + slot * kTabMaxPanels;
+#pragma unroll
+  for (int r = 0; r < KR; ++r) {
+    const double u = (y[r] - h.y_lo) * h.inv_w;
+    const double pf = fmin(fmax(floor(u), 0.0), (double)(h.P - 1));
+    const double t = fmin(fmax(2.0 * (u - pf) - 1.0, -1.0), 1.0), t2 = t + t;
+    const double2 *__restrict__ cp = reinterpret_cast<const double2 *>(base + (int)pf);
+    double c[kTabNodes];
+#pragma unroll
+    for (int k = 0; k < kTabNodes / 2; ++k) {
+      const double2 v = cp[k];
+      c[2 * k] = v.x;
+      c[2 * k + 1] = v.y;
+    }
+    const double M = cp[kTabNodes / 2].x;
+    double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = kTabNodes - 1; k > 0; --k) {
+      const double b0 = fma(t2, b1, c[k] - b2);
+      b2 = b1;
+      b1 = b0;
+    }
+    const double sv = fma(t, b1, c[0] - b2);
+    out[r] = (y[r] != y[r]) ? LseAcc{NAN, NAN} : LseAcc{M, sv};
+  }
+}
+
+// TAB (k_score_table): the two-row wave tile of a slot whose two tables are
+// certified -- the candidate load and the finalize of the tile, the table sums
+// in place of the component loops.  The other slots' blocks return at entry
+// (ScoreArgs::tab_on).  For a suggest it leaves every wave's and the slot's
+// best table score, and k_score_wave_tie picks the winner (score_block).
+// TIEK (k_score_wave_tie): the direct tile of a table slot after its table
+// pass (score_block): only the waves reaching wthr take their candidates.
+template <int KIND, bool CENSUS, typename SM, bool LDRAW = false, bool TDRAW = false, int MW = 16,
+          bool TAB = false, bool TIEK = false>
 __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot, int tile,
-                                           int ntiles, bool known_active) {
+                                           int ntiles, bool known_active, double wthr = NAN) {
   constexpr bool STAGE = std::is_same<SM, ScoreSmem1>::value;
   constexpr int KR = tile_rows(KIND);
   constexpr bool LSE = kind_lse(KIND);
@@ -1609,6 +1658,11 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   const tpe_hp H = A.hps[hp];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   SSTAMP(0);
+  if constexpr (TAB) {  // block-uniform
+    if (A.tab_on != 2 &&
+        !(tab_valid(A.tab_hdr[2 * (int64_t)hp]) && tab_valid(A.tab_hdr[2 * (int64_t)hp + 1])))
+      return;
+  }
   const bool act = A.force_active || known_active ||
                    hp_active(H, A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch);
   if (!act) {  // one record says "inactive"; no tickets are taken
@@ -1635,7 +1689,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
     if (threadIdx.x == 0) sm.arrive = 0u;
     // small mixtures' coefficients (lse_small) into LDS: thread t of the first
     // 2 x kSmallMix copies component t % kSmallMix of mixture t / kSmallMix
-    if constexpr (LSE) {
+    if constexpr (LSE && !TAB) {
       // (wave 0, every lane: lanes 32q .. 32q + 31 hold mixture q.  The
       // bound mtop: every term t_k(y) is at most its peak alpha - beta^2 /
       // (4 gamma), so 2^(t - mtop) <= 1 for any candidate -- lse_small's one
@@ -1767,6 +1821,16 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   // candidates: the mapping changes no result.
   // (wave-uniform: a scalar, so the finalize can recompute li from it)
   const int wvs = __builtin_amdgcn_readfirstlane(wave);
+  // a table slot's tile in k_score_wave (score_block, wthr): only the waves
+  // whose best table score reaches the threshold score their candidates; the
+  // others take none (the empty sums of a wave past n_cand)
+  // (the flag waits in LDS for the finalize, like the wave's candidates)
+  constexpr bool TIE = TIEK && kind_wave_lse(KIND) && KR == 2 && MW == 16 && !TAB && !TDRAW;
+  bool cold = false;
+  if constexpr (TIE) {
+    cold = A.tab_wmax[(((int64_t)s * A.n_hp + hp) * A.pstride + tile) * kWaves + wvs] < wthr;
+    if (lane == 0) sm.red_n[wave] = cold ? 1 : 0;
+  }
   int64_t wt0 = (int64_t)tile * tile_cands(KIND) + (WT ? wvs * 64 * KR : 0);
   if constexpr (kind_wave_lse(KIND)) {
     static_assert((kSortedBlock >> kSortLog2Large) == 1 &&
@@ -1781,6 +1845,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   for (int r = 0; r < KR; ++r) {
     li[r] = wt0 + r * 64 + lane;
     valid[r] = li[r] < A.n_cand;
+    if constexpr (TIE) valid[r] = valid[r] && !cold;
     if constexpr (LDRAW && (LAT || KIND == KIND_CAT)) {
       // (self-drawing lookups: the scan in the finalize below, lookup_scan,
       // draws and scores its own candidates; nothing is read here)
@@ -1810,7 +1875,27 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
     }
   }
 
-  if constexpr (LSE || ERF) {
+  if constexpr (TAB) {
+    static_assert(!TAB || (kind_wave_lse(KIND) && KR == 2), "two-row wave tiles");
+#pragma unroll
+    for (int mix = 0; mix < 2; ++mix) {
+      LseAcc acc[KR];
+      tab_eval<KR>(A.tab_hdr, A.tab, mix ? sa : sb, y, acc);
+#pragma unroll
+      for (int r = 0; r < KR; ++r) sm.wpart[mix][wave][r][lane] = make_double2(acc[r].m, acc[r].s);
+    }
+    if constexpr (CENSUS) {
+      unsigned long long c = 0;
+#pragma unroll
+      for (int r = 0; r < KR; ++r) c += valid[r] ? (unsigned long long)(ib.K + ia.K) : 0ull;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+      if (lane == 0) {
+        atomicAdd(A.census + 3, c);
+        atomicAdd(A.census + 12, c);
+      }
+    }
+  } else if constexpr (LSE || ERF) {
     // warm this XCD's L2 with both mixtures' coefficient lines: one dword per
     // 128-B line, issued before the component loop, so the loop's scalar loads
     // hit L2 instead of each group paying a far (MALL / HBM) round trip
@@ -2118,6 +2203,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
       const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
       li[r] = wt0 + r * 64 + ln;
       valid[r] = li[r] < A.n_cand;
+      if constexpr (TIE) valid[r] = valid[r] && sm.red_n[wave] == 0;
       asm volatile("" ::: "memory");  // (a reload, not the stored register)
       x[r] = sm.xs[wave][r][ln];
     }
@@ -2219,6 +2305,10 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
     // the last to arrive merges the 8 records (better() orders ties by index,
     // so arrival order does not matter) and publishes the tile -- the other
     // waves exit at once instead of waiting for the block's slowest wave
+    if constexpr (TAB) {  // the wave's best table score, for k_score_wave's pass
+      if (lane == 0 && A.tab_on != 2)
+        A.tab_wmax[(((int64_t)s * A.n_hp + hp) * A.pstride + tile) * kWaves + wave] = best_s;
+    }
     if (lane == 0) {
       sm.best_s[wave] = best_s;
       sm.best_v[wave] = best_v;
@@ -2343,6 +2433,12 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   }
 #else
   wave_best(fs, fv, fi);
+  if constexpr (TAB) {  // a suggest's table pass leaves the slot's best table score
+    if (A.tab_on != 2) {  // (its result comes from k_score_wave's pass over the records)
+      if (lane == 0) A.tab_max[(int64_t)s * A.n_hp + hp] = fs;
+      return;
+    }
+  }
   if (lane == 0) {
     Partial *rr = A.results + (int64_t)s * A.n_hp + hp;
     if (TDRAW && A.pub_flag) store_record_sc1(rr, Partial{fs, fv, fi, 1, 0});  // (never accumulating)
@@ -2439,9 +2535,44 @@ __device__ __forceinline__ void mark_inactive(const ScoreArgs &A, int s, int s0,
 // erf ones, every kind, or only the wave-tile log-sum-exp kinds (levels of
 // large draws whose every slot is one: a kernel with only their register
 // allocation -- the combined one keeps the most any kind needs).
-enum { kSetNoErf = 0, kSetAll = 1, kSetWave = 2, kSetWave1 = 3, kSetLookup = 4, kSetTiny = 5 };
+enum { kSetNoErf = 0, kSetAll = 1, kSetWave = 2, kSetWave1 = 3, kSetLookup = 4, kSetTiny = 5,
+       kSetTable = 6 };
 
-template <int SET, bool CENSUS, typename SM, int MW = 16>
+// The arrival of a tile whose record is already in place (a table slot's tile
+// that k_score_wave leaves to its table record): wave 0 takes the tile's
+// ticket and, if it is the slot's last, merges the records -- the tail of
+// score_tile without a record of its own.
+constexpr double kTabTie = 0x1p-16;  // ~25x the one-exponent form's 6e-7 on a score
+__device__ __forceinline__ void tile_arrive_kept(const ScoreArgs &A, int s, int hp, int nrec) {
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  Partial *pbase = A.partial + ((int64_t)s * A.n_hp + hp) * A.pstride;
+  int is_last = 0;
+  if (lane == 0) {
+    gu32 *tk = (gu32 *)(uintptr_t)(A.ticket + (int64_t)s * A.n_hp + hp);
+    const uint32_t t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = (t == (uint32_t)nrec - 1) ? 1 : 0;
+    if (is_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (!__shfl(is_last, 0, 64)) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  double fs = NAN, fv = NAN;
+  int64_t fi = -1;
+  for (int i = lane; i < nrec; i += 64) {
+    gu64 *rec = (gu64 *)(uintptr_t)(pbase + i);
+    const double qs = bitsd(__hip_atomic_load(rec + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const double qv = bitsd(__hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const int64_t qi = (int64_t)__hip_atomic_load(rec + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    take_better(fs, fv, fi, qs, qv, qi);
+  }
+  wave_best(fs, fv, fi);
+  if (lane == 0) {
+    Partial *rr = A.results + (int64_t)s * A.n_hp + hp;
+    if (!(A.accumulate && better(rr->score, rr->index, fs, fi))) *rr = Partial{fs, fv, fi, 1, 0};
+  }
+}
+
+template <int SET, bool CENSUS, typename SM, int MW = 16, bool TIEK = false>
 __device__ __forceinline__ void score_block(const ScoreArgs &A, SM &sm) {
   const int b = blockIdx.x;
   int g = 0;
@@ -2458,10 +2589,51 @@ __device__ __forceinline__ void score_block(const ScoreArgs &A, SM &sm) {
     if (slot < 0) return;
   }
   const bool known = A.compact != 0;
+  double wthr = NAN;
+  if constexpr (SET == kSetWave && MW == 16 && TIEK) {
+    // a slot whose two Chebyshev tables are certified (tab_on; 16-wide plans
+    // only) has been through k_score_table: its tile records hold the table
+    // winners, tab_wmax every wave's best table score and tab_max the slot's.
+    // The winner of this kernel's own sums scores (by the tables, exact to
+    // ~1e-12) within the sums' error of tab_max, so only the waves reaching
+    // tab_max - kTabTie max(1, |tab_max|) score their candidates again, here,
+    // and the argmax over their records and the kept table records of the
+    // other tiles (all below the threshold) is the one this kernel alone
+    // would find.  A NaN on either side compares false: nothing is skipped.
+    {
+      // (an inactive hp has no table pass: score_tile writes its record)
+      const int hp = A.level_hps[slot];
+      const int s = blockIdx.y;
+      const bool act = A.force_active || known ||
+                       hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent,
+                                 A.cond_branch);
+      if (act && tab_valid(A.tab_hdr[2 * (int64_t)hp]) &&
+          tab_valid(A.tab_hdr[2 * (int64_t)hp + 1])) {
+        const double tm = A.tab_max[(int64_t)s * A.n_hp + hp];
+        wthr = tm - kTabTie * fmax(1.0, fabs(tm));
+        const double *wm = A.tab_wmax + (((int64_t)s * A.n_hp + hp) * A.pstride + tile) * kWaves;
+        bool cold = true;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) cold = cold && wm[w] < wthr;
+        if (cold) {  // block-uniform: the tile's table record stays
+          tile_arrive_kept(A, s, hp, nt);
+          return;
+        }
+      }
+    }
+  }
   if constexpr (SET == kSetWave) {
     if (A.grp_kind[g] == KIND_LSE_LW)
-      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, MW>(A, sm, slot, tile, nt, known);
-    else score_tile<KIND_LSE_GW, CENSUS, SM, false, false, MW>(A, sm, slot, tile, nt, known);
+      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, MW, false, TIEK>(A, sm, slot, tile, nt,
+                                                                         known, wthr);
+    else
+      score_tile<KIND_LSE_GW, CENSUS, SM, false, false, MW, false, TIEK>(A, sm, slot, tile, nt,
+                                                                         known, wthr);
+    return;
+  } else if constexpr (SET == kSetTable) {
+    if (A.grp_kind[g] == KIND_LSE_LW)
+      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, 16, true>(A, sm, slot, tile, nt, known);
+    else score_tile<KIND_LSE_GW, CENSUS, SM, false, false, 16, true>(A, sm, slot, tile, nt, known);
     return;
   } else if constexpr (SET == kSetLookup) {
     if (A.grp_kind[g] == KIND_LAT) score_tile<KIND_LAT, CENSUS, SM, true>(A, sm, slot, tile, nt, known);
@@ -2521,6 +2693,20 @@ __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu(TPE
 void k_score_wave(ScoreArgs A) {
   __shared__ ScoreSmem sm;
   score_block<kSetWave, CENSUS, ScoreSmem, MW>(A, sm);
+}
+// k_score_wave<., 16> after a table pass (tab_on 1), in a kernel of its own:
+// k_score_wave itself stays the kernel, and the register allocation, it was
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu(TPE_WAVE_EU)))
+void k_score_wave_tie(ScoreArgs A) {
+  __shared__ ScoreSmem sm;
+  score_block<kSetWave, CENSUS, ScoreSmem, 16, true>(A, sm);
+}
+// the same tiles of the slots scored from their Chebyshev tables (tab_on)
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) void k_score_table(ScoreArgs A) {
+  __shared__ ScoreSmem sm;
+  score_block<kSetTable, CENSUS, ScoreSmem, 16>(A, sm);
 }
 // the one-row wave tiles (KIND_LSE_GW1 / LW1) in a kernel of their own: the
 // two-row kernel's register allocation is left as it is
@@ -2802,6 +2988,15 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
       else k_score_wave1<false, 16><<<g, kWaves * 64, 0, st>>>(a);
     }
   } else if (cls == 0) {
+    if (a.tab_on) {  // the table pass of the certified slots, then the direct pass
+      if (a.census) k_score_table<true><<<g, kWaves * 64, 0, st>>>(a);
+      else k_score_table<false><<<g, kWaves * 64, 0, st>>>(a);
+      if (a.tab_on == 2) return hipGetLastError();
+      // (gated on the 16-wide class: the direct pass that follows the tables)
+      if (a.census) k_score_wave_tie<true><<<g, kWaves * 64, 0, st>>>(a);
+      else k_score_wave_tie<false><<<g, kWaves * 64, 0, st>>>(a);
+      return hipGetLastError();
+    }
     if (m8) {
       if (a.census) k_score_wave<true, 8><<<g, kWaves * 64, 0, st>>>(a);
       else k_score_wave<false, 8><<<g, kWaves * 64, 0, st>>>(a);

@@ -260,7 +260,10 @@ int tpe_plan_score_candidates(tpe_plan_t p, int32_t hp, const double *x,
  * k_draw_sorted buckets its draws, then scored on the same tiles with
  * log-sum-exp prune mode `mode` (tpe_plan_set_prune: 0 every pair, 1 block
  * skip, 2 block skip + one exponent per wave, 3 the same in block-local
- * fp32).  Outputs are in the given
+ * fp32; 4: mode 3's tiles scored from the hp's certified Chebyshev tables of
+ * both mixtures alone, as suggestions of more than 2^18 candidates score a
+ * bounded continuous hp -- TPE_E_INVALID when the hp takes no table or a
+ * side's table is not certified).  Outputs are in the given
  * order.  The parity path of tpe.py:139-144 / 253-256 as the suggest
  * computes it at config 4.                                                 */
 int tpe_plan_score_candidates_sorted(tpe_plan_t p, int32_t hp, int32_t mode,
@@ -303,7 +306,9 @@ int tpe_plan_set_lattice(tpe_plan_t p, int32_t enable);
  * zeros; a wave's retried pass counts again) -- and switch the census on (enable != 0)
  * or off for the following suggests.  counts has 6 entries.               */
 int tpe_plan_census(tpe_plan_t p, int32_t enable, int64_t *counts);
-/* The same with n_counts entries (up to 12): [6] of [5] the log-sum-exp pairs
+/* The same with n_counts entries (up to 13; [12]: the pairs credited to
+ * candidates scored from the Chebyshev tables, also counted in [3], while
+ * the table build's (node, component) pairs go into [3] and [5]): [6] of [5] the log-sum-exp pairs
  * evaluated in the block-local fp32 per-group-lift form (prune mode 3 on
  * mixtures below the one-exponent size), [7] of [4] the one-exponent pairs
  * evaluated again by a wave's second attempt (its exponent re-centred),
