@@ -42,6 +42,7 @@ EXPORTS = (
     'tpe_plan_results_device', 'tpe_plan_census', 'tpe_plan_fit_suggest',
     'tpe_plan_set_lattice', 'tpe_plan_update_history', 'tpe_plan_set_prune',
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
+    'tpe_plan_tie_counts',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -156,6 +157,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_results_device': (vp, [vp]),
             'tpe_plan_census': (C.c_int, [vp, i32, C.POINTER(i64)]),
             'tpe_plan_census_n': (C.c_int, [vp, i32, C.POINTER(i64), i32]),
+            'tpe_plan_tie_counts': (C.c_int, [vp, i32, vp]),
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
             'tpe_plan_set_prune': (C.c_int, [vp, i32]),
             'tpe_plan_sample_prior': (C.c_int, [vp, C.POINTER(u64), i64, vp, i32, vp]),
@@ -587,6 +589,18 @@ class Plan(object):
         with e.lock:
             e.check(e.lib.tpe_plan_census_n(self.p, int(bool(enable)), out, int(n)))
         return tuple(int(v) for v in out[:n])
+
+    def tie_counts(self, n_suggest):
+        """Debug (tpe_plan_tie_counts): int32 [n_suggest][n_hp], the 128-candidate
+        wave tiles the direct pass behind the Chebyshev tables scored per hp in
+        the last scoring launch that took them -- the tiles in the tie window
+        of a certified slot, every tile of another, 0 for an inactive hp, -1
+        where no such launch has scored the hp."""
+        e = self.engine
+        out = np.empty((int(n_suggest), self.n_hp), dtype=np.int32)
+        with e.lock:
+            e.check(e.lib.tpe_plan_tie_counts(self.p, int(n_suggest), out.ctypes.data))
+        return out
 
     def last_stats(self):
         e = self.engine

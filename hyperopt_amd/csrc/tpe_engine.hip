@@ -105,6 +105,7 @@ static bool side_streams_on() {
 }
 static bool moment_on();
 static bool table_on();
+static double table_tie();
 // TPE_MOMENT_H=0: 16-wide plans without the degree-15 chunk table (A/B)
 static bool moment_h_on() {
   static const bool on = [] {
@@ -160,6 +161,8 @@ struct tpe_plan {
   TabPanel *d_tab = nullptr;    // [2P][kTabMaxPanels]
   double *d_tab_max = nullptr;  // [s_cap][P] best table score per slot (ScoreArgs::tab_max)
   double *d_tab_wmax = nullptr; // [partial_cap][8] ... per wave tile
+  int32_t *d_tie_list = nullptr; // [partial_cap][8] the direct pass's wave tiles (ScoreArgs::tie_list)
+  int32_t *d_tie_cnt = nullptr;  // [s_cap][P] ... and their number per slot (-1: never gathered)
   bool tab_built = false;
   bool graph_tab = false;       // the captured graph holds the build
   std::vector<double> act_frac;  // per hp: expected share of the trials it is active in
@@ -298,7 +301,7 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_partial, p->d_ext, p->d_lb, p->d_la, p->d_cand, p->d_cpos,
                   p->d_ticket, p->d_sortbuf, p->d_census, p->d_lat_info, p->d_lat, p->d_coef32, p->d_coefm,
                   p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
-                  p->d_tab_max, p->d_tab_wmax};
+                  p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -545,6 +548,10 @@ int ensure_suggest_state(tpe_engine *h, tpe_plan *p, int64_t n_sug, size_t parti
     dfree(p->d_tab_max);
     p->d_tab_max = nullptr;
     CKH(dalloc(&p->d_tab_max, (size_t)n_sug * p->P));
+    dfree(p->d_tie_cnt);
+    p->d_tie_cnt = nullptr;
+    CKH(dalloc(&p->d_tie_cnt, (size_t)n_sug * p->P));
+    CKH(hipMemset(p->d_tie_cnt, 0xff, (size_t)n_sug * p->P * sizeof(int32_t)));
     p->s_cap = n_sug;
   }
   if (partials > p->partial_cap) {
@@ -554,6 +561,9 @@ int ensure_suggest_state(tpe_engine *h, tpe_plan *p, int64_t n_sug, size_t parti
     dfree(p->d_tab_wmax);
     p->d_tab_wmax = nullptr;
     CKH(dalloc(&p->d_tab_wmax, partials * 8));  // (one per wave of a tile)
+    dfree(p->d_tie_list);
+    p->d_tie_list = nullptr;
+    CKH(dalloc(&p->d_tie_list, partials * 8));
     p->partial_cap = partials;
   }
   return TPE_OK;
@@ -721,6 +731,9 @@ ScoreArgs base_args(tpe_plan *p, int64_t n_sug) {
   a.tab = p->d_tab;
   a.tab_max = p->d_tab_max;
   a.tab_wmax = p->d_tab_wmax;
+  a.tie_list = p->d_tie_list;
+  a.tie_cnt = p->d_tie_cnt;
+  a.tab_tie = table_tie();
   return a;
 }
 
@@ -2199,6 +2212,18 @@ int tpe_plan_census_n(tpe_plan_t p, int32_t enable, int64_t *counts, int32_t n_c
   return TPE_OK;
 }
 
+int tpe_plan_tie_counts(tpe_plan_t p, int32_t n_suggest, int32_t *counts) {
+  if (!p || !counts || n_suggest < 0) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (n_suggest > p->s_cap) return fail(h, TPE_E_INVALID, "more suggestions than the last call's");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  if (n_suggest > 0)
+    CKH(hipMemcpy(counts, p->d_tie_cnt, (size_t)n_suggest * p->P * sizeof(int32_t),
+                  hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
 int tpe_plan_sample_prior(tpe_plan_t p, const uint64_t *seeds, int64_t n_sug, tpe_result *out,
                           int32_t out_on_device, void *stream) {
   if (!p) return TPE_E_INVALID;
@@ -2261,6 +2286,17 @@ static bool table_on() {
   static const bool v = [] {
     const char *e = std::getenv("TPE_TABLE");
     return !(e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+
+// the tie window of the direct pass behind the tables: a wave is scored again
+// when its best table score is within 2^TPE_TABLE_TIE_LOG2 max(1, |best|) of
+// the slot's (default -16, kTabTie; a huge value makes every wave hot: tests)
+static double table_tie() {
+  static const double v = [] {
+    const char *e = std::getenv("TPE_TABLE_TIE_LOG2");
+    return e ? std::ldexp(1.0, (int)std::max(-1074L, std::min(4096L, std::atol(e)))) : kTabTie;
   }();
   return v;
 }

@@ -266,6 +266,9 @@ struct __attribute__((aligned(16))) TabPanel {
   double pad;
 };
 static_assert(sizeof(TabHdr) == 32 && sizeof(TabPanel) == 144, "table layout");
+// the direct pass behind a suggest's table pass scores again the waves whose
+// best table score is within kTabTie max(1, |best|) of the slot's best
+constexpr double kTabTie = 0x1p-16;  // ~25x the one-exponent form's 6e-7 on a score
 // the hps a table is built for
 __host__ __device__ inline bool table_hp(const tpe_hp &h) {
   return (h.family == TPE_GMM || h.family == TPE_LGMM) && !(h.flags & TPE_HAS_Q) &&
@@ -369,14 +372,22 @@ struct ScoreArgs {
   const double2 *lat;        // lattice (lpdf below, lpdf above) pairs
   // Chebyshev tables (k_table_build): tab_on 1 -- a two-row wave-tile slot
   // whose two tables are certified is scored by k_score_table, and
-  // k_score_wave scores again only the waves within the sums' own error of the
-  // slot's best table score, so the winner is the one its sums alone give; 2 -- the operator form (k_score_table alone, the host has
-  // checked the slot's tables); 0 -- no tables
+  // k_score_wave_tie scores again only the wave tiles within the sums' own
+  // error of the slot's best table score (gathered into dense blocks by
+  // k_tie_gather), so the winner is the one its sums alone give; 2 -- the
+  // operator form (k_score_table alone, the host has checked the slot's
+  // tables); 0 -- no tables
   const TabHdr *tab_hdr;     // [2*P]
   const TabPanel *tab;       // [2*P][kTabMaxPanels]
   int32_t tab_on;
   double *tab_max;           // [S][P] tab_on 1: the slot's best table score of this launch
-  double *tab_wmax;          // [S][P][pstride][8] ... and every wave tile's
+  double *tab_wmax;          // [S][P][pstride * 8] ... and every wave tile's, by wave-tile number
+  // tab_on 1, between the two passes (k_tie_gather): the slot's wave tiles the
+  // direct pass scores, 8 per block in list order -- the hot ones of a
+  // certified slot in ascending order, every one of any other slot
+  int32_t *tie_list;         // [S][P][pstride * 8] wave-tile numbers
+  int32_t *tie_cnt;          // [S][P] entries of the list (0: inactive hp)
+  double tab_tie;            // the tie window's relative width (kTabTie; TPE_TABLE_TIE_LOG2)
   // a tile_draw launch that ends its call (pub_flag non-null): the last of its
   // pub_events final records copies all pub_words words of results into the
   // pinned pub_dst and then stores pub_seq into *pub_flag -- k_publish's

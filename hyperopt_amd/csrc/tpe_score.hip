@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "tpe_device.hpp"
@@ -1638,14 +1639,19 @@ __device__ __forceinline__ void tab_eval(const TabHdr *__restrict__ hdr,
 // TAB (k_score_table): the two-row wave tile of a slot whose two tables are
 // certified -- the candidate load and the finalize of the tile, the table sums
 // in place of the component loops.  The other slots' blocks return at entry
-// (ScoreArgs::tab_on).  For a suggest it leaves every wave's and the slot's
-// best table score, and k_score_wave_tie picks the winner (score_block).
-// TIEK (k_score_wave_tie): the direct tile of a table slot after its table
-// pass (score_block): only the waves reaching wthr take their candidates.
+// (ScoreArgs::tab_on).  This form (tab_on 2) is the operator's: its records
+// are the result.
+// TMAP (with TAB; k_score_table<., true>, tab_on 1): the table pass of a
+// suggest decides nothing -- every wave leaves its best table score in
+// tab_wmax (by wave-tile number) and is done: no positions, no block merge,
+// no tile record, no ticket.
+// TIEK (k_score_wave_tie): block `tile` of the slot's `ntiles` gathered blocks
+// (k_tie_gather): wave w scores the wave tile of list entry 8 tile + w, a
+// wave past the list's end none.  Grid (., row, suggestion).
 template <int KIND, bool CENSUS, typename SM, bool LDRAW = false, bool TDRAW = false, int MW = 16,
-          bool TAB = false, bool TIEK = false>
+          bool TAB = false, bool TIEK = false, bool TMAP = false>
 __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot, int tile,
-                                           int ntiles, bool known_active, double wthr = NAN) {
+                                           int ntiles, bool known_active) {
   constexpr bool STAGE = std::is_same<SM, ScoreSmem1>::value;
   constexpr int KR = tile_rows(KIND);
   constexpr bool LSE = kind_lse(KIND);
@@ -1653,7 +1659,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   constexpr bool ERF = KIND == KIND_ERF_G || KIND == KIND_ERF_L;
   constexpr bool LAT = KIND == KIND_LAT;  // quantized, looked up on its value lattice
   constexpr bool LOGN = kind_logn(KIND);
-  const int s = blockIdx.y;
+  const int s = TIEK ? blockIdx.z : blockIdx.y;
   const int hp = A.level_hps[slot];
   const tpe_hp H = A.hps[hp];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1666,6 +1672,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   const bool act = A.force_active || known_active ||
                    hp_active(H, A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch);
   if (!act) {  // one record says "inactive"; no tickets are taken
+    if constexpr (TMAP) return;  // (k_tie_gather writes it)
     if constexpr (TDRAW) {  // (its final record: one arrival)
       if (A.pub_flag) {
         if (tile == 0 && threadIdx.x < 64) {
@@ -1685,7 +1692,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   // staged tables (one-row wave tiles): below blocks [0, nbb), above after
   const int nbb = (ib.K + kCoefBlock - 1) / kCoefBlock, nba = (ia.K + kCoefBlock - 1) / kCoefBlock;
   bool staged = false;
-  if constexpr (WT) {  // the block's arrival counter (finalize), before any wave can arrive
+  if constexpr (WT && !TMAP) {  // the block's arrival counter (finalize), before any wave can arrive
     if (threadIdx.x == 0) sm.arrive = 0u;
     // small mixtures' coefficients (lse_small) into LDS: thread t of the first
     // 2 x kSmallMix copies component t % kSmallMix of mixture t / kSmallMix
@@ -1748,8 +1755,9 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   const double *__restrict__ cand = A.cand + coff;
   // value-bucketed candidates (k_bucket, or the sorted draw) carry their
   // chunk positions: the quantized kinds always, log-sum-exp when lse_pos
+  // (TMAP: only the score is kept, never an index)
   const int32_t *__restrict__ cpos =
-      ((ERF || (LSE && A.lse_pos)) && A.cand_pos) ? A.cand_pos + coff : nullptr;
+      (!TMAP && (ERF || (LSE && A.lse_pos)) && A.cand_pos) ? A.cand_pos + coff : nullptr;
 
   // lookup slots drawn here (ScoreArgs::lookup_draw): the below mixture's
   // draw table in LDS (block-wide, before any wave can arrive), then each
@@ -1821,18 +1829,21 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   // candidates: the mapping changes no result.
   // (wave-uniform: a scalar, so the finalize can recompute li from it)
   const int wvs = __builtin_amdgcn_readfirstlane(wave);
-  // a table slot's tile in k_score_wave (score_block, wthr): only the waves
-  // whose best table score reaches the threshold score their candidates; the
-  // others take none (the empty sums of a wave past n_cand)
+  // a gathered block of k_score_wave_tie: the wave's tile is its list entry;
+  // a wave past the list's end takes no candidates (the empty sums of a wave
+  // past n_cand)
   // (the flag waits in LDS for the finalize, like the wave's candidates)
   constexpr bool TIE = TIEK && kind_wave_lse(KIND) && KR == 2 && MW == 16 && !TAB && !TDRAW;
+  static_assert(TIE == TIEK, "k_score_wave_tie runs two-row 16-wide wave tiles only");
   bool cold = false;
-  if constexpr (TIE) {
-    cold = A.tab_wmax[(((int64_t)s * A.n_hp + hp) * A.pstride + tile) * kWaves + wvs] < wthr;
-    if (lane == 0) sm.red_n[wave] = cold ? 1 : 0;
-  }
   int64_t wt0 = (int64_t)tile * tile_cands(KIND) + (WT ? wvs * 64 * KR : 0);
-  if constexpr (kind_wave_lse(KIND)) {
+  if constexpr (TIE) {
+    const int64_t sh = (int64_t)s * A.n_hp + hp;
+    const int e = tile * kWaves + wvs;
+    cold = e >= A.tie_cnt[sh];
+    if (lane == 0) sm.red_n[wave] = cold ? 1 : 0;
+    wt0 = cold ? 0 : (int64_t)A.tie_list[sh * A.pstride * kWaves + e] * (64 * KR);
+  } else if constexpr (kind_wave_lse(KIND)) {
     static_assert((kSortedBlock >> kSortLog2Large) == 1 &&
                       (1 << kSortLog2Small) % tile_cands(KIND) == 0,
                   "blocks tile the sort block");
@@ -2299,16 +2310,17 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   wave_best(best_s, best_v, best_i);
 #endif
   if constexpr (WT) WSTAMP(8);
+  if constexpr (TMAP) {  // the wave's best table score, for k_tie_gather: all it leaves
+    if (lane == 0)
+      A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * kWaves + wt0 / (64 * KR)] = best_s;
+    return;
+  }
   if constexpr (WT) {
     // the block's argmax over its wave tiles without a block barrier: each
     // wave leaves its record in LDS and arrives on the block's LDS counter;
     // the last to arrive merges the 8 records (better() orders ties by index,
     // so arrival order does not matter) and publishes the tile -- the other
     // waves exit at once instead of waiting for the block's slowest wave
-    if constexpr (TAB) {  // the wave's best table score, for k_score_wave's pass
-      if (lane == 0 && A.tab_on != 2)
-        A.tab_wmax[(((int64_t)s * A.n_hp + hp) * A.pstride + tile) * kWaves + wave] = best_s;
-    }
     if (lane == 0) {
       sm.best_s[wave] = best_s;
       sm.best_v[wave] = best_v;
@@ -2433,12 +2445,6 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
   }
 #else
   wave_best(fs, fv, fi);
-  if constexpr (TAB) {  // a suggest's table pass leaves the slot's best table score
-    if (A.tab_on != 2) {  // (its result comes from k_score_wave's pass over the records)
-      if (lane == 0) A.tab_max[(int64_t)s * A.n_hp + hp] = fs;
-      return;
-    }
-  }
   if (lane == 0) {
     Partial *rr = A.results + (int64_t)s * A.n_hp + hp;
     if (TDRAW && A.pub_flag) store_record_sc1(rr, Partial{fs, fv, fi, 1, 0});  // (never accumulating)
@@ -2536,43 +2542,9 @@ __device__ __forceinline__ void mark_inactive(const ScoreArgs &A, int s, int s0,
 // large draws whose every slot is one: a kernel with only their register
 // allocation -- the combined one keeps the most any kind needs).
 enum { kSetNoErf = 0, kSetAll = 1, kSetWave = 2, kSetWave1 = 3, kSetLookup = 4, kSetTiny = 5,
-       kSetTable = 6 };
+       kSetTable = 6, kSetTableMap = 7 };
 
-// The arrival of a tile whose record is already in place (a table slot's tile
-// that k_score_wave leaves to its table record): wave 0 takes the tile's
-// ticket and, if it is the slot's last, merges the records -- the tail of
-// score_tile without a record of its own.
-constexpr double kTabTie = 0x1p-16;  // ~25x the one-exponent form's 6e-7 on a score
-__device__ __forceinline__ void tile_arrive_kept(const ScoreArgs &A, int s, int hp, int nrec) {
-  if (threadIdx.x >= 64) return;
-  const int lane = threadIdx.x;
-  Partial *pbase = A.partial + ((int64_t)s * A.n_hp + hp) * A.pstride;
-  int is_last = 0;
-  if (lane == 0) {
-    gu32 *tk = (gu32 *)(uintptr_t)(A.ticket + (int64_t)s * A.n_hp + hp);
-    const uint32_t t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    is_last = (t == (uint32_t)nrec - 1) ? 1 : 0;
-    if (is_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!__shfl(is_last, 0, 64)) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  double fs = NAN, fv = NAN;
-  int64_t fi = -1;
-  for (int i = lane; i < nrec; i += 64) {
-    gu64 *rec = (gu64 *)(uintptr_t)(pbase + i);
-    const double qs = bitsd(__hip_atomic_load(rec + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const double qv = bitsd(__hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const int64_t qi = (int64_t)__hip_atomic_load(rec + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    take_better(fs, fv, fi, qs, qv, qi);
-  }
-  wave_best(fs, fv, fi);
-  if (lane == 0) {
-    Partial *rr = A.results + (int64_t)s * A.n_hp + hp;
-    if (!(A.accumulate && better(rr->score, rr->index, fs, fi))) *rr = Partial{fs, fv, fi, 1, 0};
-  }
-}
-
-template <int SET, bool CENSUS, typename SM, int MW = 16, bool TIEK = false>
+template <int SET, bool CENSUS, typename SM, int MW = 16>
 __device__ __forceinline__ void score_block(const ScoreArgs &A, SM &sm) {
   const int b = blockIdx.x;
   int g = 0;
@@ -2589,46 +2561,18 @@ __device__ __forceinline__ void score_block(const ScoreArgs &A, SM &sm) {
     if (slot < 0) return;
   }
   const bool known = A.compact != 0;
-  double wthr = NAN;
-  if constexpr (SET == kSetWave && MW == 16 && TIEK) {
-    // a slot whose two Chebyshev tables are certified (tab_on; 16-wide plans
-    // only) has been through k_score_table: its tile records hold the table
-    // winners, tab_wmax every wave's best table score and tab_max the slot's.
-    // The winner of this kernel's own sums scores (by the tables, exact to
-    // ~1e-12) within the sums' error of tab_max, so only the waves reaching
-    // tab_max - kTabTie max(1, |tab_max|) score their candidates again, here,
-    // and the argmax over their records and the kept table records of the
-    // other tiles (all below the threshold) is the one this kernel alone
-    // would find.  A NaN on either side compares false: nothing is skipped.
-    {
-      // (an inactive hp has no table pass: score_tile writes its record)
-      const int hp = A.level_hps[slot];
-      const int s = blockIdx.y;
-      const bool act = A.force_active || known ||
-                       hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent,
-                                 A.cond_branch);
-      if (act && tab_valid(A.tab_hdr[2 * (int64_t)hp]) &&
-          tab_valid(A.tab_hdr[2 * (int64_t)hp + 1])) {
-        const double tm = A.tab_max[(int64_t)s * A.n_hp + hp];
-        wthr = tm - kTabTie * fmax(1.0, fabs(tm));
-        const double *wm = A.tab_wmax + (((int64_t)s * A.n_hp + hp) * A.pstride + tile) * kWaves;
-        bool cold = true;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) cold = cold && wm[w] < wthr;
-        if (cold) {  // block-uniform: the tile's table record stays
-          tile_arrive_kept(A, s, hp, nt);
-          return;
-        }
-      }
-    }
-  }
   if constexpr (SET == kSetWave) {
     if (A.grp_kind[g] == KIND_LSE_LW)
-      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, MW, false, TIEK>(A, sm, slot, tile, nt,
-                                                                         known, wthr);
+      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, MW>(A, sm, slot, tile, nt, known);
+    else score_tile<KIND_LSE_GW, CENSUS, SM, false, false, MW>(A, sm, slot, tile, nt, known);
+    return;
+  } else if constexpr (SET == kSetTableMap) {
+    if (A.grp_kind[g] == KIND_LSE_LW)
+      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, 16, true, false, true>(A, sm, slot, tile,
+                                                                               nt, known);
     else
-      score_tile<KIND_LSE_GW, CENSUS, SM, false, false, MW, false, TIEK>(A, sm, slot, tile, nt,
-                                                                         known, wthr);
+      score_tile<KIND_LSE_GW, CENSUS, SM, false, false, 16, true, false, true>(A, sm, slot, tile,
+                                                                               nt, known);
     return;
   } else if constexpr (SET == kSetTable) {
     if (A.grp_kind[g] == KIND_LSE_LW)
@@ -2696,17 +2640,172 @@ void k_score_wave(ScoreArgs A) {
 }
 // k_score_wave<., 16> after a table pass (tab_on 1), in a kernel of its own:
 // k_score_wave itself stays the kernel, and the register allocation, it was
+// Row `row` of a launch's rows -- every group's slots (its block rows, on a
+// compact grid) one after the other -- as (group, row within it).
+__device__ __forceinline__ int row_group(const ScoreArgs &A, int &row) {
+  int g = 0;
+  for (; g + 1 < A.n_groups; ++g) {
+    const int rows = (A.grp_block0[g + 1] - A.grp_block0[g]) / A.grp_tiles[g];
+    if (row < rows) break;
+    row -= rows;
+  }
+  return g;
+}
+// Grid (G, rows, suggestions).  The slot's list (k_tie_gather) holds the wave
+// tiles to score directly, 8 per gathered block: block x runs the gathered
+// blocks x, x + G, ... of its slot, one after the other, each with the
+// per-block LDS state set up again behind a barrier.  Gathered block j leaves
+// its record in partial[j]; the slot's ticket counts the nblk of them, and
+// the last to arrive merges them into results.  (No list entries -- an
+// inactive hp, whose record the gather wrote: nothing to do, no ticket.)
 template <bool CENSUS>
 __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu(TPE_WAVE_EU)))
 void k_score_wave_tie(ScoreArgs A) {
   __shared__ ScoreSmem sm;
-  score_block<kSetWave, CENSUS, ScoreSmem, 16, true>(A, sm);
+  const int s = blockIdx.z;
+  int row = blockIdx.y;
+  const int g = row_group(A, row);
+  int slot = A.grp_slot0[g] + row;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], row);
+    if (slot < 0) return;
+  }
+  const int cnt = A.tie_cnt[(int64_t)s * A.n_hp + A.level_hps[slot]];
+  const int nblk = (cnt + kWaves - 1) / kWaves;
+  const bool lw = A.grp_kind[g] == KIND_LSE_LW;
+  for (int j = blockIdx.x; j < nblk; j += gridDim.x) {
+    if (j != (int)blockIdx.x) __syncthreads();  // the last block's LDS records have been read
+    // (the slot through an opaque copy: what a tile derives from it is worked
+    // out again in every iteration, as in a block of its own, instead of
+    // staying in registers across the loop -- 167 spilled VGPRs, 187 without)
+    int sl = slot;
+    asm volatile("" : "+s"(sl));
+    if (lw)
+      score_tile<KIND_LSE_LW, CENSUS, ScoreSmem, false, false, 16, false, true>(A, sm, sl, j,
+                                                                                nblk, true);
+    else
+      score_tile<KIND_LSE_GW, CENSUS, ScoreSmem, false, false, 16, false, true>(A, sm, sl, j,
+                                                                                nblk, true);
+  }
 }
-// the same tiles of the slots scored from their Chebyshev tables (tab_on)
-template <bool CENSUS>
+// the same tiles of the slots scored from their Chebyshev tables (tab_on 2:
+// the operator form; MAP, tab_on 1: a suggest's per-wave map, score_tile TMAP)
+template <bool CENSUS, bool MAP = false>
 __global__ __launch_bounds__(kWaves * 64) void k_score_table(ScoreArgs A) {
   __shared__ ScoreSmem sm;
-  score_block<kSetTable, CENSUS, ScoreSmem, 16>(A, sm);
+  score_block<MAP ? kSetTableMap : kSetTable, CENSUS, ScoreSmem, 16>(A, sm);
+}
+
+// Between the two passes of a tab_on 1 launch: one block per (row,
+// suggestion), no block waits on another.  An inactive hp gets its
+// "inactive" record and an empty list (its tab_wmax is stale: the table pass
+// returned at entry).  A slot whose two tables are certified: tab_max, the
+// best of its waves' table scores in better()'s order on scores (a NaN ranks
+// first; the waves past n_cand hold no record), then the list of its hot
+// wave tiles -- !(wmax < tab_max - tab_tie max(1, |tab_max|)), so a NaN on
+// either side keeps the wave -- in ascending order, by a block scan.  Any
+// other slot: every wave tile, in the order of k_score_wave's interleaved
+// wave -> tile mapping, so its gathered blocks are the blocks of that kernel.
+constexpr int kGatherThreads = 1024;
+__global__ __launch_bounds__(kGatherThreads) void k_tie_gather(ScoreArgs A) {
+  constexpr int NW = kGatherThreads / 64;
+  constexpr int WC = 64 * tile_rows(KIND_LSE_GW);  // candidates per wave tile
+  static_assert(tile_rows(KIND_LSE_GW) == tile_rows(KIND_LSE_LW), "one wave-tile shape");
+  __shared__ double red_s[NW];
+  __shared__ int red_n[NW];
+  __shared__ int wsum[NW];
+  const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int row = blockIdx.x;
+  const int g = row_group(A, row);
+  const int nt = A.grp_tiles[g];
+  int slot = A.grp_slot0[g] + row;
+  if (A.compact) {
+    if (row == 0 && tid < 64) {  // (mark_inactive, with the empty lists)
+      Partial *res = A.results + (int64_t)s * A.n_hp;
+      for (int i = tid; i < A.grp_slots[g]; i += 64) {
+        const int hp = A.level_hps[A.grp_slot0[g] + i];
+        if (!hp_active(A.hps[hp], res, A.cond_parent, A.cond_branch)) {
+          res[hp] = Partial{NAN, NAN, -1, 0, 0};
+          A.tie_cnt[(int64_t)s * A.n_hp + hp] = 0;
+        }
+      }
+    }
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], row);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  const int64_t sh = (int64_t)s * A.n_hp + hp;
+  const bool act = A.force_active || A.compact ||
+                   hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent,
+                             A.cond_branch);
+  if (!act) {
+    if (tid == 0) {
+      A.results[sh] = Partial{NAN, NAN, -1, 0, 0};
+      A.tie_cnt[sh] = 0;
+    }
+    return;
+  }
+  const int ntw = nt * kWaves;  // the slot's wave tiles (<= pstride * kWaves)
+  int32_t *list = A.tie_list + sh * A.pstride * kWaves;
+  if (!(tab_valid(A.tab_hdr[2 * (int64_t)hp]) && tab_valid(A.tab_hdr[2 * (int64_t)hp + 1]))) {
+    // entry 8 j + w: wave w of tile j (score_tile's mapping)
+    const int SBB = (1 << A.sort_log2) / tile_cands(KIND_LSE_GW);
+    for (int e = tid; e < ntw; e += kGatherThreads) {
+      const int j = e / kWaves, w = e % kWaves;
+      const int sb = j / SBB, q = j % SBB;
+      const int nbs = min(SBB, nt - sb * SBB);
+      list[e] = sb * SBB * kWaves + q + nbs * w;
+    }
+    if (tid == 0) A.tie_cnt[sh] = ntw;
+    return;
+  }
+  const double *wm = A.tab_wmax + sh * A.pstride * kWaves;
+  const int nrec = (int)min<int64_t>(ntw, (A.n_cand + WC - 1) / WC);  // waves holding a record
+  double m = -INFINITY;
+  int nan = 0;
+  for (int i = tid; i < nrec; i += kGatherThreads) {
+    const double v = wm[i];
+    nan |= v != v;
+    m = fmax(m, v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m = fmax(m, __shfl_xor(m, o, 64));
+    nan |= __shfl_xor(nan, o, 64);
+  }
+  if (lane == 0) { red_s[wave] = m; red_n[wave] = nan; }
+  __syncthreads();
+  m = red_s[0];
+  nan = red_n[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) { m = fmax(m, red_s[w]); nan |= red_n[w]; }
+  const double tm = (nan || nrec <= 0) ? NAN : m;
+  if (tid == 0) A.tab_max[sh] = tm;
+  const double wthr = tm - A.tab_tie * fmax(1.0, fabs(tm));
+  int base = 0;  // list entries so far (block-uniform)
+  for (int i0 = 0; i0 < ntw; i0 += kGatherThreads) {
+    const int i = i0 + tid;
+    const bool hot = i < ntw && !(wm[i] < wthr);
+    const uint64_t bal = __ballot(hot);
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const int c = wsum[w];
+      before += w < wave ? c : 0;
+      total += c;
+    }
+    if (hot) list[base + before + __popcll(bal & (((uint64_t)1 << lane) - 1))] = i;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    A.tie_cnt[sh] = base;
+    // (never: the wave holding tab_max is hot.  Were the list empty no block
+    // of the direct pass would run, so the record is left here)
+    if (base == 0 && !A.accumulate) A.results[sh] = Partial{NAN, NAN, -1, 1, 0};
+  }
 }
 // the one-row wave tiles (KIND_LSE_GW1 / LW1) in a kernel of their own: the
 // two-row kernel's register allocation is left as it is
@@ -2969,6 +3068,19 @@ static ScoreArgs select_groups(const ScoreArgs &a, int cls) {
   return b;
 }
 
+// k_score_wave_tie's persistent blocks per CU (TPE_TIE_BLOCKS: A/B; read once).
+// Config 4, ms per step at 4 / 6 / 8 / 12 / 16 / 32: 26.86 / 26.52 / 26.44 /
+// 26.33 / 26.29 / 26.29, two rounds within 0.07 ms of each other
+// (profiles/tiegather_blocks_sweep.txt)
+static int tie_blocks_per_cu() {
+  static const int v = [] {
+    const char *e = std::getenv("TPE_TIE_BLOCKS");
+    const int n = e ? std::atoi(e) : 0;
+    return n >= 1 && n <= 64 ? n : 16;
+  }();
+  return v;
+}
+
 // one launch of a single class's groups
 static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStream_t st) {
   if (a.n_groups <= 0) return hipSuccess;
@@ -2988,13 +3100,34 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
       else k_score_wave1<false, 16><<<g, kWaves * 64, 0, st>>>(a);
     }
   } else if (cls == 0) {
-    if (a.tab_on) {  // the table pass of the certified slots, then the direct pass
+    if (a.tab_on == 2) {  // the operator form: the tables alone
       if (a.census) k_score_table<true><<<g, kWaves * 64, 0, st>>>(a);
       else k_score_table<false><<<g, kWaves * 64, 0, st>>>(a);
-      if (a.tab_on == 2) return hipGetLastError();
-      // (gated on the 16-wide class: the direct pass that follows the tables)
-      if (a.census) k_score_wave_tie<true><<<g, kWaves * 64, 0, st>>>(a);
-      else k_score_wave_tie<false><<<g, kWaves * 64, 0, st>>>(a);
+      return hipGetLastError();
+    }
+    if (a.tab_on) {
+      // the table pass of the certified slots (every wave's best table
+      // score), the gather of each slot's hot wave tiles into dense blocks,
+      // then the direct pass over those (gated on the 16-wide class)
+      if (!a.tie_list || !a.tie_cnt) return hipErrorInvalidValue;
+      if (a.census) k_score_table<true, true><<<g, kWaves * 64, 0, st>>>(a);
+      else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
+      int32_t rows = 0, ntmax = 1;
+      for (int i = 0; i < a.n_groups; ++i) {
+        rows += (a.grp_block0[i + 1] - a.grp_block0[i]) / a.grp_tiles[i];
+        ntmax = std::max(ntmax, a.grp_tiles[i]);
+      }
+      if (rows <= 0 || rows > 65535 || a.n_suggest > 65535) return hipErrorInvalidValue;
+      k_tie_gather<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
+      // persistent blocks per slot: ~tie_blocks_per_cu() blocks per CU over
+      // the launch's (row, suggestion) pairs, so that a single all-hot slot
+      // still fills the chip; never more than the slot has tiles
+      const int64_t per = ((int64_t)tie_blocks_per_cu() * kNumCUs + (int64_t)rows * a.n_suggest - 1) /
+                          ((int64_t)rows * a.n_suggest);
+      const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntmax, per));
+      const dim3 gt(G, (unsigned)rows, a.n_suggest);
+      if (a.census) k_score_wave_tie<true><<<gt, kWaves * 64, 0, st>>>(a);
+      else k_score_wave_tie<false><<<gt, kWaves * 64, 0, st>>>(a);
       return hipGetLastError();
     }
     if (m8) {

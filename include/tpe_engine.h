@@ -319,6 +319,14 @@ int tpe_plan_census(tpe_plan_t p, int32_t enable, int64_t *counts);
  * [11] of [9] the 16-component chunks read at degree 15 (table 4).         */
 int tpe_plan_census_n(tpe_plan_t p, int32_t enable, int64_t *counts, int32_t n_counts);
 
+/* Debug: counts[s * n_hp + hp], s < n_suggest (at most the last call's), the
+ * wave tiles (128 candidates each) the direct pass behind the Chebyshev
+ * tables scored for hp in the plan's last scoring launch that took them: the
+ * tiles within the tie window of a slot whose two tables are certified, every
+ * tile of any other slot, 0 for an inactive hp, -1 for an hp no such launch
+ * has scored.  Synchronizes the device.                                     */
+int tpe_plan_tie_counts(tpe_plan_t p, int32_t n_suggest, int32_t *counts);
+
 /* Prior draws of n_suggest whole suggestions (rand.suggest, the TPE startup
  * phase: hyperopt/rand.py:14-33, pyll/stochastic.py:30-142): every active hp
  * drawn from its prior, conditional hps routed by their parents' draws;
