@@ -42,7 +42,7 @@ EXPORTS = (
     'tpe_plan_results_device', 'tpe_plan_census', 'tpe_plan_fit_suggest',
     'tpe_plan_set_lattice', 'tpe_plan_update_history', 'tpe_plan_set_prune',
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
-    'tpe_plan_tie_counts',
+    'tpe_plan_tie_counts', 'tpe_plan_tab_wmax',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -158,6 +158,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_census': (C.c_int, [vp, i32, C.POINTER(i64)]),
             'tpe_plan_census_n': (C.c_int, [vp, i32, C.POINTER(i64), i32]),
             'tpe_plan_tie_counts': (C.c_int, [vp, i32, vp]),
+            'tpe_plan_tab_wmax': (C.c_int, [vp, i32, vp]),
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
             'tpe_plan_set_prune': (C.c_int, [vp, i32]),
             'tpe_plan_sample_prior': (C.c_int, [vp, C.POINTER(u64), i64, vp, i32, vp]),
@@ -600,6 +601,20 @@ class Plan(object):
         out = np.empty((int(n_suggest), self.n_hp), dtype=np.int32)
         with e.lock:
             e.check(e.lib.tpe_plan_tie_counts(self.p, int(n_suggest), out.ctypes.data))
+        return out
+
+    def tab_wmax(self, n_suggest):
+        """Debug (tpe_plan_tab_wmax): float64 [n_suggest][n_hp][8 * tiles per
+        slot], every 128-candidate wave tile's best table score as the table
+        pass of the last scoring launch that took the Chebyshev tables left
+        it; entries of hps without two certified tables, of inactive hps and
+        of wave tiles never written are unspecified."""
+        e = self.engine
+        with e.lock:
+            w = e.lib.tpe_plan_tab_wmax(self.p, int(n_suggest), None)
+            e.check(min(w, 0))
+            out = np.empty((int(n_suggest), self.n_hp, w), dtype=np.float64)
+            e.check(e.lib.tpe_plan_tab_wmax(self.p, int(n_suggest), out.ctypes.data))
         return out
 
     def last_stats(self):

@@ -163,6 +163,7 @@ struct tpe_plan {
   double *d_tab_wmax = nullptr; // [partial_cap][8] ... per wave tile
   int32_t *d_tie_list = nullptr; // [partial_cap][8] the direct pass's wave tiles (ScoreArgs::tie_list)
   int32_t *d_tie_cnt = nullptr;  // [s_cap][P] ... and their number per slot (-1: never gathered)
+  int32_t tab_pstride = 0;       // pstride of the last launch that took the tables (tab_on 1)
   bool tab_built = false;
   bool graph_tab = false;       // the captured graph holds the build
   std::vector<double> act_frac;  // per hp: expected share of the trials it is active in
@@ -839,6 +840,7 @@ int score_launch(tpe_engine *h, tpe_plan *p, ScoreArgs a, bool has_erf, int64_t 
   if (a.tab_on == 1 && (classes & 1)) {
     const int rc = table_build(h, p, sg);
     if (rc) return rc;
+    p->tab_pstride = a.pstride;  // (tpe_plan_tab_wmax's row length)
   }
   // (a level mixing wave-tile log-sum-exp slots with other kinds: those run
   // beside it on an auxiliary stream; the events are free at scoring time)
@@ -2220,6 +2222,21 @@ int tpe_plan_tie_counts(tpe_plan_t p, int32_t n_suggest, int32_t *counts) {
   CKH(hipDeviceSynchronize());
   if (n_suggest > 0)
     CKH(hipMemcpy(counts, p->d_tie_cnt, (size_t)n_suggest * p->P * sizeof(int32_t),
+                  hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out) {
+  if (!p || n_suggest < 0) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  const size_t row = (size_t)p->tab_pstride * 8;
+  if (!out) return (int)row;
+  if (n_suggest > p->s_cap || (size_t)n_suggest * p->P * p->tab_pstride > p->partial_cap)
+    return fail(h, TPE_E_INVALID, "more suggestions than the last call's");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  if (n_suggest > 0 && row > 0)
+    CKH(hipMemcpy(out, p->d_tab_wmax, (size_t)n_suggest * p->P * row * sizeof(double),
                   hipMemcpyDeviceToHost));
   return TPE_OK;
 }

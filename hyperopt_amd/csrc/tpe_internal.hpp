@@ -371,7 +371,8 @@ struct ScoreArgs {
   const LatInfo *lat_info;   // [P] value lattices (KIND_LAT slots)
   const double2 *lat;        // lattice (lpdf below, lpdf above) pairs
   // Chebyshev tables (k_table_build): tab_on 1 -- a two-row wave-tile slot
-  // whose two tables are certified is scored by k_score_table, and
+  // whose two tables are certified is scored by k_table_map (per-lane
+  // coefficient loads, TPE_TABLE_SCALAR=0: k_score_table<., true>), and
   // k_score_wave_tie scores again only the wave tiles within the sums' own
   // error of the slot's best table score (gathered into dense blocks by
   // k_tie_gather), so the winner is the one its sums alone give; 2 -- the

@@ -1598,41 +1598,101 @@ __device__ __forceinline__ void publish_arrive(const ScoreArgs &A) {
 // Both mixtures of the lane's candidates from the slots' Chebyshev tables
 // (TabHdr, k_table_build): panel p = floor((y' - y_lo) / width) clamped to
 // the table, local coordinate t in [-1, 1], a 16-term fp64 Clenshaw sum of the
-// panel's coefficients (per-lane vector loads: a wave's bucketed candidates
-// share one or two panels).  The result is the LseAcc{M_p, s} the component
-// loops would leave; a NaN candidate gives NaN.
+// panel's coefficients (a wave's bucketed candidates share one or two panels:
+// read through scalar loads panel by panel, SCALAR below, or by per-lane
+// vector loads).  The result is the LseAcc{M_p, s} the component loops would
+// leave; a NaN candidate gives NaN.
 __device__ __forceinline__ bool tab_valid(const TabHdr &h) {
   return h.P > 0 && h.ncert == (uint32_t)h.P;
 }
-template <int KR>
+// the panel's Clenshaw sum at t: the one recurrence of both forms of tab_eval
+// (the same expression on per-lane or on scalar coefficients: the same bits)
+__device__ __forceinline__ double tab_clenshaw(const double (&c)[kTabNodes], double t) {
+  const double t2 = t + t;
+  double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+  for (int k = kTabNodes - 1; k > 0; --k) {
+    const double b0 = fma(t2, b1, c[k] - b2);
+    b2 = b1;
+    b1 = b0;
+  }
+  return fma(t, b1, c[0] - b2);
+}
+// SCALAR: the coefficients through scalar loads, one panel at a time.  The
+// rows' lanes still to do (`valid` ones: a lane without a candidate gets no
+// sum) are retired panel by panel: the first pending lane's panel as a scalar
+// (ballot, readlane), its 16 coefficients and M read through that wave-uniform
+// address into SGPRs, then the recurrence for each row with a lane on it.
+// Every round retires its leader, so there are as many rounds as the wave has
+// distinct panels -- one or two for bucketed candidates -- against one 16-B
+// vector load per lane, row and coefficient pair of the per-lane form.
+template <int KR, bool SCALAR = false>
 __device__ __forceinline__ void tab_eval(const TabHdr *__restrict__ hdr,
                                          const TabPanel *__restrict__ tab, int64_t slot,
-                                         const double (&y)[KR], LseAcc (&out)[KR]) {
+                                         const double (&y)[KR], const bool (&valid)[KR],
+                                         LseAcc (&out)[KR]) {
   const TabHdr h = hdr[slot];
   const TabPanel *__restrict__ base = tab + slot * kTabMaxPanels;
+  if constexpr (SCALAR) {
+    const uint64_t ub = (uint64_t)base;
+    const uint64_t sbase =
+        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);
+    int p[KR];
+    double t[KR];
+    bool todo[KR];
 #pragma unroll
-  for (int r = 0; r < KR; ++r) {
-    const double u = (y[r] - h.y_lo) * h.inv_w;
-    const double pf = fmin(fmax(floor(u), 0.0), (double)(h.P - 1));
-    const double t = fmin(fmax(2.0 * (u - pf) - 1.0, -1.0), 1.0), t2 = t + t;
-    const double2 *__restrict__ cp = reinterpret_cast<const double2 *>(base + (int)pf);
-    double c[kTabNodes];
-#pragma unroll
-    for (int k = 0; k < kTabNodes / 2; ++k) {
-      const double2 v = cp[k];
-      c[2 * k] = v.x;
-      c[2 * k + 1] = v.y;
+    for (int r = 0; r < KR; ++r) {
+      const double u = (y[r] - h.y_lo) * h.inv_w;
+      const double pf = fmin(fmax(floor(u), 0.0), (double)(h.P - 1));
+      t[r] = fmin(fmax(2.0 * (u - pf) - 1.0, -1.0), 1.0);
+      p[r] = (int)pf;  // (a NaN candidate: panel 0)
+      todo[r] = valid[r];
+      out[r] = LseAcc{NAN, NAN};
     }
-    const double M = cp[kTabNodes / 2].x;
-    double b1 = 0.0, b2 = 0.0;
+    for (;;) {
+      int pp = -1;  // the lane's first pending panel
 #pragma unroll
-    for (int k = kTabNodes - 1; k > 0; --k) {
-      const double b0 = fma(t2, b1, c[k] - b2);
-      b2 = b1;
-      b1 = b0;
+      for (int r = KR - 1; r >= 0; --r) pp = todo[r] ? p[r] : pp;
+      const uint64_t pend = __ballot(pp >= 0);
+      if (!pend) break;
+      const int ps = __builtin_amdgcn_readlane(pp, (int)__builtin_ctzll(pend));
+      KDbl *__restrict__ cp = (KDbl *)(sbase + (uint64_t)(uint32_t)ps * sizeof(TabPanel));
+      double c[kTabNodes];
+#pragma unroll
+      for (int k = 0; k < kTabNodes; ++k) c[k] = cp[k];
+      const double M = cp[kTabNodes];
+#pragma unroll
+      for (int r = 0; r < KR; ++r) {
+        const bool mine = todo[r] && p[r] == ps;
+        if (__ballot(mine)) {  // (wave-uniform)
+          const double sv = tab_clenshaw(c, t[r]);
+          out[r] = mine ? LseAcc{M, sv} : out[r];
+          todo[r] = todo[r] && !mine;
+        }
+      }
     }
-    const double sv = fma(t, b1, c[0] - b2);
-    out[r] = (y[r] != y[r]) ? LseAcc{NAN, NAN} : LseAcc{M, sv};
+#pragma unroll
+    for (int r = 0; r < KR; ++r)
+      if (y[r] != y[r]) out[r] = LseAcc{NAN, NAN};
+  } else {
+#pragma unroll
+    for (int r = 0; r < KR; ++r) {
+      const double u = (y[r] - h.y_lo) * h.inv_w;
+      const double pf = fmin(fmax(floor(u), 0.0), (double)(h.P - 1));
+      const double t = fmin(fmax(2.0 * (u - pf) - 1.0, -1.0), 1.0);
+      const double2 *__restrict__ cp = reinterpret_cast<const double2 *>(base + (int)pf);
+      double c[kTabNodes];
+#pragma unroll
+      for (int k = 0; k < kTabNodes / 2; ++k) {
+        const double2 v = cp[k];
+        c[2 * k] = v.x;
+        c[2 * k + 1] = v.y;
+      }
+      const double M = cp[kTabNodes / 2].x;
+      const double sv = tab_clenshaw(c, t);
+      out[r] = (y[r] != y[r]) ? LseAcc{NAN, NAN} : LseAcc{M, sv};
+    }
   }
 }
 
@@ -1645,11 +1705,12 @@ __device__ __forceinline__ void tab_eval(const TabHdr *__restrict__ hdr,
 // suggest decides nothing -- every wave leaves its best table score in
 // tab_wmax (by wave-tile number) and is done: no positions, no block merge,
 // no tile record, no ticket.
+// TSCL (with TAB): the table sums by the scalar-panel form of tab_eval.
 // TIEK (k_score_wave_tie): block `tile` of the slot's `ntiles` gathered blocks
 // (k_tie_gather): wave w scores the wave tile of list entry 8 tile + w, a
 // wave past the list's end none.  Grid (., row, suggestion).
 template <int KIND, bool CENSUS, typename SM, bool LDRAW = false, bool TDRAW = false, int MW = 16,
-          bool TAB = false, bool TIEK = false, bool TMAP = false>
+          bool TAB = false, bool TIEK = false, bool TMAP = false, bool TSCL = false>
 __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot, int tile,
                                            int ntiles, bool known_active) {
   constexpr bool STAGE = std::is_same<SM, ScoreSmem1>::value;
@@ -1891,7 +1952,7 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
 #pragma unroll
     for (int mix = 0; mix < 2; ++mix) {
       LseAcc acc[KR];
-      tab_eval<KR>(A.tab_hdr, A.tab, mix ? sa : sb, y, acc);
+      tab_eval<KR, TSCL>(A.tab_hdr, A.tab, mix ? sa : sb, y, valid, acc);
 #pragma unroll
       for (int r = 0; r < KR; ++r) sm.wpart[mix][wave][r][lane] = make_double2(acc[r].m, acc[r].s);
     }
@@ -2542,7 +2603,7 @@ __device__ __forceinline__ void mark_inactive(const ScoreArgs &A, int s, int s0,
 // large draws whose every slot is one: a kernel with only their register
 // allocation -- the combined one keeps the most any kind needs).
 enum { kSetNoErf = 0, kSetAll = 1, kSetWave = 2, kSetWave1 = 3, kSetLookup = 4, kSetTiny = 5,
-       kSetTable = 6, kSetTableMap = 7 };
+       kSetTable = 6, kSetTableMap = 7, kSetTableScalar = 8 };
 
 template <int SET, bool CENSUS, typename SM, int MW = 16>
 __device__ __forceinline__ void score_block(const ScoreArgs &A, SM &sm) {
@@ -2578,6 +2639,14 @@ __device__ __forceinline__ void score_block(const ScoreArgs &A, SM &sm) {
     if (A.grp_kind[g] == KIND_LSE_LW)
       score_tile<KIND_LSE_LW, CENSUS, SM, false, false, 16, true>(A, sm, slot, tile, nt, known);
     else score_tile<KIND_LSE_GW, CENSUS, SM, false, false, 16, true>(A, sm, slot, tile, nt, known);
+    return;
+  } else if constexpr (SET == kSetTableScalar) {
+    if (A.grp_kind[g] == KIND_LSE_LW)
+      score_tile<KIND_LSE_LW, CENSUS, SM, false, false, 16, true, false, false, true>(A, sm, slot,
+                                                                                      tile, nt, known);
+    else
+      score_tile<KIND_LSE_GW, CENSUS, SM, false, false, 16, true, false, false, true>(A, sm, slot,
+                                                                                      tile, nt, known);
     return;
   } else if constexpr (SET == kSetLookup) {
     if (A.grp_kind[g] == KIND_LAT) score_tile<KIND_LAT, CENSUS, SM, true>(A, sm, slot, tile, nt, known);
@@ -2690,10 +2759,96 @@ void k_score_wave_tie(ScoreArgs A) {
 }
 // the same tiles of the slots scored from their Chebyshev tables (tab_on 2:
 // the operator form; MAP, tab_on 1: a suggest's per-wave map, score_tile TMAP)
-template <bool CENSUS, bool MAP = false>
+// (SCL: the operator form on the scalar-panel tab_eval, the default; the
+// per-lane forms stay for TPE_TABLE_SCALAR=0)
+template <bool CENSUS, bool MAP = false, bool SCL = false>
 __global__ __launch_bounds__(kWaves * 64) void k_score_table(ScoreArgs A) {
+  static_assert(!(MAP && SCL), "the scalar-panel map is k_table_map");
   __shared__ ScoreSmem sm;
-  score_block<MAP ? kSetTableMap : kSetTable, CENSUS, ScoreSmem, 16>(A, sm);
+  score_block<MAP ? kSetTableMap : SCL ? kSetTableScalar : kSetTable, CENSUS, ScoreSmem, 16>(A, sm);
+}
+
+// The table pass of a suggest (tab_on 1) as a map of its own: a wave takes
+// one wave tile, evaluates both tables by the scalar-panel tab_eval and
+// leaves the tile's best EI score in tab_wmax -- what k_score_table<., true>
+// leaves, bit for bit (the same transform, sums, score expression and order:
+// a NaN first, otherwise the maximum), without that kernel's LDS round trips,
+// block state and index-carrying argmax.  Grid and block -> (group, slot,
+// tile) mapping of score_block; wave w of block tile `tile` takes wave tile 8
+// tile + w (the block reads 8 KB of candidates in one piece).  Blocks of
+// slots without two certified tables and of inactive hps return at entry
+// (k_tie_gather handles both).  No LDS, no barrier, nothing waits.
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) void k_table_map(ScoreArgs A) {
+  constexpr int KR = tile_rows(KIND_LSE_GW);
+  static_assert(KR == 2 && tile_rows(KIND_LSE_LW) == 2, "two-row wave tiles");
+  const int b = blockIdx.x;
+  int g = 0;
+  while (g + 1 < A.n_groups && b >= A.grp_block0[g + 1]) ++g;
+  const int nt = A.grp_tiles[g];
+  const int local = xcd_local(b - A.grp_block0[g], A.grp_block0[g + 1] - A.grp_block0[g],
+                              (int)(((int64_t)blockIdx.y * gridDim.x + A.grp_block0[g]) & 7));
+  int slot = A.grp_slot0[g] + local / nt;
+  const int tile = local % nt;
+  const int s = blockIdx.y;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], local / nt);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
+  if (!(tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sa]))) return;
+  if (!(A.force_active || A.compact ||
+        hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch)))
+    return;
+  const bool logn = A.grp_kind[g] == KIND_LSE_LW;
+  const int lane = threadIdx.x & 63;
+  const int wt = tile * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const double *__restrict__ cand =
+      A.cand + (int64_t)s * A.cand_sstride + (int64_t)(A.cand_slot0 + slot) * A.n_cand;
+  const double mu = A.hps[hp].prior_mu;
+  bool valid[KR];
+  double y[KR];
+#pragma unroll
+  for (int r = 0; r < KR; ++r) {
+    const int64_t li = (int64_t)wt * (64 * KR) + r * 64 + lane;
+    valid[r] = li < A.n_cand;
+    const double x = valid[r] ? cand[li] : (logn ? 1.0 : 0.0);
+    y[r] = (logn ? fast_log(x) : x) - mu;
+  }
+  LseAcc lb[KR], la[KR];
+  tab_eval<KR, true>(A.tab_hdr, A.tab, sb, y, valid, lb);
+  tab_eval<KR, true>(A.tab_hdr, A.tab, sa, y, valid, la);
+  // the finalize's EI-only score; the lanes' maximum, or the first NaN in
+  // candidate order (its own bits), or NaN for a wave tile past n_cand
+  const double LN2 = 0.6931471805599453;
+  double sc[KR], m = -INFINITY;
+  uint64_t nanm[KR];
+#pragma unroll
+  for (int r = 0; r < KR; ++r) {
+    sc[r] = (lb[r].m == -INFINITY || la[r].m == -INFINITY)
+                ? NAN
+                : ((lb[r].m - la[r].m) + fast_log2(lb[r].s / la[r].s)) * LN2;
+    nanm[r] = __ballot(valid[r] && sc[r] != sc[r]);
+    m = fmax(m, valid[r] ? sc[r] : -INFINITY);
+  }
+  m = row16_max(m);
+  double best = fmax(fmax(bitsd(lane_value64(dbits(m), 0)), bitsd(lane_value64(dbits(m), 16))),
+                     fmax(bitsd(lane_value64(dbits(m), 32)), bitsd(lane_value64(dbits(m), 48))));
+  if (!__ballot(valid[0])) best = NAN;  // (row 1 holds candidates only behind a full row 0)
+#pragma unroll
+  for (int r = KR - 1; r >= 0; --r)
+    if (nanm[r]) best = bitsd(lane_value64(dbits(sc[r]), (int)__builtin_ctzll(nanm[r])));
+  if constexpr (CENSUS) {
+    if (lane == 0) {
+      const unsigned long long nv =
+          (unsigned long long)min<int64_t>(64 * KR, max<int64_t>(0, A.n_cand - (int64_t)wt * (64 * KR)));
+      const unsigned long long c = nv * (unsigned long long)(A.info[sb].K + A.info[sa].K);
+      atomicAdd(A.census + 3, c);
+      atomicAdd(A.census + 12, c);
+    }
+  }
+  if (lane == 0) A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * kWaves + wt] = best;
 }
 
 // Between the two passes of a tab_on 1 launch: one block per (row,
@@ -3081,6 +3236,17 @@ static int tie_blocks_per_cu() {
   return v;
 }
 
+// The table kernels' form (TPE_TABLE_SCALAR: A/B; read once): the scalar-panel
+// tab_eval -- k_table_map and k_score_table<., false, true> -- unless 0, which
+// takes the per-lane kernels k_score_table<., true> and k_score_table<.>.
+static bool table_scalar_on() {
+  static const bool v = [] {
+    const char *e = std::getenv("TPE_TABLE_SCALAR");
+    return !(e && *e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+
 // one launch of a single class's groups
 static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStream_t st) {
   if (a.n_groups <= 0) return hipSuccess;
@@ -3101,8 +3267,13 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
     }
   } else if (cls == 0) {
     if (a.tab_on == 2) {  // the operator form: the tables alone
-      if (a.census) k_score_table<true><<<g, kWaves * 64, 0, st>>>(a);
-      else k_score_table<false><<<g, kWaves * 64, 0, st>>>(a);
+      if (table_scalar_on()) {
+        if (a.census) k_score_table<true, false, true><<<g, kWaves * 64, 0, st>>>(a);
+        else k_score_table<false, false, true><<<g, kWaves * 64, 0, st>>>(a);
+      } else {
+        if (a.census) k_score_table<true><<<g, kWaves * 64, 0, st>>>(a);
+        else k_score_table<false><<<g, kWaves * 64, 0, st>>>(a);
+      }
       return hipGetLastError();
     }
     if (a.tab_on) {
@@ -3110,8 +3281,13 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
       // score), the gather of each slot's hot wave tiles into dense blocks,
       // then the direct pass over those (gated on the 16-wide class)
       if (!a.tie_list || !a.tie_cnt) return hipErrorInvalidValue;
-      if (a.census) k_score_table<true, true><<<g, kWaves * 64, 0, st>>>(a);
-      else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
+      if (table_scalar_on()) {
+        if (a.census) k_table_map<true><<<g, kWaves * 64, 0, st>>>(a);
+        else k_table_map<false><<<g, kWaves * 64, 0, st>>>(a);
+      } else {
+        if (a.census) k_score_table<true, true><<<g, kWaves * 64, 0, st>>>(a);
+        else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
+      }
       int32_t rows = 0, ntmax = 1;
       for (int i = 0; i < a.n_groups; ++i) {
         rows += (a.grp_block0[i + 1] - a.grp_block0[i]) / a.grp_tiles[i];

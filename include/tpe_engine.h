@@ -326,6 +326,15 @@ int tpe_plan_census_n(tpe_plan_t p, int32_t enable, int64_t *counts, int32_t n_c
  * tile of any other slot, 0 for an inactive hp, -1 for an hp no such launch
  * has scored.  Synchronizes the device.                                     */
 int tpe_plan_tie_counts(tpe_plan_t p, int32_t n_suggest, int32_t *counts);
+/* Debug: out[(s * n_hp + hp) * W + t], s < n_suggest (at most the last
+ * call's), the best table score of wave tile t (candidates 128 t .. 128 t +
+ * 127 of the sorted draw) of hp as the table pass of the plan's last scoring
+ * launch that took the tables left it; W = 8 * the launch's tiles per slot
+ * holds every wave tile of its candidate count.  Entries of hps without two
+ * certified tables, of inactive hps and of wave tiles no such launch has
+ * written are unspecified.  out == NULL: returns W (0: no such launch yet)
+ * and copies nothing.  Synchronizes the device.                              */
+int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out);
 
 /* Prior draws of n_suggest whole suggestions (rand.suggest, the TPE startup
  * phase: hyperopt/rand.py:14-33, pyll/stochastic.py:30-142): every active hp
