@@ -13,6 +13,6 @@ from .base import (STATUS_STRINGS, STATUS_NEW, STATUS_RUNNING, STATUS_SUSPENDED,
 from .fmin import fmin, fmin_pass_expr_memo_ctrl, FMinIter, partial, space_eval  # noqa: F401
 from .workers import ThreadTrials  # noqa: F401
 from .expr import scope  # noqa: F401
-from . import hp, rand, tpe  # noqa: F401
+from . import hp, rand, tpe, anneal, mix  # noqa: F401
 
 __version__ = '0.1.0'

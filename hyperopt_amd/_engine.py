@@ -42,7 +42,8 @@ EXPORTS = (
     'tpe_plan_results_device', 'tpe_plan_census', 'tpe_plan_fit_suggest',
     'tpe_plan_set_lattice', 'tpe_plan_update_history', 'tpe_plan_set_prune',
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
-    'tpe_plan_tie_counts', 'tpe_plan_tab_wmax',
+    'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
+    'tpe_plan_set_anneal_order',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -74,6 +75,8 @@ class TpeSpace(C.Structure):
 
 RESULT_DTYPE = np.dtype([('score', '<f8'), ('value', '<f8'), ('index', '<i8'),
                          ('active', '<i4'), ('pad', '<i4')])
+# tpe_anneal_trace
+ANNEAL_TRACE_DTYPE = np.dtype([('row', '<i4'), ('rank', '<i4'), ('u', '<f8', (4,))])
 
 _D = C.POINTER(C.c_double)
 _lib = None
@@ -162,6 +165,9 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
             'tpe_plan_set_prune': (C.c_int, [vp, i32]),
             'tpe_plan_sample_prior': (C.c_int, [vp, C.POINTER(u64), i64, vp, i32, vp]),
+            'tpe_plan_anneal': (C.c_int, [vp, dbl, dbl, C.POINTER(u64), i64, vp, i32, vp]),
+            'tpe_plan_anneal_trace': (C.c_int, [vp, i32, vp]),
+            'tpe_plan_set_anneal_order': (C.c_int, [vp, C.POINTER(i32), i32]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -349,6 +355,7 @@ class Plan(object):
             engine.check(lib.tpe_plan_create(engine.h, C.byref(sp), int(max_trials), C.byref(p)))
         self.p = p
         self.max_trials = int(max_trials)
+        self.anneal_order = None
         nl = C.c_int32(0)
         lib.tpe_plan_num_levels(p, C.byref(nl))
         self.n_levels = nl.value
@@ -490,6 +497,40 @@ class Plan(object):
                                                 seeds.size, res.ctypes.data, 0, stream))
         self._last_nsug = seeds.size
         return res
+
+    def set_anneal_order(self, hp_order):
+        """The order in which an anneal call walks the hps (hp indices of
+        CompiledSpace.draw_order; tpe_plan_set_anneal_order), once per plan."""
+        e = self.engine
+        order = np.ascontiguousarray(hp_order, dtype=np.int32)
+        with e.lock:
+            e.check(e.lib.tpe_plan_set_anneal_order(
+                self.p, order.ctypes.data_as(C.POINTER(C.c_int32)), order.size))
+        self.anneal_order = order
+
+    def anneal(self, seeds, avg_best_idx=2.0, shrink_coef=0.1, stream=None):
+        """Annealing suggestions of len(seeds) independent annealers on the
+        plan's history (tpe_plan_anneal): [S, n_hp] RESULT_DTYPE -- value,
+        index = the anchor row, score = its loss (0, 0 for a prior draw)."""
+        e = self.engine
+        seeds = _seeds(seeds)
+        res = np.empty((seeds.size, self.n_hp), dtype=RESULT_DTYPE)
+        with e.lock:
+            e.check(e.lib.tpe_plan_anneal(self.p, float(avg_best_idx), float(shrink_coef),
+                                          seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          seeds.size, res.ctypes.data, 0, stream))
+        self._last_nsug = seeds.size
+        return res
+
+    def anneal_trace(self, n_suggest):
+        """Debug (tpe_plan_anneal_trace): [n_suggest, n_hp] ANNEAL_TRACE_DTYPE
+        of the last anneal call -- anchor row, clipped rank of a fresh anchor,
+        the uniforms each hp consumed."""
+        e = self.engine
+        out = np.empty((int(n_suggest), self.n_hp), dtype=ANNEAL_TRACE_DTYPE)
+        with e.lock:
+            e.check(e.lib.tpe_plan_anneal_trace(self.p, int(n_suggest), out.ctypes.data))
+        return out
 
     def results(self):
         e = self.engine

@@ -14,9 +14,11 @@
 #include <string>
 #include <vector>
 
+#include "tpe_anneal.hpp"
 #include "tpe_internal.hpp"
 
 using namespace tpe;
+static_assert(sizeof(AnnealTrace) == sizeof(tpe_anneal_trace), "layout");
 
 static int lse_shift_min();
 static bool small_sort_on();
@@ -244,6 +246,15 @@ struct tpe_plan {
   int32_t graph_mom_w = 0; // ... the captured graph's fit (launch_step restores it)
   HistPatch pend{};        // a small history update not yet on the device: the next
   bool has_pend = false;   // fit writes it (k_fit's patch), anything else flushes it
+  // annealing (tpe_plan_anneal): allocated by its first call
+  uint64_t *d_an_keys = nullptr;    // [2][ncap] sort keys (ping-pong)
+  int32_t *d_an_idx = nullptr;      // [2][ncap] rows; [0]: the loss order
+  int32_t *d_an_T = nullptr;        // [P] rows in which each hp is active
+  int32_t *d_an_hporder = nullptr;  // [P] hps in the host's evaluation order
+  AnnealTrace *d_an_trace = nullptr;  // [an_cap][P]
+  int64_t an_cap = 0, an_nsug = 0;
+  bool an_ready = false;   // keys / idx / T allocated
+  bool an_order = false;   // d_an_hporder holds the host's order (tpe_plan_set_anneal_order)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -295,7 +306,8 @@ hipStream_t pick_stream(tpe_engine *h, void *s) {
 }
 
 void plan_free_buffers(tpe_plan *p) {
-  void *bufs[] = {p->d_hps, p->d_cp, p->d_cb, p->d_level_hps, p->d_all_hps, p->d_pprior,
+  void *bufs[] = {p->d_an_keys, p->d_an_idx, p->d_an_T, p->d_an_hporder, p->d_an_trace,
+                  p->d_hps, p->d_cp, p->d_cb, p->d_level_hps, p->d_all_hps, p->d_pprior,
                   p->d_level_off,
                   p->d_losses, p->d_vals, p->d_active, p->d_below, p->d_mw, p->d_mmu,
                   p->d_msig, p->d_scratch, p->d_info, p->d_coef, p->d_results, p->d_seeds,
@@ -2271,6 +2283,130 @@ int tpe_plan_sample_prior(tpe_plan_t p, const uint64_t *seeds, int64_t n_sug, tp
     return TPE_OK;
   }
   return copy_results(h, p, n_sug, out, out_on_device, st);
+}
+
+// ---------------------------------------------------------------- annealing
+// The order in which a suggestion walks the hps is the host's: the reference
+// interpreter's node-evaluation order (hyperopt/algobase.py:64-132 on the
+// vectorized graph; space.CompiledSpace.draw_order, pinned by
+// tests/golden/anneal.npz), compiled into the plan as an int array.
+int tpe_plan_set_anneal_order(tpe_plan_t p, const int32_t *hp_order, int32_t n_hp) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!hp_order || n_hp != p->P) return fail(h, TPE_E_INVALID, "anneal order: one entry per hp");
+  std::vector<int32_t> pos(p->P, -1);
+  for (int k = 0; k < n_hp; ++k) {
+    const int hp = hp_order[k];
+    if (hp < 0 || hp >= p->P || pos[hp] >= 0)
+      return fail(h, TPE_E_INVALID, "anneal order: not a permutation of the hps");
+    pos[hp] = k;
+  }
+  for (int hp = 0; hp < p->P; ++hp) {
+    const tpe_hp &x = p->hps[hp];
+    for (int c = 0; c < x.cond_count; ++c)
+      if (pos[p->cond_parent[x.cond_begin + c]] > pos[hp])
+        return fail(h, TPE_E_INVALID, "anneal order: an hp before the choice that leads to it");
+  }
+  CKH(hipSetDevice(h->device));
+  p->an_order = false;
+  if (!p->d_an_hporder) CKH(dalloc(&p->d_an_hporder, p->P));
+  CKH(hipDeviceSynchronize());  // (no anneal call of any stream still reads the old order)
+  CKH(hipMemcpy(p->d_an_hporder, hp_order, (size_t)n_hp * 4, hipMemcpyHostToDevice));
+  p->an_order = true;
+  return TPE_OK;
+}
+
+// sort scratch, counts and trace of an anneal call: all of it or none (a
+// failed allocation leaves nothing half-built for the next call to launch on)
+static int ensure_anneal_state(tpe_engine *h, tpe_plan *p, int64_t n_sug) {
+  if (!p->an_ready) {
+    auto drop = [p] {
+      dfree(p->d_an_keys); dfree(p->d_an_idx); dfree(p->d_an_T);
+      p->d_an_keys = nullptr; p->d_an_idx = nullptr; p->d_an_T = nullptr;
+    };
+    drop();
+    const hipError_t e1 = dalloc(&p->d_an_keys, 2 * (size_t)p->ncap);
+    const hipError_t e2 = e1 == hipSuccess ? dalloc(&p->d_an_idx, 2 * (size_t)p->ncap) : e1;
+    const hipError_t e3 = e2 == hipSuccess ? dalloc(&p->d_an_T, p->P) : e2;
+    if (e3 != hipSuccess) {
+      drop();
+      return fail(h, TPE_E_NOMEM, std::string("anneal scratch: ") + hipGetErrorString(e3));
+    }
+    p->an_ready = true;
+  }
+  if (n_sug > p->an_cap) {
+    dfree(p->d_an_trace);
+    p->d_an_trace = nullptr;
+    p->an_cap = 0;
+    CKH(dalloc(&p->d_an_trace, (size_t)n_sug * p->P));
+    p->an_cap = n_sug;
+  }
+  return TPE_OK;
+}
+
+int tpe_plan_anneal(tpe_plan_t p, double avg_best_idx, double shrink_coef, const uint64_t *seeds,
+                    int64_t n_sug, tpe_result *out, int32_t out_on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!std::isfinite(avg_best_idx) || !std::isfinite(shrink_coef) || avg_best_idx < 1.0 ||
+      shrink_coef < 0.0)
+    return fail(h, TPE_E_INVALID, "anneal: avg_best_idx >= 1 and shrink_coef >= 0, finite");
+  if (n_sug <= 0 || n_sug > INT32_MAX || !seeds) return fail(h, TPE_E_INVALID, "bad args");
+  if (p->n > INT32_MAX) return fail(h, TPE_E_INVALID, "history too long");
+  if (anneal_wave_lds(p->P) > 64 * 1024) return fail(h, TPE_E_INVALID, "anneal: too many hps");
+  if (!p->an_order) return fail(h, TPE_E_INVALID, "anneal: tpe_plan_set_anneal_order first");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  int rc = ensure_suggest_state(h, p, n_sug, 1);
+  if (rc) return rc;
+  rc = ensure_anneal_state(h, p, n_sug);
+  if (rc) return rc;
+  // the kernels read the history rows: a deferred update goes out first
+  rc = flush_patch(h, p, st);
+  if (rc) return rc;
+  p->h_seeds.assign(seeds, seeds + n_sug);  // (outlives the async copy)
+  CKH(hipMemcpyAsync(p->d_seeds, p->h_seeds.data(), n_sug * 8, hipMemcpyHostToDevice, st));
+  const int32_t n = (int32_t)p->n;
+  CKH(launch_anneal_order(p->d_losses, p->d_active, p->ncap, n, p->P, p->d_an_keys,
+                          p->d_an_keys + p->ncap, p->d_an_idx, p->d_an_idx + p->ncap, p->d_an_T,
+                          st));
+  AnnealArgs a{};
+  a.hps = p->d_hps;
+  a.n_hp = p->P;
+  a.n = n;
+  a.hp_order = p->d_an_hporder;
+  a.cond_parent = p->d_cp;
+  a.cond_branch = p->d_cb;
+  a.pprior = p->d_pprior;
+  a.losses = p->d_losses;
+  a.vals = p->d_vals;
+  a.active = p->d_active;
+  a.ld = p->ncap;
+  a.order = p->d_an_idx;
+  a.T = p->d_an_T;
+  a.p_geo = 1.0 / avg_best_idx;
+  a.log1p_mq = std::log1p(-a.p_geo);
+  a.shrink_coef = shrink_coef;
+  a.seeds = p->d_seeds;
+  a.n_suggest = (int32_t)n_sug;
+  a.results = p->d_results;
+  a.trace = p->d_an_trace;
+  CKH(launch_anneal(a, st));
+  p->last_nsug = n_sug;
+  p->an_nsug = n_sug;
+  return copy_results(h, p, n_sug, out, out_on_device, st);
+}
+
+int tpe_plan_anneal_trace(tpe_plan_t p, int32_t n_suggest, tpe_anneal_trace *out) {
+  if (!p || n_suggest < 0 || !out) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (n_suggest > p->an_nsug) return fail(h, TPE_E_INVALID, "more suggestions than the last call's");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  if (n_suggest > 0 && p->P > 0)
+    CKH(hipMemcpy(out, p->d_an_trace, (size_t)n_suggest * p->P * sizeof(AnnealTrace),
+                  hipMemcpyDeviceToHost));
+  return TPE_OK;
 }
 
 // value-bucketed, pruned log-sum-exp slots on small draws: opt-in

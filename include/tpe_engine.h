@@ -345,6 +345,42 @@ int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out);
 int tpe_plan_sample_prior(tpe_plan_t p, const uint64_t *seeds, int64_t n_suggest,
                           tpe_result *out, int32_t out_on_device, void *stream);
 
+/* Annealing suggestions (anneal.suggest, hyperopt/anneal.py:43-408): each of
+ * n_suggest independent annealers (seeds[s]) walks the hps in hp_order -- set
+ * once per plan with tpe_plan_set_anneal_order: the reference interpreter's
+ * node-evaluation order, a permutation of the hp ids in which every hp comes
+ * after the choices that lead to it (else TPE_E_INVALID; so does
+ * tpe_plan_anneal before an order is set).  An
+ * active hp with T > 0 history rows in which it is active (pending / failed
+ * rows, loss +inf, count) takes an anchor row -- the first row of the
+ * suggestion's anchor list that has the hp active, else a fresh one: rank
+ * r = clip(g - 1, 0, T - 1), g geometric(1 / avg_best_idx), in ascending
+ * (loss, row) order among the hp's rows, appended to the list -- and draws its
+ * value from the prior narrowed around the anchor's value by shrink = 1 /
+ * (1 + T shrink_coef); T = 0 draws from the prior.  results[s][hp] = (score:
+ * the anchor's loss, value, index: the anchor row, active = 1), (0, value, 0,
+ * 1) for a prior draw, (NaN, NaN, -1, 0) inactive.  Counter-based Philox keyed
+ * by seeds[s], stream 2^30 | hp (candidate draws: hp, prior draws: 2^31 | hp),
+ * counter 0, one draw4: u0 the rank draw (consumed only by a fresh anchor), u1
+ * the value draw of bounded and categorical kinds, (u2, u3) the Box-Muller
+ * pair of the normal kinds.  Reads the history (a pending update is flushed
+ * first); stream-ordered; results are kept in the plan.
+ * TPE_E_INVALID: avg_best_idx < 1, shrink_coef < 0, either non-finite,
+ * n_suggest <= 0.                                                          */
+int tpe_plan_set_anneal_order(tpe_plan_t p, const int32_t *hp_order, int32_t n_hp);
+int tpe_plan_anneal(tpe_plan_t p, double avg_best_idx, double shrink_coef,
+                    const uint64_t *seeds, int64_t n_suggest,
+                    tpe_result *out, int32_t out_on_device, void *stream);
+
+/* Debug: out[s * n_hp + hp], s < n_suggest (at most the last tpe_plan_anneal
+ * call's): row -- the anchor row (-1: prior draw or inactive hp); rank -- the
+ * clipped rank r of a fresh anchor (-1: the anchor was reused, or none);
+ * u[0] the rank draw when one was made, then the value draws in the order
+ * above (one for bounded / categorical kinds, two for normal kinds); unused
+ * slots NaN.  Synchronizes the device.                                      */
+typedef struct { int32_t row; int32_t rank; double u[4]; } tpe_anneal_trace;
+int tpe_plan_anneal_trace(tpe_plan_t p, int32_t n_suggest, tpe_anneal_trace *out);
+
 /* Large draws score log-sum-exp candidates on value-bucketed tiles.  mode 1
  * skips the blocks of 8 mixture components whose every term is below
  * 2^-(27 + log2 K) of each candidate's largest one (lpdf moved by <= 2^-26
