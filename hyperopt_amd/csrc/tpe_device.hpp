@@ -442,4 +442,23 @@ __device__ __forceinline__ double fast_log2(double x) {
   return fma(lm, 1.44269504088896340736, (double)e);
 }
 
+// Chebyshev tables (TabHdr): a slot's table is used when every panel is certified
+__device__ __forceinline__ bool tab_valid(const TabHdr &h) {
+  return h.P > 0 && h.ncert == (uint32_t)h.P;
+}
+// the panel's Clenshaw sum at t: the one recurrence of both forms of tab_eval
+// and of the bound lattice (the same expression on per-lane or on scalar
+// coefficients: the same bits)
+__device__ __forceinline__ double tab_clenshaw(const double (&c)[kTabNodes], double t) {
+  const double t2 = t + t;
+  double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+  for (int k = kTabNodes - 1; k > 0; --k) {
+    const double b0 = fma(t2, b1, c[k] - b2);
+    b2 = b1;
+    b1 = b0;
+  }
+  return fma(t, b1, c[0] - b2);
+}
+
 }  // namespace tpe

@@ -108,6 +108,7 @@ static bool side_streams_on() {
 static bool moment_on();
 static bool table_on();
 static double table_tie();
+static bool table_prefilter_on();
 // TPE_MOMENT_H=0: 16-wide plans without the degree-15 chunk table (A/B)
 static bool moment_h_on() {
   static const bool on = [] {
@@ -166,6 +167,8 @@ struct tpe_plan {
   int32_t *d_tie_list = nullptr; // [partial_cap][8] the direct pass's wave tiles (ScoreArgs::tie_list)
   int32_t *d_tie_cnt = nullptr;  // [s_cap][P] ... and their number per slot (-1: never gathered)
   int32_t tab_pstride = 0;       // pstride of the last launch that took the tables (tab_on 1)
+  double *d_tab_bound = nullptr; // [P][kBndCells] bound lattices, built with the tables
+  TabHot *d_tab_hot = nullptr;   // [s_cap][P] hot intervals of a launch (ScoreArgs::tab_hot)
   bool tab_built = false;
   bool graph_tab = false;       // the captured graph holds the build
   std::vector<double> act_frac;  // per hp: expected share of the trials it is active in
@@ -231,10 +234,11 @@ struct tpe_plan {
     int32_t mom_w = 0;   // the moment table the step's fit writes (mom_width grows with
                          // the history: a replay must not keep the captured width)
     bool tab = false;    // the step builds and scores from the Chebyshev tables
+    bool pref = false;   // ... behind the prefilter (k_table_pilot is a node of the step)
     bool operator==(const StepKey &o) const {
       return prior_weight == o.prior_weight && lf == o.lf && n_sug == o.n_sug &&
              n_cand == o.n_cand && stream == o.stream && table == o.table && fuse == o.fuse &&
-             small == o.small && mom_w == o.mom_w && tab == o.tab;
+             small == o.small && mom_w == o.mom_w && tab == o.tab && pref == o.pref;
     }
   };
   StepKey graph_key, pending_key;
@@ -314,7 +318,8 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_partial, p->d_ext, p->d_lb, p->d_la, p->d_cand, p->d_cpos,
                   p->d_ticket, p->d_sortbuf, p->d_census, p->d_lat_info, p->d_lat, p->d_coef32, p->d_coefm,
                   p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
-                  p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt};
+                  p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt, p->d_tab_bound,
+                  p->d_tab_hot};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -501,6 +506,7 @@ int plan_build(tpe_engine *h, const tpe_space *sp, int64_t max_trials, tpe_plan 
   CKH(dalloc(&p->d_tab_hdr, (size_t)slots));
   CKH(hipMemset(p->d_tab_hdr, 0, (size_t)slots * sizeof(TabHdr)));
   CKH(dalloc(&p->d_tab, (size_t)slots * kTabMaxPanels));
+  CKH(dalloc(&p->d_tab_bound, (size_t)p->P * kBndCells));
   // expected activity of every hp (mom_width): an hp conditioned on branch b
   // of a categorical parent is active in ~1 / upper of the parent's trials
   // (levels are in dependency order: parents first)
@@ -565,6 +571,9 @@ int ensure_suggest_state(tpe_engine *h, tpe_plan *p, int64_t n_sug, size_t parti
     p->d_tie_cnt = nullptr;
     CKH(dalloc(&p->d_tie_cnt, (size_t)n_sug * p->P));
     CKH(hipMemset(p->d_tie_cnt, 0xff, (size_t)n_sug * p->P * sizeof(int32_t)));
+    dfree(p->d_tab_hot);
+    p->d_tab_hot = nullptr;
+    CKH(dalloc(&p->d_tab_hot, (size_t)n_sug * p->P));
     p->s_cap = n_sug;
   }
   if (partials > p->partial_cap) {
@@ -574,6 +583,8 @@ int ensure_suggest_state(tpe_engine *h, tpe_plan *p, int64_t n_sug, size_t parti
     dfree(p->d_tab_wmax);
     p->d_tab_wmax = nullptr;
     CKH(dalloc(&p->d_tab_wmax, partials * 8));  // (one per wave of a tile)
+    // (NaN: a slot the table pass never wrote shows no score and no -inf)
+    CKH(hipMemset(p->d_tab_wmax, 0xff, partials * 8 * sizeof(double)));
     dfree(p->d_tie_list);
     p->d_tie_list = nullptr;
     CKH(dalloc(&p->d_tie_list, partials * 8));
@@ -747,6 +758,8 @@ ScoreArgs base_args(tpe_plan *p, int64_t n_sug) {
   a.tie_list = p->d_tie_list;
   a.tie_cnt = p->d_tie_cnt;
   a.tab_tie = table_tie();
+  a.tab_bound = p->d_tab_bound;
+  a.tab_hot = p->d_tab_hot;
   return a;
 }
 
@@ -834,7 +847,8 @@ int fit_launch(tpe_engine *h, tpe_plan *p, const FitArgs &a, int32_t n_hp, hipSt
 int table_build(tpe_engine *h, tpe_plan *p, hipStream_t st) {
   if (p->tab_built) return TPE_OK;
   CKH(launch_table_build(p->d_hps, p->P, p->d_info, p->d_coef, p->kcap, p->d_tab_hdr, p->d_tab,
-                         p->census ? p->d_census : nullptr, st));
+                         p->census ? p->d_census : nullptr, st,
+                         table_prefilter_on() ? p->d_tab_bound : nullptr));
   p->tab_built = true;
   return TPE_OK;
 }
@@ -1109,6 +1123,7 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
         any |= (ck[i] == KIND_LSE_GW || ck[i] == KIND_LSE_LW) && table_hp(p->hps[hl[i]]);
       a.tab_on = any && sorted_draw && p->prune_mode == 3 && n_total > kWaveRowSplitMax &&
                          a.lse_mom == 16 && table_on() ? 1 : 0;
+      a.tab_pref = a.tab_on && table_prefilter_on() ? 1 : 0;
     }
     // lookup tiles drawing their own candidates need nothing from this
     // chunk's draw: forked onto an auxiliary stream, they run beside the draw
@@ -1991,6 +2006,7 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
       sorted |= n_cand * n_sug * (int64_t)l.size() >= ((int64_t)1 << 22);
     key.mom_w = sorted && n_cand > kWaveRowSplitMax ? mom_width(p) : 0;
     key.tab = key.mom_w == 16 && p->prune_mode == 3 && table_on();
+    key.pref = key.tab && table_prefilter_on();
   }
   int rc = ensure_suggest_state(h, p, n_sug, 1);
   if (rc) return rc;
@@ -2450,6 +2466,18 @@ static double table_tie() {
   static const double v = [] {
     const char *e = std::getenv("TPE_TABLE_TIE_LOG2");
     return e ? std::ldexp(1.0, (int)std::max(-1074L, std::min(4096L, std::atol(e)))) : kTabTie;
+  }();
+  return v;
+}
+
+// the table pass behind the prefilter: wave tiles that a certified bound of
+// the table score rules out are not scored (k_table_bound / k_table_pilot;
+// TPE_TABLE_PREFILTER=0 switches it off: same-binary A/B and the tests' child
+// processes)
+static bool table_prefilter_on() {
+  static const bool v = [] {
+    const char *e = std::getenv("TPE_TABLE_PREFILTER");
+    return !(e && *e && std::atoi(e) == 0);
   }();
   return v;
 }

@@ -269,6 +269,20 @@ static_assert(sizeof(TabHdr) == 32 && sizeof(TabPanel) == 144, "table layout");
 // the direct pass behind a suggest's table pass scores again the waves whose
 // best table score is within kTabTie max(1, |best|) of the slot's best
 constexpr double kTabTie = 0x1p-16;  // ~25x the one-exponent form's 6e-7 on a score
+// Bound lattice of an hp with two certified tables (k_table_bound, DESIGN
+// 5.10): U[c] bounds the table score, as the map computes it, from above over
+// cell c of kBndCells equal cells of [y_lo, y_hi]; +inf where no bound holds.
+// Per scoring launch k_table_pilot turns it into the slot's hot intervals
+// (TabHot): the y' ranges whose score may reach the tie window of the slot's
+// best.  A wave tile whose candidates meet none of them is not scored.
+constexpr int kBndCells = 4096;
+constexpr int kHotIv = 8;     // hot intervals per (suggestion, hp)
+constexpr int kPilotWaves = 64;  // wave tiles the pilot scores (the first sort block)
+struct __attribute__((aligned(16))) TabHot {
+  double y_lo, y_hi;                 // the table's range: candidates are clamped into it
+  double lo[kHotIv], hi[kHotIv];     // closed intervals; an unused one is (+inf, -inf)
+};
+static_assert(sizeof(TabHot) == 144, "hot-interval record");
 // the hps a table is built for
 __host__ __device__ inline bool table_hp(const tpe_hp &h) {
   return (h.family == TPE_GMM || h.family == TPE_LGMM) && !(h.flags & TPE_HAS_Q) &&
@@ -389,6 +403,12 @@ struct ScoreArgs {
   int32_t *tie_list;         // [S][P][pstride * 8] wave-tile numbers
   int32_t *tie_cnt;          // [S][P] entries of the list (0: inactive hp)
   double tab_tie;            // the tie window's relative width (kTabTie; TPE_TABLE_TIE_LOG2)
+  // tab_on 1 with the prefilter (tab_pref; TPE_TABLE_PREFILTER=0: off):
+  // k_table_pilot leaves each certified slot's hot intervals, and the table
+  // pass stores -inf for a wave tile whose candidates meet none of them
+  const double *tab_bound;   // [P][kBndCells] bound lattices (k_table_bound)
+  TabHot *tab_hot;           // [S][P] hot intervals of this launch
+  int32_t tab_pref;
   // a tile_draw launch that ends its call (pub_flag non-null): the last of its
   // pub_events final records copies all pub_words words of results into the
   // pinned pub_dst and then stores pub_seq into *pub_flag -- k_publish's
@@ -537,10 +557,12 @@ hipError_t launch_sample(const tpe_hp *hp_dev, const double *mw,
 
 hipError_t launch_micro(int which, int blocks, int iters, double *sink, hipStream_t st);
 // Chebyshev tables of both mixtures of every table_hp of the plan (headers
-// zeroed first); census: optional pair counters ([3] and [5] += node pairs)
+// zeroed first); census: optional pair counters ([3] and [5] += node pairs);
+// bound (optional): then the bound lattice of every hp whose two tables are
+// certified (k_table_bound)
 hipError_t launch_table_build(const tpe_hp *hps, int32_t n_hp, const MixInfo *info,
                               const Coef *coef, int64_t kcap, TabHdr *hdr, TabPanel *tab,
-                              unsigned long long *census, hipStream_t st);
+                              unsigned long long *census, hipStream_t st, double *bound = nullptr);
 
 // small history updates travel as kernel arguments (tpe_plan_update_history):
 // one launch, no staging copy and no host synchronisation

@@ -968,14 +968,121 @@ __global__ __launch_bounds__(kTabThreads) void k_table_build(
   if (ok) atomicAdd(&hdr[slot].ncert, 1u);
 }
 
+// ---- bound lattice of the table score ("Bound lattice") ----
+// One thread per (cell, hp) of the hps whose two tables are certified; no
+// thread reads another's result and nothing is accumulated, so the lattice is
+// the same bits wherever and whenever it is built.  The cell, widened by
+// kBndWiden of its width on both sides (rounding of its end points), is cut
+// at the panel edges of either table inside it; on a piece [xa, xb] both
+// tables are one polynomial each, P_q(t) = sum c_k T_k(t), and the score
+// S = (M_b - M_a) ln 2 + ln(P_b / P_a) is C^2, so
+//   S <= max(S(xa), S(xb)) + (xb - xa)^2 / 8 max|S''|,
+//   |S''| <= sum_q D2_q / L_q + (D1_q / L_q)^2,
+// with D1_q = (2 / w_q) sum k^2 |c_k| >= max|P_q'| and D2_q = (2 / w_q)^2
+// sum k^2 (k^2 - 1) / 3 |c_k| >= max|P_q''| over the panel (in y' units) and
+// L_q = min(P_q(xa), P_q(xb)) - (xb - xa)^2 / 8 D2_q - e_q <= P_q on the
+// piece.  e_q = 2^-46 sum|c_k| + 2^-40 sum k^2 |c_k| covers the Clenshaw
+// sum's rounding (the certificate's 64 ulp of the coefficients' absolute
+// sum) and a 2^-40 error of the panel coordinate t; the slack adds the
+// division, fast_log2 and the score's add and multiply (2^-40 relative to
+// the magnitudes involved, against their few ulp).  No positive L_q, or
+// anything non-finite: +inf (the cell is always hot).
+constexpr int kBndThreads = 256;
+constexpr double kBndWiden = 0x1p-20;
+constexpr int kBndPieces = 8;  // pieces of a cell (at most 3 for kBndCells >= kTabMaxPanels)
+static_assert(kBndCells % kBndThreads == 0 && kBndCells >= 2 * kTabMaxPanels, "lattice shape");
+
+struct BndSide {
+  double va, vb;   // the panel's Clenshaw sums at the piece's end points
+  double lo;       // lower bound of the polynomial on the piece
+  double d1, d2;   // bounds of its first and second derivative in y'
+  double e;        // absolute error of a computed sum
+  double M;
+};
+__device__ __forceinline__ BndSide bound_side(const TabHdr &h, const TabPanel *__restrict__ tab,
+                                              double xa, double xb) {
+  const double um = (0.5 * (xa + xb) - h.y_lo) * h.inv_w;
+  const double pf = fmin(fmax(floor(um), 0.0), (double)(h.P - 1));
+  const TabPanel &pn = tab[(int)pf];
+  double c[kTabNodes];
+#pragma unroll
+  for (int k = 0; k < kTabNodes; ++k) c[k] = pn.c[k];
+  const double ta = fmin(fmax(2.0 * ((xa - h.y_lo) * h.inv_w - pf) - 1.0, -1.0), 1.0);
+  const double tb = fmin(fmax(2.0 * ((xb - h.y_lo) * h.inv_w - pf) - 1.0, -1.0), 1.0);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < kTabNodes; ++k) {
+    const double a = fabs(c[k]), k2 = (double)(k * k);
+    s0 += a;
+    s1 += k2 * a;
+    s2 += k2 * (k2 - 1.0) / 3.0 * a;
+  }
+  BndSide r;
+  r.va = tab_clenshaw(c, ta);
+  r.vb = tab_clenshaw(c, tb);
+  r.d1 = s1 * (2.0 * h.inv_w);
+  r.d2 = s2 * (4.0 * h.inv_w * h.inv_w);
+  r.e = s0 * 0x1p-46 + s1 * 0x1p-40;
+  const double hh = xb - xa;
+  r.lo = fmin(r.va, r.vb) - hh * hh * 0.125 * r.d2 - r.e;
+  r.M = pn.M;
+  return r;
+}
+// the first panel edge of the table behind x (> x)
+__device__ __forceinline__ double bound_next_edge(const TabHdr &h, double x) {
+  const double w = 1.0 / h.inv_w;
+  const double j = floor((x - h.y_lo) * h.inv_w) + 1.0;
+  const double e = h.y_lo + j * w;
+  return e > x ? e : h.y_lo + (j + 1.0) * w;
+}
+
+__global__ __launch_bounds__(kBndThreads) void k_table_bound(
+    const tpe_hp *__restrict__ hps, const TabHdr *__restrict__ hdr,
+    const TabPanel *__restrict__ tab, double *__restrict__ bound) {
+  const int hp = blockIdx.y, cell = blockIdx.x * kBndThreads + threadIdx.x;
+  const tpe_hp H = hps[hp];
+  if (!table_hp(H)) return;
+  const TabHdr hb = hdr[2 * (int64_t)hp], ha = hdr[2 * (int64_t)hp + 1];
+  if (!(tab_valid(hb) && tab_valid(ha))) return;  // (no lattice: the slot takes no table pass)
+  const TabPanel *__restrict__ tb = tab + 2 * (int64_t)hp * kTabMaxPanels;
+  const TabPanel *__restrict__ ta = tb + kTabMaxPanels;
+  const double LN2 = 0.6931471805599453;
+  const double y_lo = H.low - H.prior_mu, y_hi = H.high - H.prior_mu;
+  const double cw = (y_hi - y_lo) / (double)kBndCells;
+  const double a0 = cell == 0 ? y_lo : fmax(y_lo, y_lo + cw * ((double)cell - kBndWiden));
+  const double b0 =
+      cell == kBndCells - 1 ? y_hi : fmin(y_hi, y_lo + cw * ((double)(cell + 1) + kBndWiden));
+  double U = -INFINITY, x = a0;
+  bool ok = a0 < b0;
+  for (int it = 0; it < kBndPieces && ok && x < b0; ++it) {
+    const double nx = fmin(b0, fmin(bound_next_edge(hb, x), bound_next_edge(ha, x)));
+    const BndSide B = bound_side(hb, tb, x, nx), A = bound_side(ha, ta, x, nx);
+    const double la = log2(B.va / A.va), lb = log2(B.vb / A.vb), dm = B.M - A.M;
+    const double sa = (dm + la) * LN2, sb = (dm + lb) * LN2;
+    const double gb = B.d1 / B.lo, ga = A.d1 / A.lo;
+    const double curv = B.d2 / B.lo + gb * gb + A.d2 / A.lo + ga * ga;
+    const double slack =
+        2.0 * (B.e / B.lo + A.e / A.lo) + 0x1p-40 * (1.0 + fabs(dm) + fabs(la) + fabs(lb));
+    const double hh = nx - x;
+    const double u = fmax(sa, sb) + hh * hh * 0.125 * curv + slack;
+    ok = B.lo > 0.0 && A.lo > 0.0 && sa == sa && sb == sb && u == u && u < INFINITY;
+    U = fmax(U, u);
+    x = nx;
+  }
+  ok = ok && !(x < b0);  // (every piece done)
+  bound[(int64_t)hp * kBndCells + cell] = ok ? U : INFINITY;
+}
+
 hipError_t launch_table_build(const tpe_hp *hps, int32_t n_hp, const MixInfo *info,
                               const Coef *coef, int64_t kcap, TabHdr *hdr, TabPanel *tab,
-                              unsigned long long *census, hipStream_t st) {
+                              unsigned long long *census, hipStream_t st, double *bound) {
   if (n_hp <= 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(hdr, 0, (size_t)2 * n_hp * sizeof(TabHdr), st);
   if (e != hipSuccess) return e;
   k_table_build<<<dim3(kTabMaxPanels, 2 * n_hp), kTabThreads, 0, st>>>(hps, info, coef, kcap, hdr,
                                                                        tab, census);
+  if (bound)
+    k_table_bound<<<dim3(kBndCells / kBndThreads, n_hp), kBndThreads, 0, st>>>(hps, hdr, tab, bound);
   return hipGetLastError();
 }
 

@@ -1602,22 +1602,7 @@ __device__ __forceinline__ void publish_arrive(const ScoreArgs &A) {
 // read through scalar loads panel by panel, SCALAR below, or by per-lane
 // vector loads).  The result is the LseAcc{M_p, s} the component loops would
 // leave; a NaN candidate gives NaN.
-__device__ __forceinline__ bool tab_valid(const TabHdr &h) {
-  return h.P > 0 && h.ncert == (uint32_t)h.P;
-}
-// the panel's Clenshaw sum at t: the one recurrence of both forms of tab_eval
-// (the same expression on per-lane or on scalar coefficients: the same bits)
-__device__ __forceinline__ double tab_clenshaw(const double (&c)[kTabNodes], double t) {
-  const double t2 = t + t;
-  double b1 = 0.0, b2 = 0.0;
-#pragma unroll
-  for (int k = kTabNodes - 1; k > 0; --k) {
-    const double b0 = fma(t2, b1, c[k] - b2);
-    b2 = b1;
-    b1 = b0;
-  }
-  return fma(t, b1, c[0] - b2);
-}
+// (tab_valid and the panel's Clenshaw sum tab_clenshaw: tpe_device.hpp)
 // SCALAR: the coefficients through scalar loads, one panel at a time.  The
 // rows' lanes still to do (`valid` ones: a lane without a candidate gets no
 // sum) are retired panel by panel: the first pending lane's panel as a scalar
@@ -1694,6 +1679,45 @@ __device__ __forceinline__ void tab_eval(const TabHdr *__restrict__ hdr,
       out[r] = (y[r] != y[r]) ? LseAcc{NAN, NAN} : LseAcc{M, sv};
     }
   }
+}
+
+// The prefilter of both forms of a suggest's table pass (k_table_map and
+// score_tile's TMAP path; ScoreArgs::tab_pref): true when no candidate of the
+// wave can score within the tie window of the slot's best, by the slot's hot
+// intervals (k_table_pilot) -- the minimum and maximum of the valid lanes'
+// y', clamped into the table's range as tab_eval clamps them, meet none of
+// them.  A NaN candidate or a wave without candidates is never pruned.  The
+// reduction is DPP + readlane, the intervals come in through scalar loads;
+// wave-uniform result, the same in both forms (they pass the same y').
+template <int KR>
+__device__ __forceinline__ bool tab_prefilter(const ScoreArgs &A, int s, int hp,
+                                              const double (&y)[KR], const bool (&valid)[KR]) {
+  const uint64_t ub = (uint64_t)(A.tab_hot + ((int64_t)s * A.n_hp + hp));
+  KDbl *__restrict__ hot = (KDbl *)(
+      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32)) << 32) |
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub));
+  const double y_lo = hot[0], y_hi = hot[1];
+  double mn = INFINITY, mx = -INFINITY;
+  bool nan = false, any = false;
+#pragma unroll
+  for (int r = 0; r < KR; ++r) {
+    const double yc = fmin(fmax(y[r], y_lo), y_hi);
+    nan |= valid[r] && y[r] != y[r];
+    any |= valid[r];
+    mn = fmin(mn, valid[r] ? yc : INFINITY);
+    mx = fmax(mx, valid[r] ? yc : -INFINITY);
+  }
+  if (__ballot(nan) || !__ballot(any)) return false;
+  mn = row16_min(mn);
+  mx = row16_max(mx);
+  const double wmn = fmin(fmin(bitsd(lane_value64(dbits(mn), 0)), bitsd(lane_value64(dbits(mn), 16))),
+                          fmin(bitsd(lane_value64(dbits(mn), 32)), bitsd(lane_value64(dbits(mn), 48))));
+  const double wmx = fmax(fmax(bitsd(lane_value64(dbits(mx), 0)), bitsd(lane_value64(dbits(mx), 16))),
+                          fmax(bitsd(lane_value64(dbits(mx), 32)), bitsd(lane_value64(dbits(mx), 48))));
+  bool hit = false;
+#pragma unroll
+  for (int i = 0; i < kHotIv; ++i) hit |= wmx >= hot[2 + i] && wmn <= hot[2 + kHotIv + i];
+  return !hit;
 }
 
 // TAB (k_score_table): the two-row wave tile of a slot whose two tables are
@@ -1949,12 +1973,18 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
 
   if constexpr (TAB) {
     static_assert(!TAB || (kind_wave_lse(KIND) && KR == 2), "two-row wave tiles");
+    // (TMAP: a wave the prefilter rules out evaluates nothing; its pairs are
+    // still credited below, and it leaves -inf, which no real score is)
+    bool pruned = false;  // wave-uniform
+    if constexpr (TMAP) pruned = A.tab_pref && tab_prefilter<KR>(A, s, hp, y, valid);
+    if (!pruned) {
 #pragma unroll
-    for (int mix = 0; mix < 2; ++mix) {
-      LseAcc acc[KR];
-      tab_eval<KR, TSCL>(A.tab_hdr, A.tab, mix ? sa : sb, y, valid, acc);
+      for (int mix = 0; mix < 2; ++mix) {
+        LseAcc acc[KR];
+        tab_eval<KR, TSCL>(A.tab_hdr, A.tab, mix ? sa : sb, y, valid, acc);
 #pragma unroll
-      for (int r = 0; r < KR; ++r) sm.wpart[mix][wave][r][lane] = make_double2(acc[r].m, acc[r].s);
+        for (int r = 0; r < KR; ++r) sm.wpart[mix][wave][r][lane] = make_double2(acc[r].m, acc[r].s);
+      }
     }
     if constexpr (CENSUS) {
       unsigned long long c = 0;
@@ -1965,6 +1995,13 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
       if (lane == 0) {
         atomicAdd(A.census + 3, c);
         atomicAdd(A.census + 12, c);
+      }
+    }
+    if constexpr (TMAP) {
+      if (pruned) {
+        if (lane == 0)
+          A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * kWaves + wt0 / (64 * KR)] = -INFINITY;
+        return;
       }
     }
   } else if constexpr (LSE || ERF) {
@@ -2773,48 +2810,58 @@ __global__ __launch_bounds__(kWaves * 64) void k_score_table(ScoreArgs A) {
 // leaves the tile's best EI score in tab_wmax -- what k_score_table<., true>
 // leaves, bit for bit (the same transform, sums, score expression and order:
 // a NaN first, otherwise the maximum), without that kernel's LDS round trips,
-// block state and index-carrying argmax.  Grid and block -> (group, slot,
-// tile) mapping of score_block; wave w of block tile `tile` takes wave tile 8
-// tile + w (the block reads 8 KB of candidates in one piece).  Blocks of
+// block state and index-carrying argmax.  Group and slot order of
+// score_block on a grid of its own (table_map_blocks below); wave w of block
+// tile `tile` takes wave tile 8 tile + w (the block reads 8 KB of candidates
+// in one piece per block tile).  Blocks of
 // slots without two certified tables and of inactive hps return at entry
-// (k_tie_gather handles both).  No LDS, no barrier, nothing waits.
-template <bool CENSUS>
-__global__ __launch_bounds__(kWaves * 64) void k_table_map(ScoreArgs A) {
-  constexpr int KR = tile_rows(KIND_LSE_GW);
-  static_assert(KR == 2 && tile_rows(KIND_LSE_LW) == 2, "two-row wave tiles");
-  const int b = blockIdx.x;
-  int g = 0;
-  while (g + 1 < A.n_groups && b >= A.grp_block0[g + 1]) ++g;
-  const int nt = A.grp_tiles[g];
-  const int local = xcd_local(b - A.grp_block0[g], A.grp_block0[g + 1] - A.grp_block0[g],
-                              (int)(((int64_t)blockIdx.y * gridDim.x + A.grp_block0[g]) & 7));
-  int slot = A.grp_slot0[g] + local / nt;
-  const int tile = local % nt;
-  const int s = blockIdx.y;
-  if (A.compact) {
-    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], local / nt);
-    if (slot < 0) return;
-  }
-  const int hp = A.level_hps[slot];
-  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
-  if (!(tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sa]))) return;
-  if (!(A.force_active || A.compact ||
-        hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch)))
-    return;
-  const bool logn = A.grp_kind[g] == KIND_LSE_LW;
+// (k_tie_gather handles both).  No LDS, no barrier, nothing waits.  With the
+// prefilter (ScoreArgs::tab_pref) a wave tile whose candidates meet none of
+// the slot's hot intervals leaves -inf -- below every threshold of
+// k_tie_gather and ignored by its fmax -- after the candidate load, the
+// transform and a min / max reduction, before any table sum; its pairs are
+// credited to the census all the same.
+// (table_wave_tile: the wave's work, shared with k_table_pilot.  PREF: the
+// prefilter -- a wave tile it rules out gives -inf before any table sum.)
+// (the wave tile's candidates, one per lane and row; a lane past n_cand gets
+// the transform's neutral argument)
+constexpr int kMapRows = tile_rows(KIND_LSE_GW);
+static_assert(kMapRows == 2 && tile_rows(KIND_LSE_LW) == 2, "two-row wave tiles");
+__device__ __forceinline__ void table_wave_load(const ScoreArgs &A, int s, int slot, bool logn,
+                                                int wt, double (&x)[kMapRows]) {
   const int lane = threadIdx.x & 63;
-  const int wt = tile * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const double *__restrict__ cand =
       A.cand + (int64_t)s * A.cand_sstride + (int64_t)(A.cand_slot0 + slot) * A.n_cand;
-  const double mu = A.hps[hp].prior_mu;
+#pragma unroll
+  for (int r = 0; r < kMapRows; ++r) {
+    const int64_t li = (int64_t)wt * (64 * kMapRows) + r * 64 + lane;
+    x[r] = li < A.n_cand ? cand[li] : (logn ? 1.0 : 0.0);
+  }
+}
+template <bool CENSUS, bool PREF>
+__device__ __forceinline__ double table_wave_tile(const ScoreArgs &A, int s, int hp, bool logn,
+                                                  int wt, double mu, const double (&x)[kMapRows]) {
+  constexpr int KR = kMapRows;
+  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
+  const int lane = threadIdx.x & 63;
   bool valid[KR];
   double y[KR];
 #pragma unroll
   for (int r = 0; r < KR; ++r) {
-    const int64_t li = (int64_t)wt * (64 * KR) + r * 64 + lane;
-    valid[r] = li < A.n_cand;
-    const double x = valid[r] ? cand[li] : (logn ? 1.0 : 0.0);
-    y[r] = (logn ? fast_log(x) : x) - mu;
+    valid[r] = (int64_t)wt * (64 * KR) + r * 64 + lane < A.n_cand;
+    y[r] = (logn ? fast_log(x[r]) : x[r]) - mu;
+  }
+  if constexpr (CENSUS) {
+    if (lane == 0) {
+      const unsigned long long nv =
+          (unsigned long long)min<int64_t>(64 * KR, max<int64_t>(0, A.n_cand - (int64_t)wt * (64 * KR)));
+      const unsigned long long c = nv * (unsigned long long)(A.info[sb].K + A.info[sa].K);
+      atomicAdd(A.census + 3, c);
+      atomicAdd(A.census + 12, c);
+    }
+  }
+  if constexpr (PREF) {
+    if (A.tab_pref && tab_prefilter<KR>(A, s, hp, y, valid)) return -INFINITY;
   }
   LseAcc lb[KR], la[KR];
   tab_eval<KR, true>(A.tab_hdr, A.tab, sb, y, valid, lb);
@@ -2839,16 +2886,166 @@ __global__ __launch_bounds__(kWaves * 64) void k_table_map(ScoreArgs A) {
 #pragma unroll
   for (int r = KR - 1; r >= 0; --r)
     if (nanm[r]) best = bitsd(lane_value64(dbits(sc[r]), (int)__builtin_ctzll(nanm[r])));
-  if constexpr (CENSUS) {
-    if (lane == 0) {
-      const unsigned long long nv =
-          (unsigned long long)min<int64_t>(64 * KR, max<int64_t>(0, A.n_cand - (int64_t)wt * (64 * KR)));
-      const unsigned long long c = nv * (unsigned long long)(A.info[sb].K + A.info[sa].K);
-      atomicAdd(A.census + 3, c);
-      atomicAdd(A.census + 12, c);
-    }
+  return best;
+}
+// The map's own grid: a block takes kMapTiles consecutive block tiles of its
+// slot (wave w of it the wave tiles 8 tile + w of each), so that the block's
+// set-up -- group search, slot, headers, activity -- is paid once per
+// kMapTiles wave tiles of a wave and their candidate loads are in flight
+// together: with the prefilter a wave tile is little more than its load.
+// Blocks per group: its rows x ceil(tiles / kMapTiles) (table_map_blocks).
+constexpr int kMapTiles = 4;
+__host__ __device__ inline int table_map_blocks(const ScoreArgs &A, int g) {
+  const int rows = (A.grp_block0[g + 1] - A.grp_block0[g]) / A.grp_tiles[g];
+  return rows * ((A.grp_tiles[g] + kMapTiles - 1) / kMapTiles);
+}
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) void k_table_map(ScoreArgs A) {
+  constexpr int KR = kMapRows;
+  const int b = blockIdx.x;
+  int g = 0, b0 = 0;  // the block's group and that group's first block
+  for (; g + 1 < A.n_groups; ++g) {
+    const int nb = table_map_blocks(A, g);
+    if (b < b0 + nb) break;
+    b0 += nb;
   }
-  if (lane == 0) A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * kWaves + wt] = best;
+  const int nt = A.grp_tiles[g], ntb = (nt + kMapTiles - 1) / kMapTiles;
+  const int local = xcd_local(b - b0, table_map_blocks(A, g),
+                              (int)(((int64_t)blockIdx.y * gridDim.x + b0) & 7));
+  int slot = A.grp_slot0[g] + local / ntb;
+  const int tile0 = (local % ntb) * kMapTiles;
+  const int s = blockIdx.y;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], local / ntb);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
+  if (!(tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sa]))) return;
+  if (!(A.force_active || A.compact ||
+        hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch)))
+    return;
+  const bool logn = A.grp_kind[g] == KIND_LSE_LW;
+  const double mu = A.hps[hp].prior_mu;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int ntl = min(kMapTiles, nt - tile0);  // (block-uniform, >= 1)
+  double x[kMapTiles][KR];
+#pragma unroll
+  for (int j = 0; j < kMapTiles; ++j)
+    if (j < ntl) table_wave_load(A, s, slot, logn, (tile0 + j) * kWaves + wave, x[j]);
+  double *__restrict__ wmax = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * kWaves;
+#pragma unroll
+  for (int j = 0; j < kMapTiles; ++j) {
+    if (j >= ntl) break;
+    const int wt = (tile0 + j) * kWaves + wave;
+    const double best = table_wave_tile<CENSUS, true>(A, s, hp, logn, wt, mu, x[j]);
+    if ((threadIdx.x & 63) == 0) wmax[wt] = best;
+  }
+}
+
+// Ahead of the table pass of a tab_on 1 launch with the prefilter: one block
+// per (row, suggestion), k_tie_gather's row -> slot mapping; slots that are
+// inactive or without two certified tables need nothing (their map blocks
+// return at entry).  The block scores the launch's first kPilotWaves wave
+// tiles of the slot (the first sort block: a sample over the whole value
+// range) with the map's own code: L0, their best in better()'s order on
+// scores, is a lower bound of the slot's tab_max made of real scores of this
+// launch.  With T0 = L0 - tab_tie max(1, |L0|) -- k_tie_gather's expression
+// on L0 -- a lattice cell with U < T0 cannot hold a hot candidate (DESIGN
+// 5.10); the others, each widened by one cell on both sides (rounding of the
+// cell boundaries), are merged into at most kHotIv closed intervals of y',
+// the nearest runs first when there are more (a superset is always fine).
+// L0 NaN or infinite: one interval, everything.  Thread 0 walks the cells'
+// hot bits in ascending order: the intervals depend on the scores and the
+// lattice alone.
+constexpr int kPilotThreads = 1024;
+__global__ __launch_bounds__(kPilotThreads) void k_table_pilot(ScoreArgs A) {
+  constexpr int NW = kPilotThreads / 64;
+  constexpr int WC = 64 * tile_rows(KIND_LSE_GW);
+  constexpr int NWORD = kBndCells / 64;
+  static_assert(kBndCells % kPilotThreads == 0 && kPilotWaves % NW == 0, "pilot shape");
+  __shared__ double wsc[kPilotWaves];
+  __shared__ unsigned long long hotw[NWORD];
+  const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int row = blockIdx.x;
+  const int g = row_group(A, row);
+  int slot = A.grp_slot0[g] + row;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], row);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  if (!(tab_valid(A.tab_hdr[2 * (int64_t)hp]) && tab_valid(A.tab_hdr[2 * (int64_t)hp + 1]))) return;
+  if (!(A.force_active || A.compact ||
+        hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch)))
+    return;
+  const int np = (int)min<int64_t>(min(kPilotWaves, A.grp_tiles[g] * kWaves), (A.n_cand + WC - 1) / WC);
+  const bool logn = A.grp_kind[g] == KIND_LSE_LW;
+  const double mu = A.hps[hp].prior_mu;
+  for (int wt = wave; wt < np; wt += NW) {  // (wave-uniform)
+    double x[kMapRows];
+    table_wave_load(A, s, slot, logn, wt, x);
+    const double v = table_wave_tile<false, false>(A, s, hp, logn, wt, mu, x);
+    if (lane == 0) wsc[wt] = v;
+  }
+  __syncthreads();
+  double L0 = np > 0 ? -INFINITY : NAN;
+  for (int i = 0; i < np; ++i) {
+    const double v = wsc[i];
+    L0 = (v != v || L0 != L0) ? NAN : fmax(L0, v);
+  }
+  const double T0 = L0 - A.tab_tie * fmax(1.0, fabs(L0));
+  const bool all = !(L0 == L0) || fabs(L0) == INFINITY;
+  const double *__restrict__ U = A.tab_bound + (int64_t)hp * kBndCells;
+  for (int c0 = 0; c0 < kBndCells; c0 += kPilotThreads) {
+    const uint64_t bal = __ballot(all || !(U[c0 + tid] < T0));
+    if (lane == 0) hotw[(c0 + tid) >> 6] = bal;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const tpe_hp H = A.hps[hp];
+  const double y_lo = H.low - H.prior_mu, y_hi = H.high - H.prior_mu;
+  const double cw = (y_hi - y_lo) / (double)kBndCells;
+  // runs of hot cells, widened, as cell ranges [c0, c1]; kept at most kHotIv:
+  // a further run first joins the two neighbours with the smallest gap
+  int r0[kHotIv + 1], r1[kHotIv + 1], n = 0;
+  // the first cell at or behind c whose hot bit is `hot` (kBndCells: none)
+  auto next_cell = [&](int c, bool hot) {
+    while (c < kBndCells) {
+      const unsigned long long w = (hot ? hotw[c >> 6] : ~hotw[c >> 6]) >> (c & 63);
+      if (w) return c + (int)__builtin_ctzll(w);
+      c = (c | 63) + 1;
+    }
+    return (int)kBndCells;
+  };
+  for (int c = next_cell(0, true); c < kBndCells;) {
+    const int e = next_cell(c, false);  // the run: cells c .. e - 1
+    const int a0 = max(c - 1, 0), a1 = min(e, kBndCells - 1);  // (widened)
+    if (n > 0 && a0 <= r1[n - 1] + 1) {
+      r1[n - 1] = a1;
+    } else {
+      r0[n] = a0;
+      r1[n] = a1;
+      if (++n > kHotIv) {
+        int bj = 1, bg = r0[1] - r1[0];
+        for (int j = 2; j < n; ++j)
+          if (r0[j] - r1[j - 1] < bg) { bg = r0[j] - r1[j - 1]; bj = j; }
+        r1[bj - 1] = r1[bj];
+        for (int j = bj; j + 1 < n; ++j) { r0[j] = r0[j + 1]; r1[j] = r1[j + 1]; }
+        --n;
+      }
+    }
+    c = next_cell(e, true);
+  }
+  TabHot *out = A.tab_hot + ((int64_t)s * A.n_hp + hp);
+  out->y_lo = y_lo;
+  out->y_hi = y_hi;
+  for (int i = 0; i < kHotIv; ++i) {
+    const bool on = i < n;
+    out->lo[i] = !on ? INFINITY : r0[i] == 0 ? -INFINITY : y_lo + cw * (double)r0[i];
+    out->hi[i] = !on ? -INFINITY : r1[i] == kBndCells - 1 ? INFINITY : y_lo + cw * (double)(r1[i] + 1);
+  }
 }
 
 // Between the two passes of a tab_on 1 launch: one block per (row,
@@ -3281,19 +3478,27 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
       // score), the gather of each slot's hot wave tiles into dense blocks,
       // then the direct pass over those (gated on the 16-wide class)
       if (!a.tie_list || !a.tie_cnt) return hipErrorInvalidValue;
-      if (table_scalar_on()) {
-        if (a.census) k_table_map<true><<<g, kWaves * 64, 0, st>>>(a);
-        else k_table_map<false><<<g, kWaves * 64, 0, st>>>(a);
-      } else {
-        if (a.census) k_score_table<true, true><<<g, kWaves * 64, 0, st>>>(a);
-        else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
-      }
       int32_t rows = 0, ntmax = 1;
       for (int i = 0; i < a.n_groups; ++i) {
         rows += (a.grp_block0[i + 1] - a.grp_block0[i]) / a.grp_tiles[i];
         ntmax = std::max(ntmax, a.grp_tiles[i]);
       }
       if (rows <= 0 || rows > 65535 || a.n_suggest > 65535) return hipErrorInvalidValue;
+      // the prefilter's hot intervals of this launch, ahead of either map form
+      if (a.tab_pref) {
+        if (!a.tab_bound || !a.tab_hot) return hipErrorInvalidValue;
+        k_table_pilot<<<dim3((unsigned)rows, a.n_suggest), kPilotThreads, 0, st>>>(a);
+      }
+      if (table_scalar_on()) {
+        int32_t mb = 0;
+        for (int i = 0; i < a.n_groups; ++i) mb += table_map_blocks(a, i);
+        const dim3 gm((unsigned)mb, a.n_suggest);
+        if (a.census) k_table_map<true><<<gm, kWaves * 64, 0, st>>>(a);
+        else k_table_map<false><<<gm, kWaves * 64, 0, st>>>(a);
+      } else {
+        if (a.census) k_score_table<true, true><<<g, kWaves * 64, 0, st>>>(a);
+        else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
+      }
       k_tie_gather<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
       // persistent blocks per slot: ~tie_blocks_per_cu() blocks per CU over
       // the launch's (row, suggestion) pairs, so that a single all-hot slot

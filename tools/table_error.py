@@ -8,10 +8,17 @@ relative error at random points of each panel against the certified bound.
     python tools/table_error.py                 # the test shape (tests/test_gpu_table.py)
     python tools/table_error.py --gap u:-1.5:1.5
     python tools/table_error.py --cfg4 --every 7
+    python tools/table_error.py --prefilter          # and --cfg4 --every 37, --low-edge
 
 --gap LABEL:LO:HI moves the history values of LABEL inside (LO, HI) out of the
 interval (an empty gap: the edge components widen, the panels beside them lose
 their certificate).  Prints one line per (hp, side) and exits 0.
+
+--prefilter adds, per hp with two certified tables, the emulation of the table
+pass's prefilter (bound lattice, hot intervals, bucketed wave tiles) on
+--draws draws of the below mixture: cells hot, wave tiles passing, hot wave
+tiles missed (which must be 0).  --low-edge takes a history whose good trials
+cluster at the lower bound instead of the test shape.
 """
 import argparse
 import math
@@ -99,6 +106,230 @@ def evaluate(tab, y):
     return tab['M'][p] + np.log2(t * b1 + (c[:, 0] - b2))
 
 
+# ---- the prefilter of the table pass (k_table_bound / k_table_pilot /
+# tab_prefilter): bound lattice, hot intervals, bucketed waves ----
+CELLS = 4096          # kBndCells
+HOT_IV = 8            # kHotIv
+WIDEN = 2.0 ** -20    # kBndWiden
+PILOT_WAVES = 64      # kPilotWaves
+TIE = 2.0 ** -16      # kTabTie
+SORT_BLOCK, BUCKETS, WAVE = 8192, 256, 128
+LN2 = 0.6931471805599453
+_K = np.arange(NODES, dtype=np.float64)
+_K2 = _K * _K
+_K4 = _K2 * (_K2 - 1.0) / 3.0
+
+
+def _panel(tab, y):
+    u = (y - tab['y_lo']) / tab['width']
+    p = np.clip(np.floor(u), 0, tab['P'] - 1).astype(int)
+    return p, np.clip(2.0 * (u - p) - 1.0, -1.0, 1.0)
+
+
+def _clenshaw(c, t):
+    b1 = np.zeros_like(t)
+    b2 = np.zeros_like(t)
+    for k in range(NODES - 1, 0, -1):
+        b1, b2 = 2.0 * t * b1 + (c[:, k] - b2), b1
+    return t * b1 + (c[:, 0] - b2)
+
+
+def score(tb, ta, y):
+    """The table score as the map computes it: ((M_b - M_a) + log2(s_b / s_a)) ln 2,
+    y' clamped into the tables' range by the panel coordinates."""
+    y = np.asarray(y, dtype=np.float64)
+    pb, tbv = _panel(tb, y)
+    pa, tav = _panel(ta, y)
+    sb, sa = _clenshaw(tb['coef'][pb], tbv), _clenshaw(ta['coef'][pa], tav)
+    return ((tb['M'][pb] - ta['M'][pa]) + np.log2(sb / sa)) * LN2
+
+
+def _next_edge(tab, x):
+    j = np.floor((x - tab['y_lo']) / tab['width']) + 1.0
+    e = tab['y_lo'] + j * tab['width']
+    return np.where(e > x, e, tab['y_lo'] + (j + 1.0) * tab['width'])
+
+
+def _bound_side(tab, xa, xb):
+    p, _ = _panel(tab, 0.5 * (xa + xb))
+    c = tab['coef'][p]
+    inv_w = 1.0 / tab['width']
+    ta = np.clip(2.0 * ((xa - tab['y_lo']) * inv_w - p) - 1.0, -1.0, 1.0)
+    tb = np.clip(2.0 * ((xb - tab['y_lo']) * inv_w - p) - 1.0, -1.0, 1.0)
+    a = np.abs(c)
+    s0, s1, s2 = a.sum(1), (a * _K2).sum(1), (a * _K4).sum(1)
+    va, vb = _clenshaw(c, ta), _clenshaw(c, tb)
+    d1, d2 = s1 * 2.0 * inv_w, s2 * 4.0 * inv_w * inv_w
+    e = s0 * 2.0 ** -46 + s1 * 2.0 ** -40
+    h = xb - xa
+    return dict(va=va, vb=vb, d1=d1, d2=d2, e=e, lo=np.minimum(va, vb) - h * h * 0.125 * d2 - e,
+                M=tab['M'][p])
+
+
+def bound_lattice(tb, ta, cells=CELLS):
+    """U[c] >= the table score anywhere in cell c of `cells` equal cells of
+    [y_lo, y_hi] (k_table_bound): per piece between panel edges the end-point
+    scores plus (piece width)^2 / 8 max|S''| plus the rounding slack; +inf
+    where no bound holds."""
+    y_lo = tb['y_lo']
+    y_hi = y_lo + tb['width'] * tb['P']
+    cw = (y_hi - y_lo) / cells
+    c = np.arange(cells, dtype=np.float64)
+    a0 = np.maximum(y_lo, y_lo + cw * (c - WIDEN))
+    b0 = np.minimum(y_hi, y_lo + cw * (c + 1.0 + WIDEN))
+    a0[0], b0[-1] = y_lo, y_hi
+    U = np.full(cells, -np.inf)
+    ok = a0 < b0
+    x = a0.copy()
+    with np.errstate(all='ignore'):
+        for _ in range(8):
+            act = ok & (x < b0)
+            if not act.any():
+                break
+            xs = x[act]
+            nx = np.minimum(b0[act], np.minimum(_next_edge(tb, xs), _next_edge(ta, xs)))
+            B, A = _bound_side(tb, xs, nx), _bound_side(ta, xs, nx)
+            la, lb, dm = np.log2(B['va'] / A['va']), np.log2(B['vb'] / A['vb']), B['M'] - A['M']
+            sa, sb = (dm + la) * LN2, (dm + lb) * LN2
+            gb, ga = B['d1'] / B['lo'], A['d1'] / A['lo']
+            curv = B['d2'] / B['lo'] + gb * gb + A['d2'] / A['lo'] + ga * ga
+            slack = (2.0 * (B['e'] / B['lo'] + A['e'] / A['lo']) +
+                     2.0 ** -40 * (1.0 + np.abs(dm) + np.abs(la) + np.abs(lb)))
+            h = nx - xs
+            u = np.maximum(sa, sb) + h * h * 0.125 * curv + slack
+            good = (B['lo'] > 0) & (A['lo'] > 0) & np.isfinite(u) & ~np.isnan(sa) & ~np.isnan(sb)
+            idx = np.flatnonzero(act)
+            ok[idx] &= good
+            U[idx] = np.fmax(U[idx], u)
+            x[idx] = nx
+    ok &= ~(x < b0)
+    return np.where(ok, U, np.inf)
+
+
+def hot_intervals(U, L0, y_lo, y_hi, tie=TIE):
+    """k_table_pilot's intervals: the cells with !(U < T0), each widened by one
+    cell on both sides, merged into at most HOT_IV closed y' intervals (the
+    nearest runs first).  Returns (intervals, hot cell mask)."""
+    cells = U.size
+    cw = (y_hi - y_lo) / cells
+    if not np.isfinite(L0):
+        return [(-np.inf, np.inf)], np.ones(cells, dtype=bool)
+    with np.errstate(all='ignore'):
+        T0 = L0 - tie * max(1.0, abs(L0))
+        hot = ~(U < T0)
+    runs = []
+    d = np.diff(np.concatenate([[0], hot.astype(np.int8), [0]]))
+    for c, e in zip(np.flatnonzero(d == 1), np.flatnonzero(d == -1)):   # cells c .. e - 1
+        a0, a1 = max(c - 1, 0), min(e, cells - 1)
+        if runs and a0 <= runs[-1][1] + 1:
+            runs[-1][1] = a1
+            continue
+        runs.append([a0, a1])
+        if len(runs) > HOT_IV:
+            gaps = [runs[j][0] - runs[j - 1][1] for j in range(1, len(runs))]
+            j = 1 + int(np.argmin(gaps))
+            runs[j - 1][1] = runs[j][1]
+            del runs[j]
+    return [(-np.inf if a == 0 else y_lo + cw * a, np.inf if b == cells - 1 else y_lo + cw * (b + 1))
+            for a, b in runs], hot
+
+
+def draw_below(w, mu, sigma, low, high, center, n, rs):
+    """n draws of the truncated mixture, as y' (rejection, numpy's stream)."""
+    out = np.empty(0)
+    p = np.asarray(w) / np.sum(w)
+    while out.size < n:
+        k = rs.choice(p.size, size=2 * n, p=p)
+        x = rs.normal(np.asarray(mu)[k], np.asarray(sigma)[k])
+        out = np.concatenate([out, x[(x >= low) & (x < high)]])
+    return out[:n] - center
+
+
+def bucketed_waves(y, y_lo, y_hi):
+    """The draw's value bucketing (k_draw_sorted): sort blocks of SORT_BLOCK
+    candidates, each grouped stably into BUCKETS equal-width buckets of
+    [y_lo, y_hi]; wave tiles are WAVE consecutive candidates of the result.
+    Returns (y in bucketed order, list of (begin, end) per wave tile)."""
+    out = np.empty_like(y)
+    for b0 in range(0, y.size, SORT_BLOCK):
+        blk = y[b0:b0 + SORT_BLOCK]
+        key = np.clip(np.floor((blk - y_lo) / (y_hi - y_lo) * BUCKETS), 0, BUCKETS - 1)
+        out[b0:b0 + blk.size] = blk[np.argsort(key, kind='stable')]
+    return out, [(i, min(i + WAVE, y.size)) for i in range(0, y.size, WAVE)]
+
+
+def prefilter(tb, ta, y, tie=TIE, cells=CELLS):
+    """The whole prefilter on bucketed candidates y (one launch): dict with
+    the lattice U, the hot cell mask, the intervals, per wave tile its best
+    score `wmax` and whether it is pruned, the slot's tab_max and the
+    threshold T(tab_max) of k_tie_gather."""
+    y_lo = tb['y_lo']
+    y_hi = y_lo + tb['width'] * tb['P']
+    U = bound_lattice(tb, ta, cells)
+    yb, waves = bucketed_waves(y, y_lo, y_hi)
+    sc = score(tb, ta, yb)
+    wmax = np.array([sc[a:b].max() for a, b in waves])
+    L0 = wmax[:PILOT_WAVES].max()
+    iv, hot = hot_intervals(U, L0, y_lo, y_hi, tie)
+    yc = np.clip(yb, y_lo, y_hi)
+    pruned = np.ones(len(waves), dtype=bool)
+    for i, (a, b) in enumerate(waves):
+        mn, mx = yc[a:b].min(), yc[a:b].max()
+        pruned[i] = not any(mx >= lo and mn <= hi for lo, hi in iv)
+    tab_max = wmax.max()
+    return dict(U=U, hot=hot, intervals=iv, wmax=wmax, pruned=pruned, L0=L0, tab_max=tab_max,
+                thr=tab_max - tie * max(1.0, abs(tab_max)))
+
+
+def mixtures(losses, cols, label, dist, args):
+    """Both sides' (w, mu, sigma) of one hp, and (low, high, centre)."""
+    tids = np.arange(losses.size)
+    fk, pm, ps, low, high, q, tr = O.posterior_spec(dist, args, 1.0)
+    bo, ao = O.split_observations(tids, cols[label], tids, losses, 0.25, kind='stable')
+    fit = [tuple(np.asarray(v) for v in O.parzen_fit(O.transform_obs(obs, tr, low), 1.0, pm, ps,
+                                                      kind='stable')) for obs in (bo, ao)]
+    return fit, (low, high, pm)
+
+
+def certified_pair(losses, cols, label, dist, args):
+    """(tb, ta, below mixture, (low, high, centre)) of an hp whose two tables
+    are certified, else None."""
+    fit, (low, high, pm) = mixtures(losses, cols, label, dist, args)
+    tabs = [build(w, mu, sg, low, high, pm) for w, mu, sg in fit]
+    if any(t is None or not t['ok'].all() for t in tabs):
+        return None
+    return tabs[0], tabs[1], fit[0], (low, high, pm)
+
+
+def low_edge_shape(n=6000):
+    """A history whose EI maximum sits at `low`: the good trials cluster at the
+    lower bound of a uniform(-5, 5) (config 4's hp 0 behaves like this)."""
+    rs = np.random.RandomState(31)
+    v = rs.uniform(-5, 5, n)
+    losses = (v + 5.0) / 10.0 + 0.05 * rs.rand(n)
+    return losses, {'e': v}, {'e': ('uniform', (-5.0, 5.0))}
+
+
+def report_prefilter(losses, cols, specs, every=1, draws=1 << 18):
+    rs = np.random.RandomState(7)
+    for i, (label, (dist, args)) in enumerate(specs.items()):
+        if i % every:
+            continue
+        pair = certified_pair(losses, cols, label, dist, args)
+        if pair is None:
+            print('%-4s prefilter: no certified pair, every wave tile scored' % label)
+            continue
+        tb, ta, (w, mu, sg), (low, high, pm) = pair
+        r = prefilter(tb, ta, draw_below(w, mu, sg, low, high, pm, draws, rs))
+        missed = int((r['pruned'] & ~(r['wmax'] < r['thr'])).sum())
+        print('%-4s prefilter: cells hot %d / %d (%.2f %%), intervals %d, wave tiles passing %d / %d '
+              '(%.2f %%), hot wave tiles %d, missed %d'
+              % (label, int(r['hot'].sum()), r['hot'].size, 100.0 * r['hot'].mean(),
+                 len(r['intervals']), int((~r['pruned']).sum()), r['pruned'].size,
+                 100.0 * (~r['pruned']).mean(), int((~(r['wmax'] < r['thr'])).sum()), missed))
+        assert missed == 0, 'a hot wave tile was pruned'
+
+
 def report(label, side, w, mu, sigma, low, high, center, rs, pts=200):
     tab = build(w, mu, sigma, low, high, center)
     if tab is None:
@@ -161,6 +392,9 @@ def main():
     ap.add_argument('--gap', default=None, help='LABEL:LO:HI')
     ap.add_argument('--cfg4', action='store_true', help="bench.py config 4's history")
     ap.add_argument('--every', type=int, default=1, help='every n-th hp')
+    ap.add_argument('--prefilter', action='store_true', help='report the prefilter emulation')
+    ap.add_argument('--low-edge', action='store_true', help='good trials clustered at low')
+    ap.add_argument('--draws', type=int, default=1 << 18, help='--prefilter: draws per hp')
     a = ap.parse_args()
     if a.cfg4:
         sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -168,6 +402,8 @@ def main():
         dom, losses, vals, act = bench.build_workload('cfg4')
         cols = {h.label: vals[h.index] for h in dom.space.hps}
         specs = {h.label: ('uniform', (-5.0, 5.0)) for h in dom.space.hps}
+    elif a.low_edge:
+        losses, cols, specs = low_edge_shape(a.n)
     else:
         gap = None
         if a.gap:
@@ -175,6 +411,8 @@ def main():
             gap = (lab, float(lo), float(hi))
         losses, cols, specs = test_shape(a.n, gap)
     run(losses, cols, specs, a.every)
+    if a.prefilter:
+        report_prefilter(losses, cols, specs, a.every, a.draws)
 
 
 if __name__ == '__main__':
