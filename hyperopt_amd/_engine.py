@@ -43,7 +43,7 @@ EXPORTS = (
     'tpe_plan_set_lattice', 'tpe_plan_update_history', 'tpe_plan_set_prune',
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
     'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
-    'tpe_plan_set_anneal_order',
+    'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -162,6 +162,8 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_census_n': (C.c_int, [vp, i32, C.POINTER(i64), i32]),
             'tpe_plan_tie_counts': (C.c_int, [vp, i32, vp]),
             'tpe_plan_tab_wmax': (C.c_int, [vp, i32, vp]),
+            'tpe_plan_tab_bound': (C.c_int, [vp, i32, vp]),
+            'tpe_plan_tab_hot': (C.c_int, [vp, i32, vp]),
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
             'tpe_plan_set_prune': (C.c_int, [vp, i32]),
             'tpe_plan_sample_prior': (C.c_int, [vp, C.POINTER(u64), i64, vp, i32, vp]),
@@ -656,6 +658,30 @@ class Plan(object):
             e.check(min(w, 0))
             out = np.empty((int(n_suggest), self.n_hp, w), dtype=np.float64)
             e.check(e.lib.tpe_plan_tab_wmax(self.p, int(n_suggest), out.ctypes.data))
+        return out
+
+    def tab_bound(self, hp):
+        """Debug (tpe_plan_tab_bound): float64 [4096], the bound lattice of one
+        hp as the last fit left it -- an upper bound of the table score over
+        each of 4096 equal cells of the hp's range; an error when the hp takes
+        no table, a side is not certified or the prefilter is off."""
+        e = self.engine
+        with e.lock:
+            n = e.lib.tpe_plan_tab_bound(self.p, int(hp), None)
+            e.check(min(n, 0))
+            out = np.empty(n, dtype=np.float64)
+            e.check(e.lib.tpe_plan_tab_bound(self.p, int(hp), out.ctypes.data))
+        return out
+
+    def tab_hot(self, n_suggest):
+        """Debug (tpe_plan_tab_hot): float64 [n_suggest][n_hp][18] = y_lo,
+        y_hi, lo[8], hi[8], the hot intervals of the last scoring launch that
+        ran the prefilter's pilot; entries of slots it skipped are
+        unspecified."""
+        e = self.engine
+        out = np.empty((int(n_suggest), self.n_hp, 18), dtype=np.float64)
+        with e.lock:
+            e.check(e.lib.tpe_plan_tab_hot(self.p, int(n_suggest), out.ctypes.data))
         return out
 
     def last_stats(self):

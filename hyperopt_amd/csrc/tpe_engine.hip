@@ -2269,6 +2269,42 @@ int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out) {
   return TPE_OK;
 }
 
+int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out) {
+  if (!p) return TPE_E_INVALID;
+  if (!out) return kBndCells;
+  tpe_engine *h = p->eng;
+  if (hp < 0 || hp >= p->P) return fail(h, TPE_E_INVALID, "bad args");
+  if (!table_hp(p->hps[hp])) return fail(h, TPE_E_INVALID, "hp has no Chebyshev table");
+  if (!table_prefilter_on()) return fail(h, TPE_E_INVALID, "no bound lattice: the prefilter is off");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const int rc = table_build(h, p, h->stream);  // (this fit epoch's, if no launch has built them)
+  if (rc) return rc;
+  TabHdr th[2];
+  CKH(hipMemcpyAsync(th, p->d_tab_hdr + 2 * (int64_t)hp, sizeof(th), hipMemcpyDeviceToHost,
+                     h->stream));
+  CKH(hipStreamSynchronize(h->stream));
+  for (const TabHdr &t : th)
+    if (!(t.P > 0 && t.ncert == (uint32_t)t.P))
+      return fail(h, TPE_E_INVALID, "Chebyshev table not certified");
+  CKH(hipMemcpy(out, p->d_tab_bound + (int64_t)hp * kBndCells, kBndCells * sizeof(double),
+                hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+int tpe_plan_tab_hot(tpe_plan_t p, int32_t n_suggest, double *out) {
+  static_assert(sizeof(TabHot) == (2 + 2 * kHotIv) * sizeof(double), "y_lo, y_hi, lo[], hi[]");
+  if (!p || !out || n_suggest < 0) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (n_suggest > p->s_cap) return fail(h, TPE_E_INVALID, "more suggestions than the last call's");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  if (n_suggest > 0)
+    CKH(hipMemcpy(out, p->d_tab_hot, (size_t)n_suggest * p->P * sizeof(TabHot),
+                  hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
 int tpe_plan_sample_prior(tpe_plan_t p, const uint64_t *seeds, int64_t n_sug, tpe_result *out,
                           int32_t out_on_device, void *stream) {
   if (!p) return TPE_E_INVALID;

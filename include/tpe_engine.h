@@ -335,6 +335,23 @@ int tpe_plan_tie_counts(tpe_plan_t p, int32_t n_suggest, int32_t *counts);
  * written are unspecified.  out == NULL: returns W (0: no such launch yet)
  * and copies nothing.  Synchronizes the device.                              */
 int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out);
+/* Debug: out[c], c < 4096, the bound lattice of hp as the last fit left it:
+ * an upper bound of the table score (the EI score the table pass computes)
+ * over cell c of 4096 equal cells of [low, high] in the fitted domain, +inf
+ * where no bound holds.  Builds the tables of the current fit if no launch
+ * has yet.  out == NULL: returns the cell count and copies nothing.
+ * TPE_E_INVALID when the hp takes no table, either side's table is not
+ * certified or the prefilter is off (no lattice).  Synchronizes the device.  */
+int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out);
+/* Debug: out[(s * n_hp + hp) * 18 + ...] = y_lo, y_hi, lo[8], hi[8], s <
+ * n_suggest (at most the last call's): the hot intervals of hp -- closed
+ * intervals [lo[i], hi[i]] of the centred fitted-domain value, an unused one
+ * (+inf, -inf), outside of which no wave tile is table-scored -- and the range
+ * [y_lo, y_hi] candidates are clamped into, as the plan's last scoring launch
+ * that ran the prefilter's pilot left them.  Entries of hps without two
+ * certified tables, of inactive hps and of hps no such launch has scored are
+ * unspecified.  Synchronizes the device.                                    */
+int tpe_plan_tab_hot(tpe_plan_t p, int32_t n_suggest, double *out);
 
 /* Prior draws of n_suggest whole suggestions (rand.suggest, the TPE startup
  * phase: hyperopt/rand.py:14-33, pyll/stochastic.py:30-142): every active hp

@@ -4,8 +4,11 @@ pilot score leaves, and the pruning of value-bucketed wave tiles.
 
 Histories: the shape of test_gpu_table.py (N = 6000, hps u and lu); one whose
 good trials cluster at the lower bound, so the EI maximum sits at `low`
-(config 4's hp 0 behaves like this); and the gap history (--gap u:-3:0), where
-u has no certified pair -- it takes no lattice and is skipped -- and lu does.
+(config 4's hp 0 behaves like this), its mirror at `high`, the band (99 % of
+the trials a quarter unit wide: the certificate closest to its bar) and the
+comb (a local maximum of the score per tooth); the gap history (--gap
+u:-3:0), where u has no certified pair -- it takes no lattice and is skipped
+-- and lu does; and the ties history (half-unit values), which has none either.
 
 Per hp: every cell's bound holds at both end points, the midpoint and 16
 random points (cells straddling a panel edge of either table and the two edge
@@ -33,6 +36,9 @@ def _histories():
         out['shape-' + lab] = (losses, cols, lab, specs[lab])
     losses, cols, specs = TE.low_edge_shape(6000)
     out['low-edge'] = (losses, cols, 'e', specs['e'])
+    for name in ('high-edge', 'band', 'comb', 'ties'):
+        losses, cols, specs = TE.NAMED[name](6000)
+        out[name] = (losses, cols, 'e', specs['e'])
     losses, cols, specs = TE.test_shape(6000, ('u', -3.0, 0.0))
     for lab in ('u', 'lu'):
         out['gap-' + lab] = (losses, cols, lab, specs[lab])
@@ -40,7 +46,7 @@ def _histories():
 
 
 HIST = _histories()
-CERTIFIED = ('shape-u', 'shape-lu', 'low-edge', 'gap-lu')
+CERTIFIED = ('shape-u', 'shape-lu', 'low-edge', 'gap-lu', 'high-edge', 'band', 'comb')
 
 
 @pytest.fixture(scope='module')
@@ -49,8 +55,10 @@ def pairs():
 
 
 def test_gap_slot_has_no_pair(pairs):
-    """u of the gap history loses panels of its above table: no lattice."""
+    """u of the gap history loses panels of its above table, the ties
+    history one: no lattice."""
     assert pairs['gap-u'] is None
+    assert pairs['ties'] is None
     for k in CERTIFIED:
         assert pairs[k] is not None, k
 
@@ -116,6 +124,34 @@ def test_all_hot_settings(pairs):
         assert iv == [(-np.inf, np.inf)] and hot.all()
     iv, hot = TE.hot_intervals(U, 1.0, y_lo, y_hi, tie=np.inf)
     assert iv == [(-np.inf, np.inf)] and hot.all()
+
+
+def test_comb_lattice_takes_the_merge(pairs):
+    """The comb's real lattice under a tie window of 1.0: more than HOT_IV
+    runs are merged into exactly HOT_IV intervals, every hot cell stays
+    covered, some wave tile is pruned and no hot one."""
+    tb, ta, (w, mu, sg), (low, high, pm) = pairs['comb']
+    y = TE.draw_below(w, mu, sg, low, high, pm, DRAWS, np.random.RandomState(23))
+    r = TE.prefilter(tb, ta, y, tie=1.0)
+    y_lo, y_hi = tb['y_lo'], tb['y_lo'] + tb['width'] * tb['P']
+    cw = (y_hi - y_lo) / TE.CELLS
+    raw = TE.hot_runs(r['hot'])
+    print('comb, tie 1.0: cells hot', int(r['hot'].sum()), 'raw runs', raw, 'intervals',
+          len(r['intervals']), 'wave tiles pruned', int(r['pruned'].sum()), 'of', r['pruned'].size)
+    assert raw > TE.HOT_IV, raw
+    assert len(r['intervals']) == TE.HOT_IV
+    c = np.flatnonzero(r['hot']).astype(np.float64)
+    mid = y_lo + cw * (c + 0.5)
+    lo, hi = y_lo + cw * c, y_lo + cw * (c + 1.0)
+    cov = np.zeros(c.size, dtype=bool)
+    for a, b in r['intervals']:
+        cov |= (a <= lo) & (hi <= b) & (a < mid) & (mid < b)
+    assert cov.all(), c[~cov]
+    hot = ~(r['wmax'] < r['thr'])
+    assert r['pruned'].any() and not (r['pruned'] & hot).any()
+    # and the default window leaves one run
+    iv, hot_cells = TE.hot_intervals(r['U'], r['L0'], y_lo, y_hi)
+    assert TE.hot_runs(hot_cells) == 1 and len(iv) == 1
 
 
 def test_interval_merge_keeps_a_superset():

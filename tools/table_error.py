@@ -18,7 +18,9 @@ their certificate).  Prints one line per (hp, side) and exits 0.
 pass's prefilter (bound lattice, hot intervals, bucketed wave tiles) on
 --draws draws of the below mixture: cells hot, wave tiles passing, hot wave
 tiles missed (which must be 0).  --low-edge takes a history whose good trials
-cluster at the lower bound instead of the test shape.
+cluster at the lower bound instead of the test shape; --shape NAME another of
+the named histories (NAMED: high-edge, band, ties, comb), which the CPU and
+the GPU tests of the prefilter share.
 """
 import argparse
 import math
@@ -46,10 +48,12 @@ def _lse2(t, axis=-1):
     return np.squeeze(m, axis) + np.log2(np.sum(np.exp2(t - m), axis=axis))
 
 
-def terms(w, mu, sigma, center):
-    """(cc, a2, mu') of the log2-domain terms t_k = cc - a2 (y' - mu')^2."""
+def terms(w, mu, sigma, center, pacc=1.0):
+    """(cc, a2, mu') of the log2-domain terms t_k = cc - a2 (y' - mu')^2.
+    pacc: the truncation mass make_coef folds into a GMM's constants (an
+    LGMM's carry none: 1)."""
     sp = np.maximum(sigma, 1e-12)
-    cc = L2E * (np.log(w) - np.log(sp * math.sqrt(2.0 * math.pi)))
+    cc = L2E * (np.log(w) - np.log(sp * math.sqrt(2.0 * math.pi)) - math.log(pacc))
     return cc, 0.5 * L2E / (sp * sp), mu - center
 
 
@@ -57,10 +61,10 @@ def log2_g(y, cc, a2, m):
     return _lse2(cc[None, :] - a2[None, :] * (y[:, None] - m[None, :]) ** 2)
 
 
-def build(w, mu, sigma, low, high, center):
+def build(w, mu, sigma, low, high, center, pacc=1.0):
     """Panels of one mixture: dict(P, y_lo, width, M[P], coef[P, 16],
     log2_err[P], log2_glb[P], ok[P]) or None when it takes no table."""
-    cc, a2, m = terms(w, mu, sigma, center)
+    cc, a2, m = terms(w, mu, sigma, center, pacc)
     y_lo, y_hi = low - center, high - center
     sig = math.sqrt(0.5 * L2E / a2.max())
     Pd = math.ceil((y_hi - y_lo) / (2.0 * sig))
@@ -234,6 +238,15 @@ def hot_intervals(U, L0, y_lo, y_hi, tie=TIE):
             for a, b in runs], hot
 
 
+def hot_runs(hot):
+    """The pilot's runs before it merges any: runs of the hot cell mask after
+    each is widened by one cell on both sides and touching ones are joined."""
+    d = hot.copy()
+    d[:-1] |= hot[1:]
+    d[1:] |= hot[:-1]
+    return int((np.diff(np.concatenate([[0], d.astype(np.int8)])) == 1).sum())
+
+
 def draw_below(w, mu, sigma, low, high, center, n, rs):
     """n draws of the truncated mixture, as y' (rejection, numpy's stream)."""
     out = np.empty(0)
@@ -281,6 +294,12 @@ def prefilter(tb, ta, y, tie=TIE, cells=CELLS):
                 thr=tab_max - tie * max(1.0, abs(tab_max)))
 
 
+def pacc_of(family, w, mu, sigma, low, high):
+    """The truncation mass in a side's table constants: a GMM's p_accept
+    (make_coef), 1 for an LGMM (its lpdf applies none)."""
+    return float(O._truncation_mass(w, mu, sigma, low, high)) if family == 'gmm' else 1.0
+
+
 def mixtures(losses, cols, label, dist, args):
     """Both sides' (w, mu, sigma) of one hp, and (low, high, centre)."""
     tids = np.arange(losses.size)
@@ -295,7 +314,8 @@ def certified_pair(losses, cols, label, dist, args):
     """(tb, ta, below mixture, (low, high, centre)) of an hp whose two tables
     are certified, else None."""
     fit, (low, high, pm) = mixtures(losses, cols, label, dist, args)
-    tabs = [build(w, mu, sg, low, high, pm) for w, mu, sg in fit]
+    fam = O.posterior_spec(dist, args, 1.0)[0]
+    tabs = [build(w, mu, sg, low, high, pm, pacc_of(fam, w, mu, sg, low, high)) for w, mu, sg in fit]
     if any(t is None or not t['ok'].all() for t in tabs):
         return None
     return tabs[0], tabs[1], fit[0], (low, high, pm)
@@ -308,6 +328,52 @@ def low_edge_shape(n=6000):
     v = rs.uniform(-5, 5, n)
     losses = (v + 5.0) / 10.0 + 0.05 * rs.rand(n)
     return losses, {'e': v}, {'e': ('uniform', (-5.0, 5.0))}
+
+
+def high_edge_shape(n=6000):
+    """The mirror of low_edge_shape: the EI maximum sits at `high`."""
+    rs = np.random.RandomState(31)
+    v = rs.uniform(-5, 5, n)
+    losses = (5.0 - v) / 10.0 + 0.05 * rs.rand(n)
+    return losses, {'e': v}, {'e': ('uniform', (-5.0, 5.0))}
+
+
+def band_shape(n=6000):
+    """99 % of the trials in a band a quarter unit wide, the good ones at its
+    low end: narrow components beside wide ones, the certified error closest
+    to the bar of the named histories (above: 3.1e-9 against 3.7e-9; both
+    tables stay certified -- with the mask drawn after v one panel does not)."""
+    rs = np.random.RandomState(1)
+    mask = rs.rand(n) < 0.01
+    v = rs.uniform(-5, 5, n)
+    w = np.where(mask, v, 0.25 + 0.25 * rs.rand(n))
+    losses = np.abs(w - 0.3) + 0.01 * rs.rand(n)
+    return losses, {'e': w}, {'e': ('uniform', (-5.0, 5.0))}
+
+
+def ties_shape(n=6000):
+    """Values rounded to the half unit and clipped to [-5, 4.5], random
+    losses: a panel of the above table is not certified (no lattice)."""
+    rs = np.random.RandomState(2)
+    v = np.clip(np.round(rs.uniform(-5, 5, n) * 2.0) / 2.0, -5.0, 4.5)
+    losses = rs.rand(n)
+    return losses, {'e': v}, {'e': ('uniform', (-5.0, 5.0))}
+
+
+def comb_shape(n=6000, gap=0.28, period=0.7, seed=3):
+    """A comb: no trial in the first `gap` of every `period`, random losses.
+    Both tables are certified and the score has a local maximum per tooth, so
+    a wide tie window leaves more hot runs than HOT_IV."""
+    rs = np.random.RandomState(seed)
+    v = rs.uniform(-5, 5, 4 * n)
+    v = v[np.mod(v + 5.0, period) > gap][:n]
+    assert v.size == n
+    losses = rs.rand(n)
+    return losses, {'e': v}, {'e': ('uniform', (-5.0, 5.0))}
+
+
+NAMED = {'low-edge': low_edge_shape, 'high-edge': high_edge_shape, 'band': band_shape,
+         'ties': ties_shape, 'comb': comb_shape}
 
 
 def report_prefilter(losses, cols, specs, every=1, draws=1 << 18):
@@ -331,7 +397,7 @@ def report_prefilter(losses, cols, specs, every=1, draws=1 << 18):
 
 
 def report(label, side, w, mu, sigma, low, high, center, rs, pts=200):
-    tab = build(w, mu, sigma, low, high, center)
+    tab = build(w, mu, sigma, low, high, center)   # (pacc 1: a constant factor of g)
     if tab is None:
         print('%-4s %-5s K=%-5d no table (panel count out of range)' % (label, side, w.size))
         return None
@@ -394,6 +460,7 @@ def main():
     ap.add_argument('--every', type=int, default=1, help='every n-th hp')
     ap.add_argument('--prefilter', action='store_true', help='report the prefilter emulation')
     ap.add_argument('--low-edge', action='store_true', help='good trials clustered at low')
+    ap.add_argument('--shape', choices=sorted(NAMED), help='another named history')
     ap.add_argument('--draws', type=int, default=1 << 18, help='--prefilter: draws per hp')
     a = ap.parse_args()
     if a.cfg4:
@@ -402,8 +469,8 @@ def main():
         dom, losses, vals, act = bench.build_workload('cfg4')
         cols = {h.label: vals[h.index] for h in dom.space.hps}
         specs = {h.label: ('uniform', (-5.0, 5.0)) for h in dom.space.hps}
-    elif a.low_edge:
-        losses, cols, specs = low_edge_shape(a.n)
+    elif a.low_edge or a.shape:
+        losses, cols, specs = NAMED[a.shape or 'low-edge'](a.n)
     else:
         gap = None
         if a.gap:
