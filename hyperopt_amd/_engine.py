@@ -44,6 +44,7 @@ EXPORTS = (
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
     'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
     'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
+    'tpe_plan_cand_dump',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -164,6 +165,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_tab_wmax': (C.c_int, [vp, i32, vp]),
             'tpe_plan_tab_bound': (C.c_int, [vp, i32, vp]),
             'tpe_plan_tab_hot': (C.c_int, [vp, i32, vp]),
+            'tpe_plan_cand_dump': (C.c_int64, [vp, i32, i32, vp, vp]),
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
             'tpe_plan_set_prune': (C.c_int, [vp, i32]),
             'tpe_plan_sample_prior': (C.c_int, [vp, C.POINTER(u64), i64, vp, i32, vp]),
@@ -683,6 +685,21 @@ class Plan(object):
         with e.lock:
             e.check(e.lib.tpe_plan_tab_hot(self.p, int(n_suggest), out.ctypes.data))
         return out
+
+    def cand_dump(self, s, hp):
+        """Debug (tpe_plan_cand_dump): (values float64 [n], positions int32
+        [n]) of one (suggestion, hp) as the last sorted draw left them.  Wave
+        tiles the pruning draw dropped (-inf in tab_wmax; TPE_DRAW_PRUNE=0:
+        none) were never written: their entries are unspecified."""
+        e = self.engine
+        with e.lock:
+            n = e.lib.tpe_plan_cand_dump(self.p, int(s), int(hp), None, None)
+            e.check(int(min(n, 0)))
+            vals = np.empty(n, dtype=np.float64)
+            pos = np.empty(n, dtype=np.int32)
+            e.check(int(min(e.lib.tpe_plan_cand_dump(self.p, int(s), int(hp), vals.ctypes.data,
+                                                     pos.ctypes.data), 0)))
+        return vals, pos
 
     def last_stats(self):
         e = self.engine

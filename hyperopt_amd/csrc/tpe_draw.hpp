@@ -421,6 +421,13 @@ __device__ __forceinline__ int row_slot(const ScoreArgs &A, int s, int s0, int n
   return A.compact ? active_slot(A, s, s0, n, row) : s0 + row;
 }
 
+// the lpdf kind of a level slot (its group's)
+__device__ __forceinline__ int slot_kind(const ScoreArgs &A, int slot) {
+  for (int g = 0; g < A.n_groups; ++g)
+    if (slot >= A.grp_slot0[g] && slot < A.grp_slot0[g] + A.grp_slots[g]) return A.grp_kind[g];
+  return -1;
+}
+
 // One draw block (k_draw<true>, or a draw row of the fused k_lattice): the
 // below mixture's table of (suggestion s, level slot) in LDS, then a
 // grid-stride pass over the chunk's candidates bx * blockDim + t (+ stride).
@@ -756,6 +763,204 @@ __device__ __forceinline__ void sorted_block_body(const ScoreArgs &A, int slot, 
       po[p] = (int32_t)(base + i);
     });
   }
+}
+
+// ------------------------------------------------------------------------
+// The pruning sorted draw (k_draw_sorted_prune): the fast
+// path of sorted_block_body with a different tail, for the sort blocks behind
+// the pilot's of a tab_on 1 launch with the prefilter.  The draws, the key
+// range, the bucket bytes and the per-(wave, bucket) bases are those of
+// sorted_block_body.  Then, for a slot with two certified tables whose hot
+// intervals (TabHot, k_table_pilot) are not "everything":
+//  - a bucket is hot when one of its elements' y' -- the map's own
+//    expression, clamped as tab_prefilter clamps it; a NaN counts -- lies in
+//    a hot interval;
+//  - a wave tile (128 positions) is kept iff it meets the position range of
+//    a non-empty hot bucket: a superset of the tiles that hold an element
+//    inside a hot interval, which is all soundness needs (a dropped tile's
+//    candidates all lie in cells with U < T0);
+//  - a bucket is live iff its position range meets a kept tile; only the
+//    live elements are ranked (each wave compacts its own in index order, so
+//    bases plus in-row ranks give sorted_block_body's destinations) and only
+//    destinations inside kept tiles are written, values and positions;
+//  - tab_wmax gets -inf for a dropped tile and +inf ("pending": no score is
+//    +inf, the map replaces it) for a kept one.
+// Any other slot is written in full, as sorted_block_body writes it.
+// ------------------------------------------------------------------------
+typedef const double __attribute__((address_space(4))) DrawKDbl;
+constexpr int kPruneRing = 128;  // a wave's pending live elements (a ring; drained by 64)
+
+template <int CAP, int NT>
+struct PruneDrawLds {
+  SortedDrawLds<CAP, NT> S;
+  unsigned char hotb[kSortBuckets];   // the bucket holds an element of a hot interval
+  unsigned char liveb[kSortBuckets];  // the bucket meets a kept tile
+  unsigned long long keep;            // the block's kept wave tiles (bit t: positions 128 t ..)
+  uint16_t ring[NT / 64][kPruneRing];
+};
+
+// bits t0 .. t1 (0 <= t0 <= t1 <= 63)
+__device__ __forceinline__ unsigned long long tile_bits(int t0, int t1) {
+  return (~0ull >> (63 - t1)) & (~0ull << t0);
+}
+
+// tabk: the slot is a two-row wave-tile log-sum-exp slot (the kinds the table
+// pass takes).  FAST: as sorted_block_body's -- without it the slots that are
+// not bounded continuous ones with a table draw out of line (they take no
+// table, so they are written in full).  Every thread of the block calls it.
+template <int CAP, int NT, bool FAST>
+__device__ __forceinline__ void sorted_block_prune_body(const ScoreArgs &A, int slot, int s,
+                                                        int64_t base, bool bucket, bool lg,
+                                                        bool tabk, int32_t *__restrict__ pos_out,
+                                                        PruneDrawLds<CAP, NT> &P) {
+  constexpr int NW = NT / 64;
+  static_assert(kSortedBlock / 128 == 64, "a sort block's wave tiles: one 64-bit mask");
+  SortedDrawLds<CAP, NT> &L = P.S;
+  const int hp = A.level_hps[slot];
+  const tpe_hp H = A.hps[hp];
+  const int64_t sb = 2 * (int64_t)hp;
+  const double *bw = A.mw + sb * A.kcap, *bmu = A.mmu + sb * A.kcap, *bsg = A.msig + sb * A.kcap;
+  const int K = A.info[sb].K;
+  const bool tab = K >= 1 && K <= CAP;
+  if (tab) build_table(H, K, bw, bmu, bsg, L.T);
+  const uint64_t seed = suggestion_seed(A, s);
+  const int n = (int)min<int64_t>((int64_t)1 << A.sort_log2, A.n_cand - base);
+  const int64_t off = (int64_t)s * A.cand_sstride + (int64_t)slot * A.n_cand + base;
+  double *out = const_cast<double *>(A.cand) + off;
+  const int t = threadIdx.x;
+  double lo = INFINITY, hi = -INFINITY;
+  auto emit = [&](int i, double x) {
+    if (!bucket) {
+      out[i] = x;
+      return;
+    }
+    L.xs[i] = x;
+    const double key = sort_key(x, lg);
+    if (fabs(key) < INFINITY) { lo = fmin(lo, key); hi = fmax(hi, key); }
+  };
+  const bool fast = FAST || (tab && H.family != TPE_CAT && (H.flags & TPE_HAS_LOW) &&
+                             (H.flags & TPE_HAS_HIGH));
+  if (fast) {
+    const double cdf_last = L.T.cdf[K - 1];
+    const double high_prev = nextafter(H.high, -INFINITY);
+    const bool logn = H.family == TPE_LGMM, hasq = (H.flags & TPE_HAS_Q) != 0;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll 1
+    for (int i = t; i < n; i += NT) {
+      const uint64_t gi = (uint64_t)(A.cand_begin + base + i);
+      const U4 r0 = philox(U4{(uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)hp, 0u}, k0, k1);
+      emit(i, draw_bounded_inline<CAP>(L.T, K, cdf_last, bmu, bsg, H.low, H.high, high_prev,
+                                       logn, hasq, H.q, r0));
+    }
+  } else if constexpr (!FAST) {
+#pragma unroll 1
+    for (int i = t; i < n; i += NT) {
+      const uint64_t gi = (uint64_t)(A.cand_begin + base + i);
+      emit(i, tab ? draw_table_ool<CAP>(A.hps + hp, K, bmu, bsg, &L.T,
+                                        draw_block0(seed, gi, (uint32_t)hp), seed, gi, (uint32_t)hp)
+                  : draw_one_ool(A.hps + hp, A.info + sb, bw, bmu, bsg, seed, gi, (uint32_t)hp));
+    }
+  }
+  if (!bucket) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, o, 64));
+    hi = fmax(hi, __shfl_xor(hi, o, 64));
+  }
+  const int lane = t & 63, wv = t >> 6;
+  if (lane == 0) { L.red[0][wv] = lo; L.red[1][wv] = hi; }
+  if (t < kSortBuckets) P.hotb[t] = 0;
+  if (t == 0) P.keep = 0ull;
+  // the slot's hot intervals (block-uniform, scalar loads): prune only a slot
+  // the pilot left a record for -- two certified tables -- that is not
+  // "everything"
+  bool prune = tabk && fast && tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sb + 1]);
+  const uint64_t ub = (uint64_t)(A.tab_hot + ((int64_t)s * A.n_hp + hp));
+  DrawKDbl *__restrict__ hot = (DrawKDbl *)(
+      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32)) << 32) |
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub));
+  double y_lo = 0.0, y_hi = 0.0;
+  int nh = 0;  // intervals in use (they come first)
+  if (prune) {
+    y_lo = hot[0];
+    y_hi = hot[1];
+    while (nh < kHotIv && hot[2 + nh] <= hot[2 + kHotIv + nh]) ++nh;
+    prune = !(nh > 0 && hot[2] == -INFINITY && hot[2 + kHotIv] == INFINITY);
+  }
+  __syncthreads();
+  lo = INFINITY; hi = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) { lo = fmin(lo, L.red[0][w]); hi = fmax(hi, L.red[1][w]); }
+  const double scale = hi > lo ? (double)kSortBuckets / (hi - lo) : 0.0;
+  const double mu = H.prior_mu;
+  for (int i = t; i < n; i += NT) {
+    const double x = L.xs[i];
+    const double key = sort_key(x, lg);
+    int b = kSortBuckets - 1;
+    if (fabs(key) < INFINITY) b = min(kSortBuckets - 1, max(0, (int)((key - lo) * scale)));
+    L.bk[i] = (unsigned char)b;
+    if (prune) {
+      const double y = (lg ? fast_log(x) : x) - mu;
+      const double yc = fmin(fmax(y, y_lo), y_hi);
+      bool hit = y != y;
+#pragma unroll
+      for (int j = 0; j < kHotIv; ++j) {
+        if (j >= nh) break;
+        hit |= yc >= hot[2 + j] && yc <= hot[2 + kHotIv + j];
+      }
+      if (hit) P.hotb[b] = 1;
+    }
+  }
+  __syncthreads();
+  int32_t *po = pos_out + off;
+  double *__restrict__ wm = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * 8 + (base >> 7);
+  const int ntile = (n + 127) >> 7;  // the block's wave tiles that hold candidates
+  if (!prune) {
+    stable_bucket_permute<NW, kSortedBlock / NT>(L.bk, n, L.cnt, L.xs, out, po, base);
+    if (tabk && t < ntile) wm[t] = INFINITY;
+    return;
+  }
+  int r0, r1;
+  bucket_bases<NW>(L.bk, n, L.cnt, r0, r1);
+  // bucket t's position range [bb, be): wave 0's base of it and of the next
+  int bb = 0, be = 0;
+  if (t < kSortBuckets) {
+    bb = (int)((L.cnt[t >> 1] >> ((t & 1) * 16)) & 0xffffu);
+    be = t == kSortBuckets - 1 ? n : (int)((L.cnt[(t + 1) >> 1] >> (((t + 1) & 1) * 16)) & 0xffffu);
+    if (be > bb && P.hotb[t]) atomicOr(&P.keep, tile_bits(bb >> 7, (be - 1) >> 7));
+  }
+  __syncthreads();
+  const unsigned long long keep = P.keep;
+  if (t < kSortBuckets)
+    P.liveb[t] = (be > bb && (keep & tile_bits(bb >> 7, (be - 1) >> 7)) != 0ull) ? 1 : 0;
+  if (t < ntile) wm[t] = ((keep >> t) & 1ull) ? INFINITY : -INFINITY;
+  __syncthreads();
+  // the wave's live elements in index order, ranked a compacted row at a time
+  uint16_t *ring = P.ring[wv];
+  uint32_t *mine = L.cnt + wv * (kSortBuckets / 2);
+  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  int head = 0, pend = 0;  // (wave-uniform)
+  auto drain = [&](int m) {
+    const bool v = lane < m;
+    const int i = v ? (int)ring[(head + lane) & (kPruneRing - 1)] : 0;
+    const uint32_t d = v ? L.bk[i] : 0u;
+    const int p = bucket_rank(mine, d, v);
+    if (v && ((keep >> (p >> 7)) & 1ull)) {
+      out[p] = L.xs[i];
+      po[p] = (int32_t)(base + i);
+    }
+    head = (head + m) & (kPruneRing - 1);
+    pend -= m;
+  };
+  for (int rb = r0; rb < r1; rb += 64) {
+    const int i = rb + lane;
+    const bool lv = i < r1 && P.liveb[L.bk[i]] != 0;
+    const uint64_t bal = __ballot(lv);
+    if (lv) ring[(head + pend + __popcll(bal & below)) & (kPruneRing - 1)] = (uint16_t)i;
+    pend += __popcll(bal);
+    if (pend >= 64) drain(64);
+  }
+  if (pend > 0) drain(pend);
 }
 
 }  // namespace tpe

@@ -109,6 +109,7 @@ static bool moment_on();
 static bool table_on();
 static double table_tie();
 static bool table_prefilter_on();
+static bool draw_prune_on();
 // TPE_MOMENT_H=0: 16-wide plans without the degree-15 chunk table (A/B)
 static bool moment_h_on() {
   static const bool on = [] {
@@ -220,6 +221,9 @@ struct tpe_plan {
                      // an event record costs a ~6 us pipeline drain between launches)
   int64_t last_ncand = 0, last_nsug = 0;
   int32_t last_level = -1;
+  // the last sorted draw's layout in d_cand / d_cpos (tpe_plan_cand_dump)
+  int64_t dump_cn = 0, dump_sstride = 0, dump_nsug = 0;
+  int32_t dump_level = -1;
   // fit + suggest captured as one hipGraph (tpe_plan_fit_suggest): replayed
   // with the history length / n_below of the fit node and the seeds of the
   // draw nodes patched per call
@@ -235,10 +239,12 @@ struct tpe_plan {
                          // the history: a replay must not keep the captured width)
     bool tab = false;    // the step builds and scores from the Chebyshev tables
     bool pref = false;   // ... behind the prefilter (k_table_pilot is a node of the step)
+    bool dprune = false; // ... with the pruning draw (k_draw_sorted_prune, the pilot ahead of it)
     bool operator==(const StepKey &o) const {
       return prior_weight == o.prior_weight && lf == o.lf && n_sug == o.n_sug &&
              n_cand == o.n_cand && stream == o.stream && table == o.table && fuse == o.fuse &&
-             small == o.small && mom_w == o.mom_w && tab == o.tab && pref == o.pref;
+             small == o.small && mom_w == o.mom_w && tab == o.tab && pref == o.pref &&
+             dprune == o.dprune;
     }
   };
   StepKey graph_key, pending_key;
@@ -1199,8 +1205,31 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
         fast = lookup ? (a.lookup_draw != 0 && kmax <= kFuseTab)
                       : (x.family != TPE_CAT && (x.flags & TPE_HAS_LOW) && (x.flags & TPE_HAS_HIGH));
       }
-      const hipError_t e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+      // The pruning draw: behind the prefilter the hot intervals
+      // depend on the launch's first sort block alone, so that block is drawn
+      // first (today's kernel, written in full), k_table_pilot reads it -- the
+      // tables and bound lattices built ahead of it -- and the other sort
+      // blocks are drawn by the kernel that drops the wave tiles the intervals
+      // rule out.  A chunk of one sort block has nothing to prune.
+      const bool dprune = a.tab_on == 1 && a.tab_pref && (cls & 1) && draw_prune_on() &&
+                          a.sort_log2 == kSortLog2Large && cn > kSortedBlock;
+      hipError_t e;
+      if (dprune) {
+        rc = table_build(h, p, st);
+        if (rc) { join_lk(); return rc; }
+        p->tab_pstride = a.pstride;
+        e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st, 1);
+        if (e == hipSuccess) e = launch_table_pilot(a, st);
+        if (e == hipSuccess) e = launch_draw_pruned(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+        a.tab_pref = 2;
+      } else {
+        e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+      }
       if (e != hipSuccess) { join_lk(); return fail(h, TPE_E_HIP, hipGetErrorString(e)); }
+      p->dump_cn = cn;
+      p->dump_sstride = a.cand_sstride;
+      p->dump_level = level;
+      p->dump_nsug = n_sug;
     } else {
       CKH(launch_draw(a, table_draw, st));
     }
@@ -2007,6 +2036,7 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
     key.mom_w = sorted && n_cand > kWaveRowSplitMax ? mom_width(p) : 0;
     key.tab = key.mom_w == 16 && p->prune_mode == 3 && table_on();
     key.pref = key.tab && table_prefilter_on();
+    key.dprune = key.pref && draw_prune_on();
   }
   int rc = ensure_suggest_state(h, p, n_sug, 1);
   if (rc) return rc;
@@ -2269,6 +2299,28 @@ int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out) {
   return TPE_OK;
 }
 
+int64_t tpe_plan_cand_dump(tpe_plan_t p, int32_t s, int32_t hp, double *values, int32_t *positions) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->dump_level < 0 || p->dump_cn <= 0) return fail(h, TPE_E_INVALID, "no sorted draw yet");
+  if (!values && !positions) return p->dump_cn;
+  const std::vector<int32_t> &lv = p->levels[p->dump_level];
+  int64_t slot = -1;
+  for (size_t i = 0; i < lv.size(); ++i)
+    if (lv[i] == hp) slot = (int64_t)i;
+  if (slot < 0 || s < 0 || s >= p->dump_nsug)
+    return fail(h, TPE_E_INVALID, "hp / suggestion not of the last sorted draw");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const int64_t off = (int64_t)s * p->dump_sstride + slot * p->dump_cn;
+  if (values)
+    CKH(hipMemcpy(values, p->d_cand + off, (size_t)p->dump_cn * sizeof(double), hipMemcpyDeviceToHost));
+  if (positions)
+    CKH(hipMemcpy(positions, p->d_cpos + off, (size_t)p->dump_cn * sizeof(int32_t),
+                  hipMemcpyDeviceToHost));
+  return p->dump_cn;
+}
+
 int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out) {
   if (!p) return TPE_E_INVALID;
   if (!out) return kBndCells;
@@ -2510,6 +2562,18 @@ static double table_tie() {
 // the table score rules out are not scored (k_table_bound / k_table_pilot;
 // TPE_TABLE_PREFILTER=0 switches it off: same-binary A/B and the tests' child
 // processes)
+// the sorted draw behind the prefilter drops the wave tiles the hot intervals
+// rule out before ranking or writing them (k_draw_sorted_prune;
+// TPE_DRAW_PRUNE=0 restores the full draw: same-binary A/B and the tests'
+// child processes)
+static bool draw_prune_on() {
+  static const bool v = [] {
+    const char *e = std::getenv("TPE_DRAW_PRUNE");
+    return !(e && *e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+
 static bool table_prefilter_on() {
   static const bool v = [] {
     const char *e = std::getenv("TPE_TABLE_PREFILTER");

@@ -408,7 +408,9 @@ struct ScoreArgs {
   // pass stores -inf for a wave tile whose candidates meet none of them
   const double *tab_bound;   // [P][kBndCells] bound lattices (k_table_bound)
   TabHot *tab_hot;           // [S][P] hot intervals of this launch
-  int32_t tab_pref;
+  int32_t tab_pref;          // 2: the pilot has run and the draw has marked tab_wmax (-inf: a
+                             // dropped wave tile, never written -- the table pass and the
+                             // gather leave it alone; TPE_DRAW_PRUNE=0: never 2)
   // a tile_draw launch that ends its call (pub_flag non-null): the last of its
   // pub_events final records copies all pub_words words of results into the
   // pinned pub_dst and then stores pub_seq into *pub_flag -- k_publish's
@@ -460,6 +462,7 @@ bool fit_small(int64_t n);                 // k_fit<true> (all-LDS variant) serv
 const void *fit_kernel_fn(bool small);     // k_fit's host stub (graph node lookup)
 bool is_draw_kernel_fn(const void *f);     // one of k_draw's / k_draw_sorted's host stubs
 bool is_sorted_draw_kernel_fn(const void *f);
+bool is_prune_draw_kernel_fn(const void *f);  // k_draw_sorted_prune's (tpe_prune.hip)
 const void *lattice_draw_kernel_fn();      // k_lattice<true> (lattice + fused draw)
 hipError_t launch_prep(const tpe_hp *hps, int32_t n_hp, const double *mw,
                        const double *mmu, const double *msig, MixInfo *info,
@@ -532,8 +535,20 @@ __host__ __device__ constexpr int sort_log2_for(int64_t n_total) {
 // fast: every slot the launch draws is a bounded continuous one (low and
 // high) whose below mixture fits the table, the rest lookup slots their tiles
 // draw (lookup_draw) -- the kernel without the out-of-line draws
+// max_blocks: only the launch's first sort blocks (the pilot's, ahead of
+// launch_draw_pruned)
 hipError_t launch_draw_sorted(const ScoreArgs &a, bool small_table, bool fast, int32_t *pos_out,
+                              hipStream_t st, int64_t max_blocks = INT64_MAX);
+// The sort blocks behind the first of a tab_on 1 launch with the prefilter,
+// once k_table_pilot has left this launch's hot intervals: the fast draw that
+// neither ranks nor writes the wave tiles they rule out and leaves -inf
+// (dropped) / +inf (pending) in tab_wmax (k_draw_sorted_prune).  The launch's
+// table pass then runs with tab_pref 2.  8192-candidate sort blocks only.
+hipError_t launch_draw_pruned(const ScoreArgs &a, bool small_table, bool fast, int32_t *pos_out,
                               hipStream_t st);
+// k_table_pilot of the launch's wave-tile class on its own, for the draw that
+// needs the hot intervals (launch_score with tab_pref 2 does not launch it)
+hipError_t launch_table_pilot(const ScoreArgs &a, hipStream_t st);
 static_assert(kSortedBlock == TPE_SHARD_ALIGN, "shard alignment is the sorted-draw block");
 // given candidates src[slot][n_cand] (one suggestion) bucketed exactly as
 // k_draw_sorted buckets its draws (tpe_plan_score_candidates_sorted)

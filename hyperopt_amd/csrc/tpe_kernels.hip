@@ -56,12 +56,6 @@ __global__ __launch_bounds__(kDrawThreads) void k_draw(ScoreArgs A) {
   }
 }
 
-__device__ __forceinline__ int slot_kind(const ScoreArgs &A, int slot) {
-  for (int g = 0; g < A.n_groups; ++g)
-    if (slot >= A.grp_slot0[g] && slot < A.grp_slot0[g] + A.grp_slots[g]) return A.grp_kind[g];
-  return -1;
-}
-
 template <int CAP, int NT, bool EXT, bool FAST = false>
 __device__ __forceinline__ void sorted_block(const ScoreArgs &A, int32_t *__restrict__ pos_out,
                                              const double *__restrict__ src,
@@ -681,7 +675,8 @@ bool is_sorted_draw_kernel_fn(const void *f) {
          f == reinterpret_cast<const void *>(&k_draw_sorted_wide<kFuseTab>) ||
          f == reinterpret_cast<const void *>(&k_draw_sorted_wide<kTabCap>) ||
          f == reinterpret_cast<const void *>(&k_draw_sorted_wide_fast<kFuseTab>) ||
-         f == reinterpret_cast<const void *>(&k_draw_sorted_wide_fast<kTabCap>);
+         f == reinterpret_cast<const void *>(&k_draw_sorted_wide_fast<kTabCap>) ||
+         is_prune_draw_kernel_fn(f);
 }
 
 hipError_t launch_draw(const ScoreArgs &a, bool table, hipStream_t st) {
@@ -697,10 +692,10 @@ hipError_t launch_draw(const ScoreArgs &a, bool table, hipStream_t st) {
 }
 
 hipError_t launch_draw_sorted(const ScoreArgs &a, bool small_table, bool fast, int32_t *pos_out,
-                              hipStream_t st) {
+                              hipStream_t st, int64_t max_blocks) {
   if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= 0) return hipSuccess;
   const int64_t sbk = (int64_t)1 << a.sort_log2;
-  const unsigned gx = (unsigned)((a.n_cand + sbk - 1) / sbk);
+  const unsigned gx = (unsigned)std::min<int64_t>((a.n_cand + sbk - 1) / sbk, max_blocks);
   const dim3 g(gx, (unsigned)a.slot_rows, a.n_suggest);
   // fewer blocks than ~2 per CU: 1024-thread blocks (a 256-thread block is 1
   // wave per SIMD; the launch is then bound by one block's latency)

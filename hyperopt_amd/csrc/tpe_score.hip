@@ -1937,6 +1937,23 @@ __device__ __forceinline__ void score_tile(const ScoreArgs &A, SM &sm, int slot,
     const int nbs = min(SBB, ntiles - sb * SBB);
     wt0 = ((int64_t)sb * SBB * kWaves + q + (int64_t)nbs * wvs) * 64 * KR;
   }
+  if constexpr (TMAP) {
+    // a wave tile the draw dropped (tab_pref 2: -inf in tab_wmax ahead of the
+    // table pass): its candidates were never written -- nothing is read, the
+    // entry stays; its pairs are credited as a prefiltered tile's are
+    if (A.tab_pref == 2 && wt0 < A.n_cand &&
+        A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * kWaves + wt0 / (64 * KR)] == -INFINITY) {
+      if constexpr (CENSUS) {
+        if (lane == 0) {
+          const unsigned long long c = (unsigned long long)min<int64_t>(64 * KR, A.n_cand - wt0) *
+                                       (unsigned long long)(ib.K + ia.K);
+          atomicAdd(A.census + 3, c);
+          atomicAdd(A.census + 12, c);
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int r = 0; r < KR; ++r) {
     li[r] = wt0 + r * 64 + lane;
@@ -2943,6 +2960,88 @@ __global__ __launch_bounds__(kWaves * 64) void k_table_map(ScoreArgs A) {
   }
 }
 
+// The map behind the pruning draw (tab_pref 2; k_draw_sorted_prune has left
+// -inf in tab_wmax for the wave tiles it dropped and +inf for the others): a
+// block per kMapDpTiles = 512 wave tiles (eight sort blocks) of its slot, every
+// kWaves-th of them per wave -- one entry per lane, read in one load
+// instruction (a wave is mostly its set-up: the fewer the better).
+// A -inf entry of a tile that holds candidates stays as it is and nothing of
+// the tile is read (its candidates were never written); every other tile runs
+// k_table_map's code, tab_prefilter included, so its entry is that kernel's
+// bits.  The census credits a dropped tile's pairs as a prefiltered one's.
+constexpr int kMapDpTiles = 512;
+__host__ __device__ inline int table_map_dp_blocks(const ScoreArgs &A, int g) {
+  const int rows = (A.grp_block0[g + 1] - A.grp_block0[g]) / A.grp_tiles[g];
+  return rows * ((A.grp_tiles[g] * kWaves + kMapDpTiles - 1) / kMapDpTiles);
+}
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) void k_table_map_dp(ScoreArgs A) {
+  constexpr int KR = kMapRows, PW = kMapDpTiles / kWaves;
+  static_assert(PW == 64, "a wave's tile mask: one entry per lane");
+  const int b = blockIdx.x;
+  int g = 0, b0 = 0;  // the block's group and that group's first block
+  for (; g + 1 < A.n_groups; ++g) {
+    const int nb = table_map_dp_blocks(A, g);
+    if (b < b0 + nb) break;
+    b0 += nb;
+  }
+  const int ntw = A.grp_tiles[g] * kWaves, nsb = (ntw + kMapDpTiles - 1) / kMapDpTiles;
+  const int local = b - b0;
+  int slot = A.grp_slot0[g] + local / nsb;
+  const int s = blockIdx.y;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], local / nsb);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
+  if (!(tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sa]))) return;
+  if (!(A.force_active || A.compact ||
+        hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch)))
+    return;
+  const bool logn = A.grp_kind[g] == KIND_LSE_LW;
+  const double mu = A.hps[hp].prior_mu;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  double *__restrict__ wmax = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * kWaves;
+  // (interleaved: wave w takes the block's tiles w, w + 8, ... -- the kept
+  // tiles of a sort block are neighbours, the positions of its hot buckets,
+  // and consecutive tiles per wave left them all to one wave)
+  const int wt0 = (local % nsb) * kMapDpTiles + wave;
+  // lane j < PW: wave tile wt0 + 8 j -- to run unless the draw dropped it (a
+  // tile wholly past n_cand has no mark: it gets k_table_map's NaN)
+  const int wl = wt0 + kWaves * lane;
+  const bool in = wl < ntw;
+  const bool drop = in && (int64_t)wl * (64 * KR) < A.n_cand && wmax[wl] == -INFINITY;
+  auto uniform64 = [](uint64_t m) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+  };
+  uint64_t todo = uniform64(__ballot(in && !drop));
+  if constexpr (CENSUS) {
+    uint64_t dr = uniform64(__ballot(drop));
+    while (dr) {
+      const int wt = wt0 + kWaves * (int)__builtin_ctzll(dr);
+      dr &= dr - 1;
+      if (lane == 0) {
+        const unsigned long long c =
+            (unsigned long long)min<int64_t>(64 * KR, A.n_cand - (int64_t)wt * (64 * KR)) *
+            (unsigned long long)(A.info[sb].K + A.info[sa].K);
+        atomicAdd(A.census + 3, c);
+        atomicAdd(A.census + 12, c);
+      }
+    }
+  }
+  while (todo) {  // (wave-uniform)
+    const int wt = wt0 + kWaves * (int)__builtin_ctzll(todo);
+    todo &= todo - 1;
+    double x[KR];
+    table_wave_load(A, s, slot, logn, wt, x);
+    const double best = table_wave_tile<CENSUS, true>(A, s, hp, logn, wt, mu, x);
+    if (lane == 0) wmax[wt] = best;
+  }
+}
+
 // Ahead of the table pass of a tab_on 1 launch with the prefilter: one block
 // per (row, suggestion), k_tie_gather's row -> slot mapping; slots that are
 // inactive or without two certified tables need nothing (their map blocks
@@ -3134,10 +3233,13 @@ __global__ __launch_bounds__(kGatherThreads) void k_tie_gather(ScoreArgs A) {
   const double tm = (nan || nrec <= 0) ? NAN : m;
   if (tid == 0) A.tab_max[sh] = tm;
   const double wthr = tm - A.tab_tie * fmax(1.0, fabs(tm));
+  // (tab_pref 2: a wave tile the draw dropped holds nothing -- never listed,
+  // whatever tab_max is; with a finite tab_max -inf < wthr says so already)
+  const bool dp = A.tab_pref == 2;
   int base = 0;  // list entries so far (block-uniform)
   for (int i0 = 0; i0 < ntw; i0 += kGatherThreads) {
     const int i = i0 + tid;
-    const bool hot = i < ntw && !(wm[i] < wthr);
+    const bool hot = i < ntw && !(wm[i] < wthr) && !(dp && i < nrec && wm[i] == -INFINITY);
     const uint64_t bal = __ballot(hot);
     if (lane == 0) wsum[wave] = __popcll(bal);
     __syncthreads();
@@ -3485,11 +3587,18 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
       }
       if (rows <= 0 || rows > 65535 || a.n_suggest > 65535) return hipErrorInvalidValue;
       // the prefilter's hot intervals of this launch, ahead of either map form
-      if (a.tab_pref) {
+      // (tab_pref 2: launch_table_pilot has run it, ahead of the pruning draw)
+      if (a.tab_pref == 1) {
         if (!a.tab_bound || !a.tab_hot) return hipErrorInvalidValue;
         k_table_pilot<<<dim3((unsigned)rows, a.n_suggest), kPilotThreads, 0, st>>>(a);
       }
-      if (table_scalar_on()) {
+      if (table_scalar_on() && a.tab_pref == 2) {
+        int32_t mb = 0;
+        for (int i = 0; i < a.n_groups; ++i) mb += table_map_dp_blocks(a, i);
+        const dim3 gm((unsigned)mb, a.n_suggest);
+        if (a.census) k_table_map_dp<true><<<gm, kWaves * 64, 0, st>>>(a);
+        else k_table_map_dp<false><<<gm, kWaves * 64, 0, st>>>(a);
+      } else if (table_scalar_on()) {
         int32_t mb = 0;
         for (int i = 0; i < a.n_groups; ++i) mb += table_map_blocks(a, i);
         const dim3 gm((unsigned)mb, a.n_suggest);
@@ -3551,6 +3660,17 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
     if (a.census) k_score<false, true><<<g, kWaves * 64, 0, st>>>(a);
     else k_score<false, false><<<g, kWaves * 64, 0, st>>>(a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_table_pilot(const ScoreArgs &a0, hipStream_t st) {
+  const ScoreArgs a = score_classes(a0) == 1 ? a0 : select_groups(a0, 0);
+  if (a.n_groups <= 0 || !a.tab_bound || !a.tab_hot) return hipErrorInvalidValue;
+  int32_t rows = 0;
+  for (int i = 0; i < a.n_groups; ++i)
+    rows += (a.grp_block0[i + 1] - a.grp_block0[i]) / a.grp_tiles[i];
+  if (rows <= 0 || rows > 65535 || a.n_suggest > 65535) return hipErrorInvalidValue;
+  k_table_pilot<<<dim3((unsigned)rows, a.n_suggest), kPilotThreads, 0, st>>>(a);
   return hipGetLastError();
 }
 

@@ -332,7 +332,10 @@ int tpe_plan_tie_counts(tpe_plan_t p, int32_t n_suggest, int32_t *counts);
  * launch that took the tables left it; W = 8 * the launch's tiles per slot
  * holds every wave tile of its candidate count.  Entries of hps without two
  * certified tables, of inactive hps and of wave tiles no such launch has
- * written are unspecified.  out == NULL: returns W (0: no such launch yet)
+ * written are unspecified.  -inf: a wave tile the prefilter ruled out, in
+ * the map or -- unless TPE_DRAW_PRUNE=0 -- already in the sorted draw, which
+ * then neither ranked nor wrote its candidates (tpe_plan_cand_dump).
+ * out == NULL: returns W (0: no such launch yet)
  * and copies nothing.  Synchronizes the device.                              */
 int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out);
 /* Debug: out[c], c < 4096, the bound lattice of hp as the last fit left it:
@@ -352,6 +355,16 @@ int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out);
  * certified tables, of inactive hps and of hps no such launch has scored are
  * unspecified.  Synchronizes the device.                                    */
 int tpe_plan_tab_hot(tpe_plan_t p, int32_t n_suggest, double *out);
+/* Debug: the value-bucketed candidates of (suggestion s, hp) as the plan's
+ * last sorted draw left them in the candidate buffer: values[i] and
+ * positions[i] (the candidate's index within the launch's chunk), i < n, the
+ * launch's candidates per slot.  Either pointer may be NULL; both NULL:
+ * returns n and copies nothing.  Behind the pruning draw (TPE_DRAW_PRUNE, on
+ * by default) the wave tiles it dropped -- -inf in tpe_plan_tab_wmax -- were
+ * never written: their entries are unspecified.  Adds no launch; synchronizes
+ * the device.  Returns n, or a negative status.                             */
+int64_t tpe_plan_cand_dump(tpe_plan_t p, int32_t s, int32_t hp, double *values,
+                           int32_t *positions);
 
 /* Prior draws of n_suggest whole suggestions (rand.suggest, the TPE startup
  * phase: hyperopt/rand.py:14-33, pyll/stochastic.py:30-142): every active hp

@@ -9,6 +9,7 @@ relative error at random points of each panel against the certified bound.
     python tools/table_error.py --gap u:-1.5:1.5
     python tools/table_error.py --cfg4 --every 7
     python tools/table_error.py --prefilter          # and --cfg4 --every 37, --low-edge
+    python tools/table_error.py --drawprune          # and --cfg4 --only 0,42,76, --shape band
 
 --gap LABEL:LO:HI moves the history values of LABEL inside (LO, HI) out of the
 interval (an empty gap: the edge components widen, the panels beside them lose
@@ -21,6 +22,12 @@ tiles missed (which must be 0).  --low-edge takes a history whose good trials
 cluster at the lower bound instead of the test shape; --shape NAME another of
 the named histories (NAMED: high-edge, band, ties, comb), which the CPU and
 the GPU tests of the prefilter share.
+
+--drawprune adds the emulation of the pruning sorted draw (k_draw_sorted_prune,
+DESIGN 5.6) on the same draws and bucketing: per hp the share of the wave
+tiles the draw keeps (beside the exact filter's passing share), the share of
+the elements it ranks, and the hot wave tiles it drops (which must be 0).
+--only I,J,... takes just those hps.
 """
 import argparse
 import math
@@ -294,6 +301,46 @@ def prefilter(tb, ta, y, tie=TIE, cells=CELLS):
                 thr=tab_max - tie * max(1.0, abs(tab_max)))
 
 
+def draw_prune(tb, ta, y, tie=TIE, cells=CELLS):
+    """The pruning draw on the candidates y of one launch (draw order), on top
+    of prefilter(): sort block 0 is the pilot's and kept whole; in every other
+    block a bucket is hot when one of its elements' clamped y' lies in a hot
+    interval (a NaN counts), a wave tile is kept iff its position range meets
+    that of a non-empty hot bucket, and a bucket is live -- its elements are
+    ranked -- iff its position range meets a kept tile.  Adds `kept` per wave
+    tile, `live` (share of the elements behind block 0 that are ranked) and
+    `dropped_hot`, the wave tiles dropped although their best score reaches
+    k_tie_gather's threshold."""
+    r = prefilter(tb, ta, y, tie, cells)
+    y_lo = tb['y_lo']
+    y_hi = y_lo + tb['width'] * tb['P']
+    n = y.size
+    kept = np.ones((n + WAVE - 1) // WAVE, dtype=bool)
+    live = 0
+    for b0 in range(SORT_BLOCK, n, SORT_BLOCK):
+        blk = y[b0:b0 + SORT_BLOCK]
+        key = np.clip(np.floor((blk - y_lo) / (y_hi - y_lo) * BUCKETS), 0, BUCKETS - 1).astype(int)
+        yc = np.clip(blk, y_lo, y_hi)
+        hit = np.isnan(blk)
+        for lo, hi in r['intervals']:
+            hit |= (yc >= lo) & (yc <= hi)
+        cnt = np.bincount(key, minlength=BUCKETS)
+        base = np.cumsum(cnt) - cnt
+        full = cnt > 0
+        t0, t1 = base // WAVE, np.where(full, (base + cnt - 1) // WAVE, base // WAVE)
+        hotb = full & (np.bincount(key[hit], minlength=BUCKETS) > 0)
+        keep = np.zeros((blk.size + WAVE - 1) // WAVE, dtype=bool)
+        for b in np.flatnonzero(hotb):
+            keep[t0[b]:t1[b] + 1] = True
+        ck = np.concatenate([[0], np.cumsum(keep)])
+        liveb = full & (ck[np.minimum(t1 + 1, keep.size)] - ck[np.minimum(t0, keep.size)] > 0)
+        live += int(cnt[liveb].sum())
+        kept[b0 // WAVE:b0 // WAVE + keep.size] = keep
+    hot_tiles = ~(r['wmax'] < r['thr'])
+    return dict(r, kept=kept, live=live / max(1, n - min(n, SORT_BLOCK)),
+                dropped_hot=int((hot_tiles & ~kept).sum()))
+
+
 def pacc_of(family, w, mu, sigma, low, high):
     """The truncation mass in a side's table constants: a GMM's p_accept
     (make_coef), 1 for an LGMM (its lpdf applies none)."""
@@ -396,6 +443,27 @@ def report_prefilter(losses, cols, specs, every=1, draws=1 << 18):
         assert missed == 0, 'a hot wave tile was pruned'
 
 
+def report_drawprune(losses, cols, specs, every=1, draws=1 << 18, only=None):
+    rs = np.random.RandomState(7)
+    out = {}
+    for i, (label, (dist, args)) in enumerate(specs.items()):
+        if (i % every) if only is None else (i not in only):
+            continue
+        pair = certified_pair(losses, cols, label, dist, args)
+        if pair is None:
+            print('%-4s drawprune: no certified pair, every wave tile written' % label)
+            continue
+        tb, ta, (w, mu, sg), (low, high, pm) = pair
+        r = draw_prune(tb, ta, draw_below(w, mu, sg, low, high, pm, draws, rs))
+        out[label] = r
+        print('%-4s drawprune: wave tiles kept %d / %d (%.2f %%), exact filter passing %.2f %%, '
+              'elements ranked %.2f %%, hot wave tiles dropped %d'
+              % (label, int(r['kept'].sum()), r['kept'].size, 100.0 * r['kept'].mean(),
+                 100.0 * (~r['pruned']).mean(), 100.0 * r['live'], r['dropped_hot']))
+        assert r['dropped_hot'] == 0, 'a hot wave tile was dropped'
+    return out
+
+
 def report(label, side, w, mu, sigma, low, high, center, rs, pts=200):
     tab = build(w, mu, sigma, low, high, center)   # (pacc 1: a constant factor of g)
     if tab is None:
@@ -459,6 +527,8 @@ def main():
     ap.add_argument('--cfg4', action='store_true', help="bench.py config 4's history")
     ap.add_argument('--every', type=int, default=1, help='every n-th hp')
     ap.add_argument('--prefilter', action='store_true', help='report the prefilter emulation')
+    ap.add_argument('--drawprune', action='store_true', help='report the pruning-draw emulation')
+    ap.add_argument('--only', default=None, help='--drawprune: comma-separated hp numbers')
     ap.add_argument('--low-edge', action='store_true', help='good trials clustered at low')
     ap.add_argument('--shape', choices=sorted(NAMED), help='another named history')
     ap.add_argument('--draws', type=int, default=1 << 18, help='--prefilter: draws per hp')
@@ -477,9 +547,13 @@ def main():
             lab, lo, hi = a.gap.split(':')
             gap = (lab, float(lo), float(hi))
         losses, cols, specs = test_shape(a.n, gap)
-    run(losses, cols, specs, a.every)
+    if not (a.drawprune and a.only):
+        run(losses, cols, specs, a.every)
     if a.prefilter:
         report_prefilter(losses, cols, specs, a.every, a.draws)
+    if a.drawprune:
+        only = None if a.only is None else {int(x) for x in a.only.split(',')}
+        report_drawprune(losses, cols, specs, a.every, a.draws, only)
 
 
 if __name__ == '__main__':
