@@ -118,6 +118,25 @@ def _tiles(a):
     return np.concatenate([a, np.repeat(a[-1:], pad)]).reshape(NWT, 128)
 
 
+def check_wmax_pair(a, b, ctx):
+    """One (suggestion, hp)'s tab_wmax bits of the default run (a) and of the
+    TPE_DRAW_PRUNE=0 child (b): a's -inf set contains b's, every other entry
+    is bit-equal, every extra -inf tile scores under the child's own tie
+    threshold, and some tiles are -inf but not all.  Returns the -inf share of
+    a and the number of extra -inf entries."""
+    da, db = a == NEG_INF, b == NEG_INF
+    assert not (db & ~da).any()        # the default's -inf set contains the child's
+    np.testing.assert_array_equal(a[~da], b[~da])
+    extra = da & ~db
+    w = b.view(np.float64)
+    real = w[~db]
+    tab_max = np.nan if np.isnan(real).any() else real.max()
+    thr = tab_max - 2.0 ** -16 * max(1.0, abs(tab_max))
+    assert (w[extra] < thr).all(), ctx + (float(w[extra].max()), thr)
+    assert da.any() and not da.all(), ctx + (int(da.sum()),)
+    return da.mean(), int(extra.sum())
+
+
 @pytest.mark.parametrize('kind', ['plain', 'gap', 'cond'])
 def test_draw_prune_changes_nothing_downstream(on_run, off_run, kind):
     (on, on_d), (off, off_d) = on_run, off_run
@@ -137,18 +156,9 @@ def test_draw_prune_changes_nothing_downstream(on_run, off_run, kind):
         for s in range(n_sug):
             if c[s] == 0:                      # (cond: inactive, its wave scores are stale)
                 continue
-            da, db = a[s] == NEG_INF, b[s] == NEG_INF
-            assert not (db & ~da).any()        # the default's -inf set contains the child's
-            np.testing.assert_array_equal(a[s][~da], b[s][~da])
-            extra = da & ~db
-            w = b[s].view(np.float64)
-            real = w[~db]
-            tab_max = np.nan if np.isnan(real).any() else real.max()
-            thr = tab_max - 2.0 ** -16 * max(1.0, abs(tab_max))
-            assert (w[extra] < thr).all(), (kind, lab, s, float(w[extra].max()), thr)
-            assert da.any() and not da.all(), (kind, lab, s, int(da.sum()))
-            fracs.append(da.mean())
-            extras += int(extra.sum())
+            frac, extra = check_wmax_pair(a[s], b[s], (kind, lab, s))
+            fracs.append(frac)
+            extras += extra
         assert fracs, (kind, lab)
         print('%s %s: -inf share of the wave tiles min %.4f median %.4f max %.4f; '
               '%d entries -inf beyond the map prefilter\'s' %

@@ -10,6 +10,7 @@ relative error at random points of each panel against the certified bound.
     python tools/table_error.py --cfg4 --every 7
     python tools/table_error.py --prefilter          # and --cfg4 --every 37, --low-edge
     python tools/table_error.py --drawprune          # and --cfg4 --only 0,42,76, --shape band
+    python tools/table_error.py --fit-set pw-zero --drawprune    # or --gamma 1 --gamma-cap 200 ...
 
 --gap LABEL:LO:HI moves the history values of LABEL inside (LO, HI) out of the
 interval (an empty gap: the edge components widen, the panels beside them lose
@@ -28,6 +29,11 @@ DESIGN 5.6) on the same draws and bucketing: per hp the share of the wave
 tiles the draw keeps (beside the exact filter's passing share), the share of
 the elements it ranks, and the hot wave tiles it drops (which must be 0).
 --only I,J,... takes just those hps.
+
+--gamma, --gamma-cap, --prior-weight and --lf are the fit parameters of
+tpe_plan_fit (defaults 0.25, 25, 1.0, 25); --fit-set NAME takes those of one
+of the named sets (FIT_SETS), which the CPU and the GPU tests of the table
+path away from the default fit share.
 """
 import argparse
 import math
@@ -347,22 +353,61 @@ def pacc_of(family, w, mu, sigma, low, high):
     return float(O._truncation_mass(w, mu, sigma, low, high)) if family == 'gmm' else 1.0
 
 
-def mixtures(losses, cols, label, dist, args):
+# Named fit parameters (tpe_plan_fit's gamma, gamma_cap, prior_weight, lf) on
+# the test shape (N = 6000), with the split and mixture sizes they give there:
+# K_below = n_below + 1 picks the draw kernels (<= 32 the small LDS draw table,
+# <= 2048 the large one, above it no sorted draw and no tables), a tiny K_below
+# leaves a below table of one or two panels, prior_weight 0 a -inf coefficient
+# on the widest component, and prior_weight / lf change every weight.
+def _fit_set(gamma, gamma_cap, prior_weight, lf, n_below, n=6000):
+    return dict(gamma=gamma, gamma_cap=gamma_cap, prior_weight=prior_weight, lf=lf,
+                n_below=n_below, K_below=n_below + 1, K_above=n - n_below + 1)
+
+
+FIT_KEYS = ('gamma', 'gamma_cap', 'prior_weight', 'lf')
+FIT_SETS = {
+    'default': _fit_set(0.25, 25, 1.0, 25, 20),
+    'wide-below': _fit_set(1.0, 200, 1.0, 25, 78),
+    'huge-below': _fit_set(16.0, 2000, 1.0, 25, 1240),
+    'over-cap': _fit_set(32.0, 2500, 1.0, 25, 2479),
+    'few-below': _fit_set(0.02, 25, 1.0, 25, 2),
+    'prior-only': _fit_set(0.0, 25, 1.0, 25, 0),
+    'pw-small': _fit_set(0.25, 25, 1e-3, 25, 20),
+    'pw-big': _fit_set(0.25, 25, 50.0, 25, 20),
+    'pw-zero': _fit_set(0.25, 25, 0.0, 25, 20),
+    'lf-off': _fit_set(0.25, 25, 1.0, 0, 20),
+    'lf-long': _fit_set(1.0, 200, 0.5, 3000, 78),
+}
+
+
+def fit_params(name):
+    """The four fit parameters of a named set, as keyword arguments."""
+    return {k: FIT_SETS[name][k] for k in FIT_KEYS}
+
+
+def mixtures(losses, cols, label, dist, args, gamma=0.25, gamma_cap=25, prior_weight=1.0, lf=25):
     """Both sides' (w, mu, sigma) of one hp, and (low, high, centre)."""
     tids = np.arange(losses.size)
-    fk, pm, ps, low, high, q, tr = O.posterior_spec(dist, args, 1.0)
-    bo, ao = O.split_observations(tids, cols[label], tids, losses, 0.25, kind='stable')
-    fit = [tuple(np.asarray(v) for v in O.parzen_fit(O.transform_obs(obs, tr, low), 1.0, pm, ps,
-                                                      kind='stable')) for obs in (bo, ao)]
+    with np.errstate(all='ignore'):    # (prior_weight 0 takes log(0))
+        fk, pm, ps, low, high, q, tr = O.posterior_spec(dist, args, prior_weight)
+        bo, ao = O.split_observations(tids, cols[label], tids, losses, gamma, gamma_cap,
+                                      kind='stable')
+        fit = [tuple(np.asarray(v) for v in O.parzen_fit(O.transform_obs(obs, tr, low), prior_weight,
+                                                          pm, ps, lf=lf, kind='stable'))
+               for obs in (bo, ao)]
     return fit, (low, high, pm)
 
 
-def certified_pair(losses, cols, label, dist, args):
+def certified_pair(losses, cols, label, dist, args, gamma=0.25, gamma_cap=25, prior_weight=1.0,
+                   lf=25):
     """(tb, ta, below mixture, (low, high, centre)) of an hp whose two tables
     are certified, else None."""
-    fit, (low, high, pm) = mixtures(losses, cols, label, dist, args)
-    fam = O.posterior_spec(dist, args, 1.0)[0]
-    tabs = [build(w, mu, sg, low, high, pm, pacc_of(fam, w, mu, sg, low, high)) for w, mu, sg in fit]
+    fit, (low, high, pm) = mixtures(losses, cols, label, dist, args, gamma, gamma_cap, prior_weight,
+                                    lf)
+    fam = O.posterior_spec(dist, args, prior_weight)[0]
+    with np.errstate(all='ignore'):
+        tabs = [build(w, mu, sg, low, high, pm, pacc_of(fam, w, mu, sg, low, high))
+                for w, mu, sg in fit]
     if any(t is None or not t['ok'].all() for t in tabs):
         return None
     return tabs[0], tabs[1], fit[0], (low, high, pm)
@@ -423,17 +468,18 @@ NAMED = {'low-edge': low_edge_shape, 'high-edge': high_edge_shape, 'band': band_
          'ties': ties_shape, 'comb': comb_shape}
 
 
-def report_prefilter(losses, cols, specs, every=1, draws=1 << 18):
+def report_prefilter(losses, cols, specs, every=1, draws=1 << 18, **fit):
     rs = np.random.RandomState(7)
     for i, (label, (dist, args)) in enumerate(specs.items()):
         if i % every:
             continue
-        pair = certified_pair(losses, cols, label, dist, args)
+        pair = certified_pair(losses, cols, label, dist, args, **fit)
         if pair is None:
             print('%-4s prefilter: no certified pair, every wave tile scored' % label)
             continue
         tb, ta, (w, mu, sg), (low, high, pm) = pair
-        r = prefilter(tb, ta, draw_below(w, mu, sg, low, high, pm, draws, rs))
+        with np.errstate(all='ignore'):
+            r = prefilter(tb, ta, draw_below(w, mu, sg, low, high, pm, draws, rs))
         missed = int((r['pruned'] & ~(r['wmax'] < r['thr'])).sum())
         print('%-4s prefilter: cells hot %d / %d (%.2f %%), intervals %d, wave tiles passing %d / %d '
               '(%.2f %%), hot wave tiles %d, missed %d'
@@ -443,18 +489,19 @@ def report_prefilter(losses, cols, specs, every=1, draws=1 << 18):
         assert missed == 0, 'a hot wave tile was pruned'
 
 
-def report_drawprune(losses, cols, specs, every=1, draws=1 << 18, only=None):
+def report_drawprune(losses, cols, specs, every=1, draws=1 << 18, only=None, **fit):
     rs = np.random.RandomState(7)
     out = {}
     for i, (label, (dist, args)) in enumerate(specs.items()):
         if (i % every) if only is None else (i not in only):
             continue
-        pair = certified_pair(losses, cols, label, dist, args)
+        pair = certified_pair(losses, cols, label, dist, args, **fit)
         if pair is None:
             print('%-4s drawprune: no certified pair, every wave tile written' % label)
             continue
         tb, ta, (w, mu, sg), (low, high, pm) = pair
-        r = draw_prune(tb, ta, draw_below(w, mu, sg, low, high, pm, draws, rs))
+        with np.errstate(all='ignore'):
+            r = draw_prune(tb, ta, draw_below(w, mu, sg, low, high, pm, draws, rs))
         out[label] = r
         print('%-4s drawprune: wave tiles kept %d / %d (%.2f %%), exact filter passing %.2f %%, '
               'elements ranked %.2f %%, hot wave tiles dropped %d'
@@ -465,11 +512,13 @@ def report_drawprune(losses, cols, specs, every=1, draws=1 << 18, only=None):
 
 
 def report(label, side, w, mu, sigma, low, high, center, rs, pts=200):
-    tab = build(w, mu, sigma, low, high, center)   # (pacc 1: a constant factor of g)
+    with np.errstate(all='ignore'):
+        tab = build(w, mu, sigma, low, high, center)   # (pacc 1: a constant factor of g)
     if tab is None:
         print('%-4s %-5s K=%-5d no table (panel count out of range)' % (label, side, w.size))
         return None
-    cc, a2, m = terms(w, mu, sigma, center)
+    with np.errstate(all='ignore'):
+        cc, a2, m = terms(w, mu, sigma, center)
     worst = 0.0
     for p in range(tab['P']):
         y = tab['y_lo'] + tab['width'] * (p + rs.rand(pts))
@@ -504,19 +553,16 @@ def apply_gap(v, lo, hi, log=False):
     return np.exp(x) if log else x
 
 
-def run(losses, cols, specs, every=1):
+def run(losses, cols, specs, every=1, gamma=0.25, gamma_cap=25, prior_weight=1.0, lf=25):
     rs = np.random.RandomState(5)
-    tids = np.arange(losses.size)
     tabs = {}
     for i, (label, (dist, args)) in enumerate(specs.items()):
         if i % every:
             continue
-        fk, pm, ps, low, high, q, tr = O.posterior_spec(dist, args, 1.0)
-        bo, ao = O.split_observations(tids, cols[label], tids, losses, 0.25, kind='stable')
-        for side, obs in (('below', bo), ('above', ao)):
-            w, mu, sg = O.parzen_fit(O.transform_obs(obs, tr, low), 1.0, pm, ps, kind='stable')
-            tabs[label, side] = report(label, side, np.asarray(w), np.asarray(mu), np.asarray(sg),
-                                       low, high, pm, rs)
+        fit, (low, high, pm) = mixtures(losses, cols, label, dist, args, gamma, gamma_cap,
+                                        prior_weight, lf)
+        for side, (w, mu, sg) in zip(('below', 'above'), fit):
+            tabs[label, side] = report(label, side, w, mu, sg, low, high, pm, rs)
     return tabs
 
 
@@ -532,7 +578,14 @@ def main():
     ap.add_argument('--low-edge', action='store_true', help='good trials clustered at low')
     ap.add_argument('--shape', choices=sorted(NAMED), help='another named history')
     ap.add_argument('--draws', type=int, default=1 << 18, help='--prefilter: draws per hp')
+    ap.add_argument('--gamma', type=float, default=0.25)
+    ap.add_argument('--gamma-cap', type=int, default=25)
+    ap.add_argument('--prior-weight', type=float, default=1.0)
+    ap.add_argument('--lf', type=int, default=25)
+    ap.add_argument('--fit-set', choices=sorted(FIT_SETS), help='the fit parameters of a named set')
     a = ap.parse_args()
+    fit = fit_params(a.fit_set) if a.fit_set else dict(
+        gamma=a.gamma, gamma_cap=a.gamma_cap, prior_weight=a.prior_weight, lf=a.lf)
     if a.cfg4:
         sys.path.insert(0, os.path.join(ROOT, 'tests'))
         import bench
@@ -548,12 +601,12 @@ def main():
             gap = (lab, float(lo), float(hi))
         losses, cols, specs = test_shape(a.n, gap)
     if not (a.drawprune and a.only):
-        run(losses, cols, specs, a.every)
+        run(losses, cols, specs, a.every, **fit)
     if a.prefilter:
-        report_prefilter(losses, cols, specs, a.every, a.draws)
+        report_prefilter(losses, cols, specs, a.every, a.draws, **fit)
     if a.drawprune:
         only = None if a.only is None else {int(x) for x in a.only.split(',')}
-        report_drawprune(losses, cols, specs, a.every, a.draws, only)
+        report_drawprune(losses, cols, specs, a.every, a.draws, only, **fit)
 
 
 if __name__ == '__main__':
