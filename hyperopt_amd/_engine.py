@@ -44,7 +44,7 @@ EXPORTS = (
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
     'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
     'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
-    'tpe_plan_cand_dump',
+    'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -166,6 +166,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_tab_bound': (C.c_int, [vp, i32, vp]),
             'tpe_plan_tab_hot': (C.c_int, [vp, i32, vp]),
             'tpe_plan_cand_dump': (C.c_int64, [vp, i32, i32, vp, vp]),
+            'tpe_plan_draw_screen_stats': (C.c_int, [vp, vp]),
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
             'tpe_plan_set_prune': (C.c_int, [vp, i32]),
             'tpe_plan_sample_prior': (C.c_int, [vp, C.POINTER(u64), i64, vp, i32, vp]),
@@ -700,6 +701,16 @@ class Plan(object):
             e.check(int(min(e.lib.tpe_plan_cand_dump(self.p, int(s), int(hp), vals.ctypes.data,
                                                      pos.ctypes.data), 0)))
         return vals, pos
+
+    def draw_screen_stats(self):
+        """Debug (tpe_plan_draw_screen_stats): (sort blocks screened, sort
+        blocks fallen back to the full draw, candidates inverted in the
+        screened blocks) since the last read; reset on read."""
+        e = self.engine
+        out = np.zeros(3, dtype=np.int64)
+        with e.lock:
+            e.check(e.lib.tpe_plan_draw_screen_stats(self.p, out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def last_stats(self):
         e = self.engine

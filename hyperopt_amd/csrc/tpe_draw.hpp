@@ -308,15 +308,22 @@ __device__ __forceinline__ int pick_cdf_ladder(const double *cdf, int K, double 
 // are the same bits (the regeneration tests compare every winner with
 // tpe_sample's draw_table).  cdf_last = T.cdf[K - 1]; high_prev =
 // nextafter(high, -inf).
+// Two halves, so that the screened draw (tpe_screen.hip) can stop between
+// them: the pick (component k and the uniform u1 the inversion takes) ...
 template <int CAP>
-__device__ __forceinline__ double draw_bounded_inline(const DrawTableT<CAP> &T, int K,
-                                                      double cdf_last,
+__device__ __forceinline__ int draw_bounded_pick(const DrawTableT<CAP> &T, int K, double cdf_last,
+                                                 U4 r0, double &u1) {
+  const double u0 = u53(r0.x, r0.y);
+  u1 = u53(r0.z, r0.w);
+  return pick_cdf_ladder<CAP>(T.cdf, K, u0 * cdf_last);
+}
+// ... and the inversion: for a fixed k the value is nondecreasing in u1
+template <int CAP>
+__device__ __forceinline__ double draw_bounded_invert(const DrawTableT<CAP> &T, int k, double u1,
                                                       const double *__restrict__ mu,
                                                       const double *__restrict__ sg, double low,
                                                       double high, double high_prev, bool logn,
-                                                      bool hasq, double qv, U4 r0) {
-  const double u0 = u53(r0.x, r0.y), u1 = u53(r0.z, r0.w);
-  const int k = pick_cdf_ladder<CAP>(T.cdf, K, u0 * cdf_last);
+                                                      bool hasq, double qv) {
   const double s2 = 1.4142135623730951 * sg[k], b = T.base[k], m = T.mass[k];
   const int md = T.mode[k];
   // (draw_table_from's codegen: u1 m once, b -/+ it unfused; x by one fma)
@@ -336,6 +343,17 @@ __device__ __forceinline__ double draw_bounded_inline(const DrawTableT<CAP> &T, 
   if (logn) x = exp(x);
   if (hasq) x = rint(x / qv) * qv;
   return x;
+}
+template <int CAP>
+__device__ __forceinline__ double draw_bounded_inline(const DrawTableT<CAP> &T, int K,
+                                                      double cdf_last,
+                                                      const double *__restrict__ mu,
+                                                      const double *__restrict__ sg, double low,
+                                                      double high, double high_prev, bool logn,
+                                                      bool hasq, double qv, U4 r0) {
+  double u1;
+  const int k = draw_bounded_pick<CAP>(T, K, cdf_last, r0, u1);
+  return draw_bounded_invert<CAP>(T, k, u1, mu, sg, low, high, high_prev, logn, hasq, qv);
 }
 
 // s is wave-uniform: select the inline seed with an unrolled compare chain
@@ -498,32 +516,12 @@ __device__ __forceinline__ uint64_t lanes_equal8(uint32_t d, bool v) {
   return __ballot(v) & ~(((uint64_t)mhi << 32) | mlo);
 }
 
-// counts, then per (bucket, wave) output bases in cnt (16-bit halves); every
-// thread of the block calls it.  Returns the wave's row range [r0, r1).
+// the per (wave, bucket) counts in cnt (16-bit halves) into per (bucket, wave)
+// output bases, in place; every thread of the block calls it, behind a barrier
+// that follows the counting
 template <int NW>
-__device__ __forceinline__ void bucket_bases(const unsigned char *bk, int n, uint32_t *cnt,
-                                             int &r0, int &r1) {
-  // counts and bases per (wave, bucket) are < 2^16 (n <= kSortedBlock): two
-  // buckets per 32-bit LDS word, bucket b in half b & 1 of word b >> 1
-  static_assert(kSortedBlock < 65536, "16-bit bucket counts");
+__device__ __forceinline__ void bucket_bases_scan(uint32_t *cnt) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int per = ((n + NW * 64 - 1) / (NW * 64)) * 64;
-  r0 = w * per;
-  r1 = min(n, r0 + per);
-  uint32_t *mine = cnt + w * (kSortBuckets / 2);
-  for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
-  // (a wave's LDS ops complete in order: no barrier between its own rows)
-  // counts: one LDS atomic per element into the wave's own bins (the order
-  // of the adds does not matter; the ranks below keep the scatter stable)
-  for (int base = r0; base < r1; base += 64) {
-    const int i = base + lane;
-    if (i < r1) {
-      const unsigned d = bk[i];
-      __hip_atomic_fetch_add(&mine[d >> 1], 1u << ((d & 1) * 16), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  }
-  __syncthreads();
   // bucket b (thread b of the first 256): its total over the waves, a block
   // scan of the totals, then the (bucket, wave) bases in place (the even
   // thread of each pair writes the pair's word)
@@ -553,6 +551,35 @@ __device__ __forceinline__ void bucket_bases(const unsigned char *bk, int n, uin
     }
   }
   __syncthreads();
+}
+
+// counts, then per (bucket, wave) output bases in cnt (16-bit halves); every
+// thread of the block calls it.  Returns the wave's row range [r0, r1).
+template <int NW>
+__device__ __forceinline__ void bucket_bases(const unsigned char *bk, int n, uint32_t *cnt,
+                                             int &r0, int &r1) {
+  // counts and bases per (wave, bucket) are < 2^16 (n <= kSortedBlock): two
+  // buckets per 32-bit LDS word, bucket b in half b & 1 of word b >> 1
+  static_assert(kSortedBlock < 65536, "16-bit bucket counts");
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int per = ((n + NW * 64 - 1) / (NW * 64)) * 64;
+  r0 = w * per;
+  r1 = min(n, r0 + per);
+  uint32_t *mine = cnt + w * (kSortBuckets / 2);
+  for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
+  // (a wave's LDS ops complete in order: no barrier between its own rows)
+  // counts: one LDS atomic per element into the wave's own bins (the order
+  // of the adds does not matter; the ranks below keep the scatter stable)
+  for (int base = r0; base < r1; base += 64) {
+    const int i = base + lane;
+    if (i < r1) {
+      const unsigned d = bk[i];
+      __hip_atomic_fetch_add(&mine[d >> 1], 1u << ((d & 1) * 16), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  bucket_bases_scan<NW>(cnt);
 }
 
 // the destination of element i of the wave's current row (its bucket's base

@@ -110,6 +110,9 @@ static bool table_on();
 static double table_tie();
 static bool table_prefilter_on();
 static bool draw_prune_on();
+static bool draw_screen_on();
+static int32_t draw_screen_tiles();
+static int64_t draw_screen_min();
 // TPE_MOMENT_H=0: 16-wide plans without the degree-15 chunk table (A/B)
 static bool moment_h_on() {
   static const bool on = [] {
@@ -170,6 +173,8 @@ struct tpe_plan {
   int32_t tab_pstride = 0;       // pstride of the last launch that took the tables (tab_on 1)
   double *d_tab_bound = nullptr; // [P][kBndCells] bound lattices, built with the tables
   TabHot *d_tab_hot = nullptr;   // [s_cap][P] hot intervals of a launch (ScoreArgs::tab_hot)
+  DrawZone *d_draw_zone = nullptr;  // [s_cap][P] the screened draw's zones (k_draw_zone)
+  unsigned long long *d_screen_stats = nullptr;  // [2] tpe_plan_draw_screen_stats
   bool tab_built = false;
   bool graph_tab = false;       // the captured graph holds the build
   std::vector<double> act_frac;  // per hp: expected share of the trials it is active in
@@ -240,11 +245,13 @@ struct tpe_plan {
     bool tab = false;    // the step builds and scores from the Chebyshev tables
     bool pref = false;   // ... behind the prefilter (k_table_pilot is a node of the step)
     bool dprune = false; // ... with the pruning draw (k_draw_sorted_prune, the pilot ahead of it)
+    int32_t dscreen = -1; // ... screened (k_draw_zone, k_draw_sorted_screen): the zones'
+                          // widening in pilot wave tiles; -1: not screened
     bool operator==(const StepKey &o) const {
       return prior_weight == o.prior_weight && lf == o.lf && n_sug == o.n_sug &&
              n_cand == o.n_cand && stream == o.stream && table == o.table && fuse == o.fuse &&
              small == o.small && mom_w == o.mom_w && tab == o.tab && pref == o.pref &&
-             dprune == o.dprune;
+             dprune == o.dprune && dscreen == o.dscreen;
     }
   };
   StepKey graph_key, pending_key;
@@ -325,7 +332,7 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_ticket, p->d_sortbuf, p->d_census, p->d_lat_info, p->d_lat, p->d_coef32, p->d_coefm,
                   p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
                   p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt, p->d_tab_bound,
-                  p->d_tab_hot};
+                  p->d_tab_hot, p->d_draw_zone, p->d_screen_stats};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -580,6 +587,13 @@ int ensure_suggest_state(tpe_engine *h, tpe_plan *p, int64_t n_sug, size_t parti
     dfree(p->d_tab_hot);
     p->d_tab_hot = nullptr;
     CKH(dalloc(&p->d_tab_hot, (size_t)n_sug * p->P));
+    dfree(p->d_draw_zone);
+    p->d_draw_zone = nullptr;
+    CKH(dalloc(&p->d_draw_zone, (size_t)n_sug * p->P));
+    if (!p->d_screen_stats) {
+      CKH(dalloc(&p->d_screen_stats, 2));
+      CKH(hipMemset(p->d_screen_stats, 0, 2 * sizeof(unsigned long long)));
+    }
     p->s_cap = n_sug;
   }
   if (partials > p->partial_cap) {
@@ -1220,7 +1234,19 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
         p->tab_pstride = a.pstride;
         e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st, 1);
         if (e == hipSuccess) e = launch_table_pilot(a, st);
-        if (e == hipSuccess) e = launch_draw_pruned(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+        // the launches that take k_draw_sorted_prune<kFuseTab, true> screen their
+        // candidates on u1 first (TPE_DRAW_SCREEN=0: today's kernel)
+        // from draw_screen_min() candidate-slots up: below, k_draw_zone's ~33 us
+        // ahead of the draw cost more than the screen saves
+        if (fast && kmax <= kFuseTab && draw_screen_on() &&
+            cn * n_sug * n_level >= draw_screen_min()) {
+          if (e == hipSuccess)
+            e = launch_draw_zone(a, p->d_draw_zone, draw_screen_tiles(), kScreenMargin, st);
+          if (e == hipSuccess)
+            e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats, st);
+        } else if (e == hipSuccess) {
+          e = launch_draw_pruned(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+        }
         a.tab_pref = 2;
       } else {
         e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st);
@@ -1983,13 +2009,20 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
     LatJobs jobs{};
     double2 *lat_out = nullptr;
     int32_t *pos_out = nullptr;
-    void *args[3] = {&da, &jobs, &lat_out};
+    const DrawZone *zones = nullptr;  // (k_draw_sorted_screen's zones and counters)
+    unsigned long long *stats = nullptr;
+    void *args[4] = {&da, &jobs, &lat_out, &stats};
     if (kp.func == lattice_draw_kernel_fn()) {
       jobs = *static_cast<const LatJobs *>(kp.kernelParams[1]);
       lat_out = *static_cast<double2 *const *>(kp.kernelParams[2]);
     } else if (is_sorted_draw_kernel_fn(kp.func)) {
       pos_out = *static_cast<int32_t *const *>(kp.kernelParams[1]);
       args[1] = &pos_out;
+      if (is_screen_draw_kernel_fn(kp.func)) {
+        zones = *static_cast<const DrawZone *const *>(kp.kernelParams[2]);
+        stats = *static_cast<unsigned long long *const *>(kp.kernelParams[3]);
+        args[2] = &zones;
+      }
     }
     kp.kernelParams = args;
     kp.extra = nullptr;
@@ -2037,6 +2070,7 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
     key.tab = key.mom_w == 16 && p->prune_mode == 3 && table_on();
     key.pref = key.tab && table_prefilter_on();
     key.dprune = key.pref && draw_prune_on();
+    key.dscreen = key.dprune && draw_screen_on() ? draw_screen_tiles() : -1;
   }
   int rc = ensure_suggest_state(h, p, n_sug, 1);
   if (rc) return rc;
@@ -2344,6 +2378,22 @@ int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out) {
   return TPE_OK;
 }
 
+int tpe_plan_draw_screen_stats(tpe_plan_t p, int64_t *out) {
+  if (!p || !out) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  out[0] = out[1] = out[2] = 0;
+  if (!p->d_screen_stats) return TPE_OK;
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  unsigned long long v[2];
+  CKH(hipMemcpy(v, p->d_screen_stats, sizeof(v), hipMemcpyDeviceToHost));
+  CKH(hipMemset(p->d_screen_stats, 0, sizeof(v)));
+  out[0] = (int64_t)(v[0] >> 40);
+  out[1] = (int64_t)v[1];
+  out[2] = (int64_t)(v[0] & ((1ull << 40) - 1));
+  return TPE_OK;
+}
+
 int tpe_plan_tab_hot(tpe_plan_t p, int32_t n_suggest, double *out) {
   static_assert(sizeof(TabHot) == (2 + 2 * kHotIv) * sizeof(double), "y_lo, y_hi, lo[], hi[]");
   if (!p || !out || n_suggest < 0) return TPE_E_INVALID;
@@ -2570,6 +2620,38 @@ static bool draw_prune_on() {
   static const bool v = [] {
     const char *e = std::getenv("TPE_DRAW_PRUNE");
     return !(e && *e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+
+// the pruning draw screens its candidates on (component, u1) and inverts only
+// the ones near a hot interval (k_draw_zone, k_draw_sorted_screen;
+// TPE_DRAW_SCREEN=0 restores k_draw_sorted_prune: same-binary A/B and the
+// tests' child processes)
+static bool draw_screen_on() {
+  static const bool v = [] {
+    const char *e = std::getenv("TPE_DRAW_SCREEN");
+    return !(e && *e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+// the zones' widening beyond a hot interval, in pilot wave tiles per side
+// (TPE_DRAW_SCREEN_TILES; DESIGN 7: the sweep behind the default)
+static int32_t draw_screen_tiles() {
+  static const int32_t v = [] {
+    const char *e = std::getenv("TPE_DRAW_SCREEN_TILES");
+    return e && *e ? std::max(0, std::min(kPilotWaves, std::atoi(e))) : 2;
+  }();
+  return v;
+}
+
+// the smallest launch (candidates x suggestions x slots) the screen takes: it
+// saves ~1.4 us per 2^20 candidate-slots on an MI355X, k_draw_zone costs ~33 us
+// (TPE_DRAW_SCREEN_MIN overrides: the tests' small launches)
+static int64_t draw_screen_min() {
+  static const int64_t v = [] {
+    const char *e = std::getenv("TPE_DRAW_SCREEN_MIN");
+    return e && *e ? (int64_t)std::atoll(e) : (int64_t)1 << 26;
   }();
   return v;
 }

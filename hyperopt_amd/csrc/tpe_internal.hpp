@@ -462,7 +462,8 @@ bool fit_small(int64_t n);                 // k_fit<true> (all-LDS variant) serv
 const void *fit_kernel_fn(bool small);     // k_fit's host stub (graph node lookup)
 bool is_draw_kernel_fn(const void *f);     // one of k_draw's / k_draw_sorted's host stubs
 bool is_sorted_draw_kernel_fn(const void *f);
-bool is_prune_draw_kernel_fn(const void *f);  // k_draw_sorted_prune's (tpe_prune.hip)
+bool is_prune_draw_kernel_fn(const void *f);  // k_draw_sorted_prune's (tpe_prune.hip) or
+                                              // k_draw_sorted_screen's (tpe_screen.hip)
 const void *lattice_draw_kernel_fn();      // k_lattice<true> (lattice + fused draw)
 hipError_t launch_prep(const tpe_hp *hps, int32_t n_hp, const double *mw,
                        const double *mmu, const double *msig, MixInfo *info,
@@ -546,6 +547,36 @@ hipError_t launch_draw_sorted(const ScoreArgs &a, bool small_table, bool fast, i
 // table pass then runs with tab_pref 2.  8192-candidate sort blocks only.
 hipError_t launch_draw_pruned(const ScoreArgs &a, bool small_table, bool fast, int32_t *pos_out,
                               hipStream_t st);
+// The screened pruning draw (tpe_screen.hip): k_draw_zone turns a
+// slot's hot intervals and the pilot's sort block into at most kZoneMax
+// disjoint value zones -- the first from -inf, the last to +inf -- outside
+// which no candidate can be hot, and into the u1 thresholds at which each
+// component's draw crosses their edges; k_draw_sorted_screen inverts the CDF
+// only for the candidates whose u1 falls in a zone.
+constexpr int kZoneMax = 6;
+constexpr int kZoneEdges = 2 * kZoneMax - 2;  // interior edges: two per gap between zones
+// the zone edges' widening in sigma of the component: 16 times the largest
+// |draw_bounded_invert's x - the true quantile| / sigma measured over the tail
+// probabilities the screen covers (tools/table_error.py --erfcinv)
+constexpr double kScreenMargin = 1.6e-5;
+struct __attribute__((aligned(16))) DrawZone {
+  int32_t nz;                    // zones in use (0: do not screen the slot)
+  int32_t pad;
+  double gap_lo[kZoneMax - 1];   // gap g: the upper edge of zone g ...
+  double gap_hi[kZoneMax - 1];   // ... and the lower edge of zone g + 1
+  // component k's draw lies strictly inside gap g iff thr[k][2g] <= u1 < thr[k][2g + 1]
+  // (nondecreasing in the edge; all 1: the component is always inverted)
+  double thr[kFuseTab][kZoneEdges];
+};
+// the zones of a launch's slots: after k_table_pilot, ahead of the screened draw
+// (tiles: pilot wave tiles of widening per side; margin: |x drawn - x true| / sigma covered)
+hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, double margin,
+                            hipStream_t st);
+// launch_draw_pruned's fast small-table launch with the screen; stats: two
+// counters (blocks screened << 40 | elements inverted; blocks fallen back)
+hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
+                                unsigned long long *stats, hipStream_t st);
+bool is_screen_draw_kernel_fn(const void *f);  // k_draw_sorted_screen's (tpe_screen.hip)
 // k_table_pilot of the launch's wave-tile class on its own, for the draw that
 // needs the hot intervals (launch_score with tab_pref 2 does not launch it)
 hipError_t launch_table_pilot(const ScoreArgs &a, hipStream_t st);

@@ -48,7 +48,8 @@ bool is_prune_draw_kernel_fn(const void *f) {
   return f == reinterpret_cast<const void *>(&k_draw_sorted_prune<kFuseTab, true>) ||
          f == reinterpret_cast<const void *>(&k_draw_sorted_prune<kTabCap, true>) ||
          f == reinterpret_cast<const void *>(&k_draw_sorted_prune<kFuseTab, false>) ||
-         f == reinterpret_cast<const void *>(&k_draw_sorted_prune<kTabCap, false>);
+         f == reinterpret_cast<const void *>(&k_draw_sorted_prune<kTabCap, false>) ||
+         is_screen_draw_kernel_fn(f);
 }
 
 hipError_t launch_draw_pruned(const ScoreArgs &a, bool small_table, bool fast, int32_t *pos_out,

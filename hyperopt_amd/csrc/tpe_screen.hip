@@ -1,0 +1,518 @@
+// tpe_screen.hip -- the screened pruning draw in a translation
+// unit of its own: the kernels of tpe_prune.hip and tpe_kernels.hip keep their
+// code and register allocation.
+//
+// k_draw_sorted_prune inverts the CDF of every candidate and buckets it, and
+// then drops most wave tiles unread.  For a fixed component k the drawn value
+// is nondecreasing in u1, so whether a candidate can lie near a hot interval
+// is decided from (k, u1): k_draw_zone leaves, per (suggestion, slot), value
+// zones outside which nothing is hot and the u1 thresholds of their edges per
+// component; k_draw_sorted_screen draws Philox and the pick for every
+// candidate, inverts only the ones inside a zone, and composes the kept tiles
+// from those alone where it can prove that the layout is the full draw's.
+// Where it cannot, the sort block runs sorted_block_prune_body from scratch.
+#include <float.h>
+#include <math.h>
+
+#include "tpe_draw.hpp"
+#include "tpe_internal.hpp"
+
+namespace tpe {
+
+constexpr double kScreenQMin = 0x1p-24;  // w = 15.25 at q = 2^-24
+constexpr int kScreenThreads = 512;  // (k_draw_sorted_prune's block)
+constexpr int kZoneThreads = 256;
+constexpr int kZoneCand = kHotIv + 2;  // zones before merging: the hot intervals and two tails
+// a wave's inverted elements (of at most kSortedBlock / 8 = 1024): room for 62 %
+constexpr int kScreenList = 640;
+
+// ------------------------------------------------------------------------
+// k_draw_zone
+// ------------------------------------------------------------------------
+// "the draw of component k at u1 certainly lies above v" (up: an upper zone
+// edge, v = edge + delta) or "... does not certainly lie below v" (a lower
+// zone edge, v = edge - delta): false, then true as u1 grows.  The tail
+// probability is computed from u1 by draw_bounded_invert's own operations
+// (monotone in u1 as floating-point functions) and compared with the normal
+// tail probability of v, so the screen relies on nothing but
+// |draw_bounded_invert's x - the true quantile at that probability| <= delta.
+__device__ __forceinline__ bool zone_crossed(double u1, double b, double m, int md, double z,
+                                             double tail, bool up) {
+  double pu, pp, q1;
+  {
+#pragma clang fp contract(off)
+    const double um = u1 * m;
+    pu = b - um;
+    pp = b + um;
+    q1 = 1.0 - pp;
+  }
+  constexpr double rho = 1e-13;  // (erfc's own error, a few ulp)
+  const double t_hi = tail * (1.0 + rho), t_lo = tail * (1.0 - rho);
+  bool above, below;
+  if (md == 1) {                       // tail = Q(z); x grows as pu falls
+    above = pu < t_lo;
+    below = pu > t_hi;
+  } else if (md == 2 || z < 0.0) {     // tail = Phi(z); below the mean, x grows with pp
+    above = pp > t_hi;
+    below = pp < t_lo;
+  } else {                             // tail = Q(z) at or above the mean
+    above = pp >= 0.5 && q1 < t_lo;
+    below = pp < 0.5 || q1 > t_hi;
+  }
+  // erfcinv_fast holds that bound only for w = -log(2q (2 - 2q)) < 16 (its
+  // tail polynomial drifts beyond: tools/table_error.py --erfcinv), so a tail
+  // probability under kScreenQMin is never cold: every threshold is clamped
+  // into the u1 range with q >= kScreenQMin
+  const bool ok_lo = md == 1 || pp >= kScreenQMin;
+  const bool deep_hi = md == 1 ? pu < kScreenQMin : md == 0 && pp >= 0.5 && q1 < kScreenQMin;
+  return deep_hi || (ok_lo && (up ? above : !below));
+}
+
+// One block per (suggestion, slot row), the grid rows of the draw.  Reads the
+// slot's TabHot and the pilot's sort block (block 0 of A.cand, whole) and
+// writes the slot's DrawZone.
+__global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZone *zones,
+                                                            int32_t tiles, double margin) {
+  __shared__ DrawTableT<kFuseTab> T;
+  __shared__ double tmin[kPilotWaves], tmax[kPilotWaves];
+  __shared__ double zlo[kZoneCand], zhi[kZoneCand];
+  __shared__ int nz_s;
+  const int s = blockIdx.y;
+  const int slot = row_slot(A, s, 0, A.n_slots, blockIdx.x);
+  if (slot < 0) return;
+  const int hp = A.level_hps[slot];
+  const tpe_hp H = A.hps[hp];
+  if (!A.force_active && !A.compact &&
+      !hp_active(H, A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch))
+    return;
+  const int kind = slot_kind(A, slot);
+  if ((kind == KIND_CAT || kind == KIND_LAT) && lookup_inline(A, A.info[2 * hp].K)) return;
+  DrawZone *Z = zones + ((int64_t)s * A.n_hp + hp);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int64_t sb = 2 * (int64_t)hp;
+  const int K = A.info[sb].K;
+  const TabHot *hot = A.tab_hot + ((int64_t)s * A.n_hp + hp);
+  // the slots the screen takes: two-row wave-tile GMM slots, bounded, not
+  // quantized, with a small table, two certified Chebyshev tables and hot
+  // intervals that are not "everything" (sorted_block_prune_body's `prune`)
+  bool scr = kind == KIND_LSE_GW && H.family == TPE_GMM && (H.flags & TPE_HAS_LOW) &&
+             (H.flags & TPE_HAS_HIGH) && !(H.flags & TPE_HAS_Q) && K >= 1 && K <= kFuseTab &&
+             tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sb + 1]);
+  int nh = 0;
+  if (scr) {
+    while (nh < kHotIv && hot->lo[nh] <= hot->hi[nh]) ++nh;
+    scr = !(nh > 0 && hot->lo[0] == -INFINITY && hot->hi[0] == INFINITY);
+  }
+  if (!scr) {  // (block-uniform)
+    if (t == 0) Z->nz = 0;
+    return;
+  }
+  // minimum and maximum of the pilot's 64 wave tiles
+  const double *pc = A.cand + (int64_t)s * A.cand_sstride + (int64_t)slot * A.n_cand;
+  for (int w = wv; w < kPilotWaves; w += kZoneThreads / 64) {
+    const double a = pc[w * 128 + lane], b = pc[w * 128 + 64 + lane];
+    double mn = fmin(a, b), mx = fmax(a, b);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      mn = fmin(mn, __shfl_xor(mn, o, 64));
+      mx = fmax(mx, __shfl_xor(mx, o, 64));
+    }
+    if (lane == 0) { tmin[w] = mn; tmax[w] = mx; }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const double pm = H.prior_mu, y_lo = hot->y_lo, y_hi = hot->y_hi;
+    int nz = 0;
+    // the tails: the block's key range comes from inverted elements alone
+    zlo[nz] = -INFINITY; zhi[nz] = tmax[0]; ++nz;
+    zlo[nz] = tmin[kPilotWaves - 1]; zhi[nz] = INFINITY; ++nz;
+    for (int j = 0; j < nh; ++j) {
+      // the values whose y' = x - prior_mu, clamped into [y_lo, y_hi], can
+      // lie in the interval (a few ulp wider: the rounding of y')
+      const double l = hot->lo[j], h = hot->hi[j];
+      const double a = l <= y_lo ? -INFINITY : (l + pm) - 8.0 * DBL_EPSILON * (fabs(l) + fabs(pm));
+      const double b = h >= y_hi ? INFINITY : (h + pm) + 8.0 * DBL_EPSILON * (fabs(h) + fabs(pm));
+      // ... widened by `tiles` pilot wave tiles on each side: the tiles the
+      // draw keeps reach that far beyond the interval
+      int tf = 0, tl = kPilotWaves - 1;
+      while (tf < kPilotWaves && !(tmax[tf] >= a)) ++tf;
+      while (tl >= 0 && !(tmin[tl] <= b)) --tl;
+      double za = a, zb = b;
+      if (a != -INFINITY) {
+        const int w = tf - tiles;
+        za = w < 0 ? -INFINITY : w < kPilotWaves ? fmin(a, tmin[w]) : a;
+      }
+      if (b != INFINITY) {
+        const int w = tl + tiles;
+        zb = w >= kPilotWaves ? INFINITY : w >= 0 ? fmax(b, tmax[w]) : b;
+      }
+      zlo[nz] = za; zhi[nz] = zb; ++nz;
+    }
+    // by lower edge, overlapping or touching ones merged
+    for (int i = 1; i < nz; ++i)
+      for (int j = i; j > 0 && zlo[j] < zlo[j - 1]; --j) {
+        const double a = zlo[j], b = zhi[j];
+        zlo[j] = zlo[j - 1]; zhi[j] = zhi[j - 1];
+        zlo[j - 1] = a; zhi[j - 1] = b;
+      }
+    int m = 0;
+    for (int i = 1; i < nz; ++i) {
+      if (zlo[i] <= zhi[m]) zhi[m] = fmax(zhi[m], zhi[i]);
+      else { ++m; zlo[m] = zlo[i]; zhi[m] = zhi[i]; }
+    }
+    nz = m + 1;
+    while (nz > kZoneMax) {  // the narrowest gap goes
+      int g = 0;
+      for (int i = 1; i + 1 < nz; ++i)
+        if (zlo[i + 1] - zhi[i] < zlo[g + 1] - zhi[g]) g = i;
+      zhi[g] = zhi[g + 1];
+      for (int i = g + 1; i + 1 < nz; ++i) { zlo[i] = zlo[i + 1]; zhi[i] = zhi[i + 1]; }
+      --nz;
+    }
+    // (one zone: everything would be inverted; the first zone starts at -inf
+    // and the last ends at +inf by the tails)
+    if (nz < 2 || zlo[0] != -INFINITY || zhi[nz - 1] != INFINITY) nz = 0;
+    nz_s = nz;
+    Z->nz = nz;
+    for (int g = 0; g + 1 < nz; ++g) { Z->gap_lo[g] = zhi[g]; Z->gap_hi[g] = zlo[g + 1]; }
+  }
+  __syncthreads();
+  const int nz = nz_s;
+  if (nz == 0) return;
+  const double *bw = A.mw + sb * A.kcap, *bmu = A.mmu + sb * A.kcap, *bsg = A.msig + sb * A.kcap;
+  build_table(H, K, bw, bmu, bsg, T);
+  // threshold (k, e): the smallest u1 = j 2^-53 at which the edge is crossed
+  // (1: none), by bisection on j
+  const int E = 2 * (nz - 1);
+  for (int idx = t; idx < K * E; idx += kZoneThreads) {
+    const int k = idx / E, e = idx - k * E;
+    const bool up = !(e & 1);
+    const double edge = up ? zhi[e >> 1] : zlo[(e >> 1) + 1];
+    const double mu = bmu[k], sg = bsg[k], b = T.base[k], m = T.mass[k];
+    const int md = T.mode[k];
+    double thr = 1.0;
+    if (m > 0.0 && fabs(m) < INFINITY && fabs(b) < INFINITY && sg > 0.0 && fabs(sg) < INFINITY &&
+        fabs(mu) < INFINITY) {
+      const double delta = margin * sg + 8.0 * DBL_EPSILON * (fabs(edge) + fabs(mu));
+      const double v = up ? edge + delta : edge - delta;
+      const double z = (v - mu) / (1.4142135623730951 * sg);
+      const double tail = (md == 1 || (md == 0 && z >= 0.0)) ? 0.5 * erfc(z) : 0.5 * erfc(-z);
+      uint64_t lo = 0, hi = 1ull << 53;
+#pragma unroll 1
+      while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (zone_crossed((double)mid * 0x1p-53, b, m, md, z, tail, up)) hi = mid;
+        else lo = mid + 1;
+      }
+      thr = (double)lo * 0x1p-53;
+      if (!(tail == tail)) thr = 1.0;
+    }
+    Z->thr[k][e] = thr;
+  }
+  __syncthreads();
+  // nondecreasing in the edge (the margins of two close edges may cross: that
+  // gap is empty); a component with a threshold of 1 at its first edge is
+  // never cold
+  for (int k = t; k < K; k += kZoneThreads) {
+    double run = 0.0;
+    for (int e = 0; e < E; ++e) {
+      run = fmax(run, Z->thr[k][e]);
+      Z->thr[k][e] = run;
+    }
+  }
+}
+
+hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, double margin,
+                            hipStream_t st) {
+  const int64_t sbk = (int64_t)1 << a.sort_log2;
+  if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
+  if (sbk != kSortedBlock || sbk != kPilotWaves * 128 || !zones || !a.tab_hot || !a.tab_hdr ||
+      tiles < 0)
+    return hipErrorInvalidValue;
+  k_draw_zone<<<dim3((unsigned)a.slot_rows, a.n_suggest), kZoneThreads, 0, st>>>(a, zones, tiles,
+                                                                                 margin);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------
+// k_draw_sorted_screen
+// ------------------------------------------------------------------------
+template <int NT>
+struct ScreenLds {
+  DrawTableT<kFuseTab> T;
+  double thr[kFuseTab * kZoneEdges];
+  uint32_t cnt[NT / 64 * kSortBuckets / 2];  // (SortedDrawLds::cnt)
+  double red[2][NT / 64];
+  unsigned char hotb[kSortBuckets], liveb[kSortBuckets];  // (PruneDrawLds')
+  unsigned long long keep;
+  int fail;
+  int gapc[NT / 64][kZoneMax - 1];  // a wave's cold elements per gap
+  int ncl[NT / 64];                 // a wave's inverted elements
+  // a wave's inverted elements in index order: u1, then the value; the index
+  // in the block with the component, then with the bucket, above bit 16
+  double cx[NT / 64][kScreenList];
+  uint32_t ci[NT / 64][kScreenList];
+};
+template <int CAP, int NT>
+union ScreenUnion {
+  PruneDrawLds<CAP, NT> P;
+  ScreenLds<NT> S;
+};
+static_assert(sizeof(ScreenUnion<kFuseTab, kScreenThreads>) ==
+                  sizeof(PruneDrawLds<kFuseTab, kScreenThreads>),
+              "the screen's layout lies inside the pruning draw's");
+
+// sorted_block_prune_body's bucket of a key in the block range
+__device__ __forceinline__ int screen_bucket(double key, double lo, double scale) {
+  int b = kSortBuckets - 1;
+  if (fabs(key) < INFINITY) b = min(kSortBuckets - 1, max(0, (int)((key - lo) * scale)));
+  return b;
+}
+
+// One sort block of a screened slot (Z.nz >= 2: a bounded GMM slot, not
+// quantized, K <= CAP, pruned by sorted_block_prune_body).  True: the block's
+// kept tiles and tab_wmax marks are written, as that body writes them.
+// False: nothing is written (the caller runs that body).  Every thread of the
+// block calls it; the result is block-uniform.  nexact: the inverted elements.
+template <int CAP, int NT>
+__device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int s, int64_t base,
+                                               int32_t *__restrict__ pos_out,
+                                               const DrawZone *__restrict__ Z, int nz,
+                                               ScreenLds<NT> &L, int &nexact) {
+  constexpr int NW = NT / 64;
+  const int hp = A.level_hps[slot];
+  const tpe_hp H = A.hps[hp];
+  const int64_t sb = 2 * (int64_t)hp;
+  const double *bw = A.mw + sb * A.kcap, *bmu = A.mmu + sb * A.kcap, *bsg = A.msig + sb * A.kcap;
+  const int K = A.info[sb].K;
+  build_table(H, K, bw, bmu, bsg, L.T);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int E = 2 * (nz - 1);
+  for (int idx = t; idx < K * kZoneEdges; idx += NT) L.thr[idx] = (&Z->thr[0][0])[idx];
+  if (t < kSortBuckets) L.hotb[t] = 0;
+  if (t == 0) { L.keep = 0ull; L.fail = 0; }
+  __syncthreads();
+  const uint64_t seed = suggestion_seed(A, s);
+  const int n = (int)min<int64_t>((int64_t)1 << A.sort_log2, A.n_cand - base);
+  const int64_t off = (int64_t)s * A.cand_sstride + (int64_t)slot * A.n_cand + base;
+  double *out = const_cast<double *>(A.cand) + off;
+  // the wave's rows: bucket_bases' [r0, r1)
+  const int per = ((n + NW * 64 - 1) / (NW * 64)) * 64;
+  const int r0 = wv * per, r1 = min(n, r0 + per);
+  const double cdf_last = L.T.cdf[K - 1];
+  const double high_prev = nextafter(H.high, -INFINITY);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  double *cx = L.cx[wv];
+  uint32_t *ci = L.ci[wv];
+  // phase 1: Philox and the pick of every element; the ones inside a zone to
+  // the wave's list, the others counted per gap
+  int ncl = 0;  // (wave-uniform)
+  int gc[kZoneMax - 1];
+#pragma unroll
+  for (int g = 0; g < kZoneMax - 1; ++g) gc[g] = 0;
+#pragma unroll 1
+  for (int rb = r0; rb < r1; rb += 64) {
+    const int i = rb + lane;
+    const bool v = i < r1;
+    const uint64_t gi = (uint64_t)(A.cand_begin + base + i);
+    const U4 r = philox(U4{(uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)hp, 0u}, k0, k1);
+    double u1;
+    const int k = draw_bounded_pick<CAP>(L.T, K, cdf_last, r, u1);
+    const double *th = L.thr + k * kZoneEdges;
+    int c = 0;
+    for (int e = 0; e < E; ++e) c += u1 >= th[e] ? 1 : 0;
+    const bool exact = v && !(c & 1);
+    const uint64_t bal = __ballot(exact);
+    const int pos = ncl + __popcll(bal & below);
+    if (exact && pos < kScreenList) {
+      cx[pos] = u1;
+      ci[pos] = (uint32_t)i | ((uint32_t)k << 16);
+    }
+    ncl += __popcll(bal);
+    const int gap = (v && (c & 1)) ? (c >> 1) : -1;
+#pragma unroll
+    for (int g = 0; g < kZoneMax - 1; ++g)
+      if (g < nz - 1) gc[g] += __popcll(__ballot(gap == g));
+  }
+  const bool over = ncl > kScreenList;  // (a list overflow: the block falls back)
+  if (over) ncl = 0;
+  if (lane == 0) {
+    L.ncl[wv] = ncl;
+#pragma unroll
+    for (int g = 0; g < kZoneMax - 1; ++g) L.gapc[wv][g] = gc[g];
+    if (over) L.fail = 1;
+  }
+  // the inversion of the listed elements, in dense rows
+  double lo = INFINITY, hi = -INFINITY;
+#pragma unroll 1
+  for (int j0 = 0; j0 < ncl; j0 += 64) {
+    const int j = j0 + lane;
+    const bool v = j < ncl;
+    const double u1 = v ? cx[j] : 0.5;
+    const int k = v ? (int)(ci[j] >> 16) : 0;
+    const double x = draw_bounded_invert<CAP>(L.T, k, u1, bmu, bsg, H.low, H.high, high_prev, false,
+                                              false, 0.0);
+    if (v) {
+      cx[j] = x;
+      if (fabs(x) < INFINITY) { lo = fmin(lo, x); hi = fmax(hi, x); }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, o, 64));
+    hi = fmax(hi, __shfl_xor(hi, o, 64));
+  }
+  if (lane == 0) { L.red[0][wv] = lo; L.red[1][wv] = hi; }
+  uint32_t *mine = L.cnt + wv * (kSortBuckets / 2);
+  for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
+  __syncthreads();
+  lo = INFINITY; hi = -INFINITY;
+  nexact = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    lo = fmin(lo, L.red[0][w]);
+    hi = fmax(hi, L.red[1][w]);
+    nexact += L.ncl[w];
+  }
+  // every cold element lies strictly between the tails' edges: with an
+  // inverted element at or beyond each, the key range is the full draw's
+  if (L.fail || !(lo <= Z->gap_lo[0]) || !(hi >= Z->gap_hi[nz - 2])) return false;
+  // phase 2: buckets and the hot test of the inverted elements, as
+  // sorted_block_prune_body's second pass
+  const double scale = hi > lo ? (double)kSortBuckets / (hi - lo) : 0.0;
+  const double mu = H.prior_mu;
+  const TabHot *hot = A.tab_hot + ((int64_t)s * A.n_hp + hp);
+  const double y_lo = hot->y_lo, y_hi = hot->y_hi;
+  int nh = 0;
+  while (nh < kHotIv && hot->lo[nh] <= hot->hi[nh]) ++nh;
+#pragma unroll 1
+  for (int j0 = 0; j0 < ncl; j0 += 64) {
+    const int j = j0 + lane;
+    if (j < ncl) {
+      const double x = cx[j];
+      const int b = screen_bucket(x, lo, scale);
+      ci[j] = (ci[j] & 0xffffu) | ((uint32_t)b << 16);
+      __hip_atomic_fetch_add(&mine[b >> 1], 1u << ((b & 1) * 16), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+      const double y = x - mu;
+      const double yc = fmin(fmax(y, y_lo), y_hi);
+      bool hit = y != y;
+      for (int q = 0; q < nh; ++q) hit |= yc >= hot->lo[q] && yc <= hot->hi[q];
+      if (hit) L.hotb[b] = 1;
+    }
+  }
+  // a gap's cold elements: counted in the bucket of the zone edge below them
+  // (their own buckets lie between that and the bucket of the edge above)
+  if (lane < nz - 1) {
+    const int c = L.gapc[wv][lane];
+    if (c > 0) {
+      const int b = screen_bucket(Z->gap_lo[lane], lo, scale);
+      __hip_atomic_fetch_add(&mine[b >> 1], (uint32_t)c << ((b & 1) * 16), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  bucket_bases_scan<NW>(L.cnt);
+  int bb = 0, be = 0;
+  if (t < kSortBuckets) {
+    bb = (int)((L.cnt[t >> 1] >> ((t & 1) * 16)) & 0xffffu);
+    be = t == kSortBuckets - 1 ? n : (int)((L.cnt[(t + 1) >> 1] >> (((t + 1) & 1) * 16)) & 0xffffu);
+    if (be > bb && L.hotb[t]) atomicOr(&L.keep, tile_bits(bb >> 7, (be - 1) >> 7));
+  }
+  __syncthreads();
+  const unsigned long long keep = L.keep;
+  if (t < kSortBuckets) {
+    const bool live = be > bb && (keep & tile_bits(bb >> 7, (be - 1) >> 7)) != 0ull;
+    L.liveb[t] = live ? 1 : 0;
+    // a live bucket inside the bucket range a gap's cold elements can occupy:
+    // its base or its members may differ from the full draw's
+    if (live) {
+      for (int g = 0; g < nz - 1; ++g) {
+        int c = 0;
+        for (int w = 0; w < NW; ++w) c += L.gapc[w][g];
+        if (c > 0 && t >= screen_bucket(Z->gap_lo[g], lo, scale) &&
+            t <= screen_bucket(Z->gap_hi[g], lo, scale))
+          L.fail = 1;
+      }
+    }
+  }
+  __syncthreads();
+  if (L.fail) return false;
+  // every hot and every live bucket holds inverted elements only, and each
+  // cold element's bucket is on its proxy's side of every live bucket: keep,
+  // the live buckets' bases and the ranks are the full draw's
+  int32_t *po = pos_out + off;
+  double *__restrict__ wm = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * 8 + (base >> 7);
+  const int ntile = (n + 127) >> 7;
+  if (t < ntile) wm[t] = ((keep >> t) & 1ull) ? INFINITY : -INFINITY;
+#pragma unroll 1
+  for (int j0 = 0; j0 < ncl; j0 += 64) {
+    const int j = j0 + lane;
+    const uint32_t ik = j < ncl ? ci[j] : 0u;
+    const bool lv = j < ncl && L.liveb[ik >> 16] != 0;
+    const int p = bucket_rank(mine, lv ? ik >> 16 : 0u, lv);
+    if (lv && ((keep >> (p >> 7)) & 1ull)) {
+      out[p] = cx[j];
+      po[p] = (int32_t)(base + (ik & 0xffffu));
+    }
+  }
+  return true;
+}
+
+// k_draw_sorted_prune with the screen: the same grid, the same slots; a slot
+// k_draw_zone left no zones for, and a sort block whose screen cannot prove
+// its layout, run sorted_block_prune_body.
+template <int CAP, bool FAST>
+__global__ __launch_bounds__(kScreenThreads) __attribute__((amdgpu_waves_per_eu(4)))
+void k_draw_sorted_screen(ScoreArgs A, int32_t *__restrict__ pos_out,
+                          const DrawZone *__restrict__ zones, unsigned long long *stats) {
+  static_assert(CAP == kFuseTab && FAST, "the small-table inline draw only");
+  __shared__ ScreenUnion<CAP, kScreenThreads> U;
+  const int s = blockIdx.z;
+  const int slot = row_slot(A, s, 0, A.n_slots, blockIdx.y);
+  if (slot < 0) return;
+  const int hp = A.level_hps[slot];
+  if (!A.force_active && !A.compact &&
+      !hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch))
+    return;
+  const int kind = slot_kind(A, slot);
+  if ((kind == KIND_CAT || kind == KIND_LAT) && lookup_inline(A, A.info[2 * hp].K)) return;
+  const bool tabk = kind == KIND_LSE_GW || kind == KIND_LSE_LW;
+  if (tabk && blockIdx.x == 0 && threadIdx.x < (1 << A.sort_log2) / 128 &&
+      (int64_t)threadIdx.x * 128 < A.n_cand)
+    A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * 8 + threadIdx.x] = INFINITY;
+  const int64_t base = (int64_t)(blockIdx.x + 1) << A.sort_log2;
+  const DrawZone *Z = zones + ((int64_t)s * A.n_hp + hp);
+  // (k_draw_zone leaves zones for KIND_LSE_GW slots only)
+  const int nz = kind == KIND_LSE_GW ? __builtin_amdgcn_readfirstlane(Z->nz) : 0;
+  if (nz >= 2 && nz <= kZoneMax) {
+    int nexact = 0;
+    const bool done = screened_block<CAP, kScreenThreads>(A, slot, s, base, pos_out, Z, nz, U.S,
+                                                          nexact);
+    if (threadIdx.x == 0)
+      atomicAdd(stats + (done ? 0 : 1), done ? (1ull << 40) | (unsigned long long)nexact : 1ull);
+    if (done) return;
+    __syncthreads();
+  }
+  sorted_block_prune_body<CAP, kScreenThreads, FAST>(
+      A, slot, s, base, kind_lse(kind) || kind == KIND_ERF_G || kind == KIND_ERF_L,
+      kind_logn(kind), tabk, pos_out, U.P);
+}
+
+bool is_screen_draw_kernel_fn(const void *f) {
+  return f == reinterpret_cast<const void *>(&k_draw_sorted_screen<kFuseTab, true>);
+}
+
+hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
+                                unsigned long long *stats, hipStream_t st) {
+  const int64_t sbk = (int64_t)1 << a.sort_log2;
+  if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
+  if (sbk != kSortedBlock || !a.tab_wmax || !a.tab_hot || !a.tab_hdr || !zones || !stats)
+    return hipErrorInvalidValue;
+  const dim3 g((unsigned)((a.n_cand + sbk - 1) / sbk - 1), (unsigned)a.slot_rows, a.n_suggest);
+  k_draw_sorted_screen<kFuseTab, true><<<g, kScreenThreads, 0, st>>>(a, pos_out, zones, stats);
+  return hipGetLastError();
+}
+
+}  // namespace tpe

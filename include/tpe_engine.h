@@ -365,6 +365,14 @@ int tpe_plan_tab_hot(tpe_plan_t p, int32_t n_suggest, double *out);
  * the device.  Returns n, or a negative status.                             */
 int64_t tpe_plan_cand_dump(tpe_plan_t p, int32_t s, int32_t hp, double *values,
                            int32_t *positions);
+/* Debug: the screened pruning draw's counters since the last read (reset on
+ * read): out[0] sort blocks composed from the screened candidates, out[1]
+ * sort blocks that fell back to the full draw, out[2] candidates whose CDF was
+ * inverted in the blocks of out[0] (of up to 8192 each).  Slots that are not
+ * screened count nowhere.  TPE_DRAW_SCREEN=0: all zero.  The counters take
+ * one atomic add per sort block and wrap (2^24 blocks, 2^40 candidates).
+ * Adds no launch; synchronizes the device.                                  */
+int tpe_plan_draw_screen_stats(tpe_plan_t p, int64_t *out);
 
 /* Prior draws of n_suggest whole suggestions (rand.suggest, the TPE startup
  * phase: hyperopt/rand.py:14-33, pyll/stochastic.py:30-142): every active hp

@@ -347,6 +347,329 @@ def draw_prune(tb, ta, y, tie=TIE, cells=CELLS):
                 dropped_hot=int((hot_tiles & ~kept).sum()))
 
 
+def _fmaf(a, b, c):
+    """fp32 fused multiply-add: the product of two fp32 is exact in fp64."""
+    return np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+
+
+_ERFCINV_C = [2.81022636e-08, 3.43273939e-07, -3.5233877e-06, -4.39150654e-06, 0.00021858087,
+              -0.00125372503, -0.00417768164, 0.246640727, 1.50140941]
+_ERFCINV_T = [-0.000200214257, 0.000100950558, 0.00134934322, -0.00367342844, 0.00573950773,
+              -0.0076224613, 0.00943887047, 1.00167406, 2.83297682]
+
+
+def erfcinv_fast_emul(y):
+    """erfcinv_fast (tpe_draw.hpp) on fp64 y in (0, 1], its fp32 steps in fp32:
+    w = -ln(y (2 - y)) from the two mantissas' log2 (numpy's log2 for
+    v_log_f32), both polynomials by fused multiply-adds, p (1 - y) in fp64;
+    beyond w = 36 the fp64 erfcinv (scipy for OCML's)."""
+    from scipy.special import erfcinv
+    f = np.float32
+    y = np.asarray(y, dtype=np.float64)
+    m1, e1 = np.frexp(y)
+    m2, e2 = np.frexp(2.0 - y)
+    l2 = f(f(np.log2(m1.astype(f)) + np.log2(m2.astype(f))) + (e1 + e2).astype(f))
+    w = f(f(-0.6931471805599453) * l2)
+    wc = f(w - f(2.5))
+    pc = np.full(y.shape, f(_ERFCINV_C[0]), dtype=f)
+    for c in _ERFCINV_C[1:]:
+        pc = _fmaf(pc, wc, f(c))
+    with np.errstate(invalid='ignore'):
+        wt = f(np.sqrt(w) - f(3.0))
+    pt = np.full(y.shape, f(_ERFCINV_T[0]), dtype=f)
+    for c in _ERFCINV_T[1:]:
+        pt = _fmaf(pt, wt, f(c))
+    out = np.where(w < f(5.0), pc, pt).astype(np.float64) * (1.0 - y)
+    far = ~(w <= f(36.0))
+    out[far] = erfcinv(y[far])
+    return out
+
+
+def erfcinv_grid(per_decade=20000):
+    """A dense grid of y = 2 q in (0, 1]: log-spaced from 1e-17 (past the
+    w > 36 hand-off) to 1, the approach to 1 from below, and the w = 5 and
+    w = 36 switches themselves."""
+    y = [np.logspace(-17, 0, 17 * per_decade + 1),
+         1.0 - np.logspace(-16, -0.31, 16 * per_decade),
+         np.linspace(0.5, 1.0, 8 * per_decade),
+         1.0 - np.sqrt(1.0 - np.exp(-np.linspace(4.99, 5.01, per_decade))),
+         1.0 - np.sqrt(1.0 - np.exp(-np.linspace(35.9, 36.1, per_decade)))]
+    y = np.concatenate(y)
+    return np.unique(y[(y > 0.0) & (y <= 1.0)])
+
+
+def invert_error():
+    """max |x drawn - x true| / sigma of draw_bounded_invert over erfcinv_grid:
+    x = mu +- sqrt2 sigma erfcinv(2 q) in every mode of the table, so the
+    error in sigma is sqrt2 |erfcinv_fast - erfcinv| whichever tail the mode
+    inverts.  Per range of w: (label, max error, y at the maximum)."""
+    from scipy.special import erfcinv
+    y = erfcinv_grid()
+    err = math.sqrt(2.0) * np.abs(erfcinv_fast_emul(y) - erfcinv(y))
+    w = -np.log(y * (2.0 - y))
+    rows = []
+    for lab, sel in (('w < 5 (central)', w < 5.0),
+                     ('5 <= w <= %.2f (screened tail)' % SCREEN_W_MAX, (w >= 5.0) & (w <= SCREEN_W_MAX)),
+                     ('%.2f < w <= 36 (tail, never cold)' % SCREEN_W_MAX, (w > SCREEN_W_MAX) & (w <= 36.0)),
+                     ('w > 36 (fp64 hand-off, never cold)', w > 36.0)):
+        i = int(np.argmax(np.where(sel, err, -1.0)))
+        rows.append((lab, float(err[i]), float(y[i])))
+    return rows
+
+
+# The screened draw (tpe_screen.hip): a draw whose tail probability q is under
+# SCREEN_Q_MIN is always inverted (erfcinv_fast's tail polynomial drifts from
+# w = 16 on, to ~1 sigma at w = 36), and the zone edges are widened by
+# SCREEN_MARGIN sigma: at least 16 times invert_error()'s maximum over
+# w <= SCREEN_W_MAX (the 16: v_log_f32 / v_sqrt_f32 against numpy's by an ulp)
+SCREEN_Q_MIN = 2.0 ** -24
+SCREEN_W_MAX = -math.log(2.0 * SCREEN_Q_MIN * (2.0 - 2.0 * SCREEN_Q_MIN))
+SCREEN_MARGIN = 1.6e-5
+
+
+def draw_table(w, mu, sigma, low, high):
+    """build_table's per-component constants of a bounded mixture: (pick
+    weights, base, mass, mode)."""
+    from scipy.special import erfc
+    w, mu, sigma = (np.asarray(v, dtype=np.float64) for v in (w, mu, sigma))
+    s2 = 1.4142135623730951 * sigma
+    za, zb = (low - mu) / s2, (high - mu) / s2
+    mode = np.where(za >= 0.0, 1, np.where(zb <= 0.0, 2, 0))
+    base = np.where(mode == 1, 0.5 * erfc(za), 0.5 * erfc(-za))
+    mass = np.where(mode == 1, base - 0.5 * erfc(zb), 0.5 * erfc(-zb) - base)
+    mass = np.where(mass > 0.0, mass, 0.0)
+    return w * mass, base, mass, mode
+
+
+def draw_invert_emul(base, mass, mode, mu, sigma, low, high, u1):
+    """draw_bounded_invert (GMM, not quantized) with erfcinv_fast_emul: the
+    value of component constants (arrays, broadcast against u1)."""
+    um = u1 * mass
+    pu, pp = base - um, base + um
+    lower = (mode != 1) & ((mode == 2) | (pp < 0.5))
+    q = np.where(mode == 1, pu, np.where(lower, pp, 1.0 - pp))
+    with np.errstate(all='ignore'):
+        e = erfcinv_fast_emul(np.where(q > 0.0, 2.0 * q, 1.0))
+        e = np.where(q > 0.0, e, np.inf)
+        x = np.where(lower, -1.0, 1.0) * (1.4142135623730951 * sigma) * e + mu
+    x = np.where(x >= low, x, low)
+    return np.where(x < high, x, np.nextafter(high, -np.inf))
+
+
+def zone_crossed(u1, base, mass, mode, z, tail, up):
+    """tpe_screen.hip's zone_crossed, operation for operation (arrays)."""
+    um = u1 * mass
+    pu, pp = base - um, base + um
+    q1 = 1.0 - pp
+    rho = 1e-13
+    t_hi, t_lo = tail * (1.0 + rho), tail * (1.0 - rho)
+    phi = (mode == 2) | ((mode == 0) & (z < 0.0))
+    above = np.where(mode == 1, pu < t_lo, np.where(phi, pp > t_hi, (pp >= 0.5) & (q1 < t_lo)))
+    below = np.where(mode == 1, pu > t_hi, np.where(phi, pp < t_lo, (pp < 0.5) | (q1 > t_hi)))
+    ok_lo = (mode == 1) | (pp >= SCREEN_Q_MIN)
+    deep_hi = np.where(mode == 1, pu < SCREEN_Q_MIN,
+                       (mode == 0) & (pp >= 0.5) & (q1 < SCREEN_Q_MIN))
+    return deep_hi | (ok_lo & np.where(up, above, ~below))
+
+
+def zone_thresholds(zlo, zhi, base, mass, mode, mu, sigma, margin=None):
+    """k_draw_zone's u1 thresholds thr[K][2 (nz - 1)] of the disjoint value
+    zones [zlo[i], zhi[i]] (ascending, the first from -inf, the last to +inf):
+    component k's draw is cold in gap g iff thr[k][2g] <= u1 < thr[k][2g + 1]."""
+    from scipy.special import erfc
+    margin = SCREEN_MARGIN if margin is None else margin
+    nz, K = len(zlo), len(mu)
+    E = 2 * (nz - 1)
+    e = np.arange(E)
+    up = (e % 2 == 0)[None, :]
+    edge = np.where(up, np.asarray(zhi, dtype=np.float64)[e // 2][None, :],
+                    np.asarray(zlo, dtype=np.float64)[np.minimum(e // 2 + 1, nz - 1)][None, :])
+    b, m, md, mu_, sg = (np.broadcast_to(np.asarray(v)[:, None], (K, E)) for v in
+                         (base, mass, mode, mu, sigma))
+    eps = np.finfo(np.float64).eps
+    delta = margin * sg + 8.0 * eps * (np.abs(edge) + np.abs(mu_))
+    v = np.where(up, edge + delta, edge - delta)
+    z = (v - mu_) / (1.4142135623730951 * sg)
+    tail = np.where((md == 1) | ((md == 0) & (z >= 0.0)), 0.5 * erfc(z), 0.5 * erfc(-z))
+    lo = np.zeros((K, E), dtype=np.uint64)
+    hi = np.full((K, E), 1 << 53, dtype=np.uint64)
+    for _ in range(54):
+        mid = (lo + hi) >> np.uint64(1)
+        c = zone_crossed(mid.astype(np.float64) * 2.0 ** -53, b, m, md, z, tail, up)
+        act = lo < hi
+        hi = np.where(act & c, mid, hi)
+        lo = np.where(act & ~c, mid + np.uint64(1), lo)
+    thr = lo.astype(np.float64) * 2.0 ** -53
+    bad = ~((m > 0.0) & np.isfinite(m) & np.isfinite(b) & (sg > 0.0) & np.isfinite(sg) &
+            np.isfinite(mu_) & ~np.isnan(tail))
+    thr = np.where(bad, 1.0, thr)
+    return np.maximum.accumulate(thr, axis=1)
+
+
+def screen_gap(thr_k, u1):
+    """The screen's class of draws u1 of one component (its thresholds): the
+    gap number of a cold draw, -1 for one that is inverted."""
+    c = (u1[:, None] >= thr_k[None, :]).sum(axis=1)
+    return np.where(c % 2 == 1, c // 2, -1)
+
+
+def draw_picks(w, mu, sigma, low, high, n, rs):
+    """n draws of the table sampler: (component, u1, value)."""
+    pw, base, mass, mode = draw_table(w, mu, sigma, low, high)
+    cdf = np.cumsum(pw)
+    k = np.minimum(np.searchsorted(cdf, rs.random_sample(n) * cdf[-1], side='right'), cdf.size - 1)
+    u1 = np.floor(rs.random_sample(n) * 2.0 ** 53) * 2.0 ** -53
+    mu, sigma = np.asarray(mu), np.asarray(sigma)
+    return k, u1, draw_invert_emul(base[k], mass[k], mode[k], mu[k], sigma[k], low, high, u1)
+
+
+def _block_bytes(x, lo, hi):
+    scale = BUCKETS / (hi - lo) if hi > lo else 0.0
+    return np.clip(((x - lo) * scale).astype(np.int64), 0, BUCKETS - 1)
+
+
+def _block_layout(key, hit, n):
+    """sorted_block_prune_body's layout from the bucket bytes and the hot
+    flags: (counts, bases, keep per wave tile, live per bucket)."""
+    cnt = np.bincount(key, minlength=BUCKETS)
+    base = np.cumsum(cnt) - cnt
+    full = cnt > 0
+    t0, t1 = base // WAVE, np.where(full, (base + cnt - 1) // WAVE, base // WAVE)
+    hotb = full & (np.bincount(key[hit], minlength=BUCKETS) > 0)
+    keep = np.zeros((n + WAVE - 1) // WAVE, dtype=bool)
+    for b in np.flatnonzero(hotb):
+        keep[t0[b]:t1[b] + 1] = True
+    ck = np.concatenate([[0], np.cumsum(keep)])
+    live = full & (ck[np.minimum(t1 + 1, keep.size)] - ck[np.minimum(t0, keep.size)] > 0)
+    return cnt, base, keep, live
+
+
+def draw_zones(pilot, intervals, y_lo, y_hi, center, tiles, zone_max=6):
+    """k_draw_zone's value zones (zlo, zhi) from the pilot's sort block (draw
+    order) and the hot intervals in y'; None: the slot is not screened."""
+    key = _block_bytes(pilot, pilot.min(), pilot.max())
+    t = pilot[np.argsort(key, kind='stable')].reshape(-1, WAVE)
+    tmin, tmax = t.min(axis=1), t.max(axis=1)
+    nt = tmin.size
+    eps = np.finfo(np.float64).eps
+    z = [(-np.inf, tmax[0]), (tmin[-1], np.inf)]
+    for l, h in intervals:
+        a = -np.inf if l <= y_lo else (l + center) - 8.0 * eps * (abs(l) + abs(center))
+        b = np.inf if h >= y_hi else (h + center) + 8.0 * eps * (abs(h) + abs(center))
+        reach = np.flatnonzero(tmax >= a)
+        tf = int(reach[0]) if reach.size else nt
+        reach = np.flatnonzero(tmin <= b)
+        tl = int(reach[-1]) if reach.size else -1
+        za, zb = a, b
+        if a != -np.inf:
+            w = tf - tiles
+            za = -np.inf if w < 0 else min(a, tmin[w]) if w < nt else a
+        if b != np.inf:
+            w = tl + tiles
+            zb = np.inf if w >= nt else max(b, tmax[w]) if w >= 0 else b
+        z.append((za, zb))
+    z.sort(key=lambda p: p[0])
+    out = [list(z[0])]
+    for a, b in z[1:]:
+        if a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    while len(out) > zone_max:
+        g = int(np.argmin([out[i + 1][0] - out[i][1] for i in range(len(out) - 1)]))
+        out[g][1] = out[g + 1][1]
+        del out[g + 1]
+    if len(out) < 2:
+        return None
+    return np.array([a for a, _ in out]), np.array([b for _, b in out])
+
+
+def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cells=CELLS):
+    """The screened draw on the draws (k, u1, x) of one launch (draw_picks),
+    block by block behind the pilot's, beside the full computation on all
+    elements: dict with `blocks`, `fallback` (blocks that would run the full
+    body), `exact` (share of the screened blocks' elements inverted) and
+    `mismatch`: the blocks that do not fall back and whose key range, kept
+    mask, live buckets, their counts and bases, or the bucket bytes of the
+    inverted elements differ from the full computation's (must be empty)."""
+    w, mu, sigma = mix
+    r = prefilter(tb, ta, x - center, tie, cells)
+    y_lo = tb['y_lo']
+    y_hi = y_lo + tb['width'] * tb['P']
+    out = dict(blocks=0, fallback=0, exact=0.0, mismatch=[])
+    zones = draw_zones(x[:SORT_BLOCK], r['intervals'], y_lo, y_hi, center, tiles)
+    if zones is None:
+        return out
+    zlo, zhi = zones
+    _, base, mass, mode = draw_table(w, mu, sigma, low, high)
+    thr = zone_thresholds(zlo, zhi, base, mass, mode, np.asarray(mu), np.asarray(sigma))
+    c = (u1[:, None] >= thr[k]).sum(axis=1)
+    cold, gap = c % 2 == 1, c // 2
+    yc = np.clip(x - center, y_lo, y_hi)
+    hit = np.isnan(x)
+    for lo_i, hi_i in r['intervals']:
+        hit |= (yc >= lo_i) & (yc <= hi_i)
+    nex = nscr = 0
+    for b0 in range(SORT_BLOCK, x.size, SORT_BLOCK):
+        s = slice(b0, b0 + SORT_BLOCK)
+        xb, cb, gb, hb = x[s], cold[s], gap[s], hit[s]
+        out['blocks'] += 1
+        ex = ~cb
+        if not ex.any() or xb[ex].min() > zhi[0] or xb[ex].max() < zlo[-1] or (hb & cb).any():
+            out['fallback'] += 1       # (a hot cold element cannot happen: counted, never hidden)
+            if (hb & cb).any():
+                out['mismatch'].append((b0, 'hot element screened out'))
+            continue
+        lo, hi = xb[ex].min(), xb[ex].max()
+        full = _block_layout(_block_bytes(xb, xb.min(), xb.max()), hb, xb.size)
+        key = np.where(cb, _block_bytes(zhi[np.where(cb, gb, 0)], lo, hi), _block_bytes(xb, lo, hi))
+        cnt, bas, keep, live = _block_layout(key, hb, xb.size)
+        bad = False
+        for g in np.unique(gb[cb]):
+            p0, p1 = int(_block_bytes(zhi[g], lo, hi)), int(_block_bytes(zlo[g + 1], lo, hi))
+            bad |= bool(live[p0:p1 + 1].any())
+        if bad:
+            out['fallback'] += 1
+            continue
+        nscr += xb.size
+        nex += int(ex.sum())
+        same = (lo == xb.min() and hi == xb.max() and (keep == full[2]).all() and
+                (live == full[3]).all() and (cnt[live] == full[0][live]).all() and
+                (bas[live] == full[1][live]).all() and
+                (key[ex] == _block_bytes(xb, xb.min(), xb.max())[ex]).all())
+        if not same:
+            out['mismatch'].append((b0, 'layout'))
+    out['exact'] = nex / max(1, nscr)
+    return out
+
+
+def report_drawscreen(losses, cols, specs, every=1, draws=1 << 18, only=None, tiles=2, **fit):
+    """Per hp with two certified tables: blocks, fallback blocks and the share
+    of inverted elements of the screened draw's emulation."""
+    for i, (label, (dist, args)) in enumerate(specs.items()):
+        if i % every or (only is not None and i not in only):
+            continue
+        cp = certified_pair(losses, cols, label, dist, args, **fit)
+        if cp is None or dist != 'uniform':
+            print('%-6s not screened' % label)
+            continue
+        tb, ta, mix, (low, high, center) = cp
+        k, u1, x = draw_picks(*mix, low, high, draws, np.random.RandomState(1000 + i))
+        r = draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles)
+        print('%-6s blocks %4d fallback %4d inverted %.4f mismatches %d'
+              % (label, r['blocks'], r['fallback'], r['exact'], len(r['mismatch'])))
+
+
+def report_erfcinv():
+    rows = invert_error()
+    for lab, e, y in rows:
+        print('erfcinv_fast %-40s max |x - x_ref| / sigma %.3e at y = %.6e' % (lab, e, y))
+    worst = max(e for _, e, _ in rows[:2])
+    print('screened range: max %.3e, 16 x = %.3e, SCREEN_MARGIN %.3e' % (worst, 16.0 * worst,
+                                                                          SCREEN_MARGIN))
+    return worst
+
+
 def pacc_of(family, w, mu, sigma, low, high):
     """The truncation mass in a side's table constants: a GMM's p_accept
     (make_coef), 1 for an LGMM (its lpdf applies none)."""
@@ -583,7 +906,14 @@ def main():
     ap.add_argument('--prior-weight', type=float, default=1.0)
     ap.add_argument('--lf', type=int, default=25)
     ap.add_argument('--fit-set', choices=sorted(FIT_SETS), help='the fit parameters of a named set')
+    ap.add_argument('--drawscreen', action='store_true', help='report the screened-draw emulation')
+    ap.add_argument('--tiles', type=int, default=2, help='--drawscreen: zone widening in pilot tiles')
+    ap.add_argument('--erfcinv', action='store_true',
+                    help="only report erfcinv_fast's emulated error (the screened draw's margin)")
     a = ap.parse_args()
+    if a.erfcinv:
+        report_erfcinv()
+        return
     fit = fit_params(a.fit_set) if a.fit_set else dict(
         gamma=a.gamma, gamma_cap=a.gamma_cap, prior_weight=a.prior_weight, lf=a.lf)
     if a.cfg4:
@@ -600,6 +930,10 @@ def main():
             lab, lo, hi = a.gap.split(':')
             gap = (lab, float(lo), float(hi))
         losses, cols, specs = test_shape(a.n, gap)
+    if a.drawscreen:
+        only = None if a.only is None else {int(x) for x in a.only.split(',')}
+        report_drawscreen(losses, cols, specs, a.every, a.draws, only, a.tiles, **fit)
+        return
     if not (a.drawprune and a.only):
         run(losses, cols, specs, a.every, **fit)
     if a.prefilter:
