@@ -16,112 +16,11 @@
 
 #include "tpe_anneal.hpp"
 #include "tpe_internal.hpp"
+#include "tpe_level_plan.hpp"
+#include "tpe_switches.hpp"
 
 using namespace tpe;
 static_assert(sizeof(AnnealTrace) == sizeof(tpe_anneal_trace), "layout");
-
-static int lse_shift_min();
-static bool small_sort_on();
-static int64_t chunk_budget();
-// TPE_SIDE_STREAMS=1: the lattice launch and a mixed level's lookup launch
-// run on auxiliary streams beside the draw / the wave-tile launch (fork and
-// join events); default off: every launch in order on the suggest stream
-// lookup slots drawn inside their scoring tiles (ScoreArgs::lookup_draw);
-// TPE_LOOKUP_DRAW=0 writes them from the sorted draw instead (A/B)
-static bool lookup_draw_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_LOOKUP_DRAW");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-// TPE_LOOKUP_FORK=0: a chunk's self-drawing lookup launch in order on the
-// suggest stream instead of beside its draw
-static bool lookup_fork_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_LOOKUP_FORK");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-// TPE_PUBLISH=0: results to the host by a runtime copy + stream synchronize
-// instead of k_publish + a spin on its completion word
-static bool publish_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_PUBLISH");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-// TPE_PATCH_DEFER=0: small history updates go out at once (k_hist_patch)
-// instead of riding the next fit's arguments
-static bool patch_defer_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_PATCH_DEFER");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-// TPE_TILE_DRAW=0: tiny unsorted draws by k_draw instead of their tiles
-static bool tile_draw_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_TILE_DRAW");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-// TPE_PUBLISH_FUSE=0: a call whose last launch is a tile_draw scoring launch
-// still ends with k_publish (default: that launch's last record publishes)
-static bool publish_fuse_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_PUBLISH_FUSE");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-// TPE_L2_WARM=1: scoring tiles first touch every 128-B line of both
-// mixtures' coefficient tables (round 2's L2 warm-up).  Off by default since
-// round 6: the same-box A/B (gpurun_out/r6_05) gave config 4 127.3 -> 124.2 ms
-// and config 5 543 -> 536 ms per step without it -- the waves' first envelope
-// reads waited on those loads, and the tables are L2-resident after the first
-// blocks anyway
-// TPE_TIGHTEN=0: wave tiles keep lse_window's skip threshold (no tightening
-// from the block of the highest bound) -- A/B
-static bool tighten_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_TIGHTEN");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-static bool l2_warm_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_L2_WARM");
-    return e && std::atoi(e) != 0;
-  }();
-  return on;
-}
-static bool side_streams_on() {
-  static const bool on = std::getenv("TPE_SIDE_STREAMS") != nullptr;
-  return on;
-}
-static bool moment_on();
-static bool table_on();
-static double table_tie();
-static bool table_prefilter_on();
-static bool draw_prune_on();
-static bool draw_screen_on();
-static int32_t draw_screen_tiles();
-static int64_t draw_screen_min();
-// TPE_MOMENT_H=0: 16-wide plans without the degree-15 chunk table (A/B)
-static bool moment_h_on() {
-  static const bool on = [] {
-    const char *e = std::getenv("TPE_MOMENT_H");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-constexpr int64_t kSmallSortMin = 2048;  // candidates per chunk worth bucketing a small draw
 
 struct tpe_engine {
   int32_t device = 0;
@@ -132,18 +31,15 @@ struct tpe_engine {
   tpe_plan *op = nullptr;  // cached single-hp plan for operator-level calls
 };
 
-struct tpe_plan {
+// (PlanShape: the compiled space as plan_level reads it -- hps, conditions,
+// levels, value lattices, kcap, act_frac)
+struct tpe_plan : PlanShape {
   tpe_engine *eng = nullptr;
   int32_t P = 0;
-  int64_t ncap = 0, kcap = 0;
+  int64_t ncap = 0;
   int32_t last_nb = -1;  // n_below of the last tpe_plan_fit (below K <= n_below + 1)
-  std::vector<tpe_hp> hps;
-  std::vector<int32_t> cond_parent, cond_branch;
   std::vector<double> pprior;
-  std::vector<std::vector<int32_t>> levels;
   std::vector<int32_t> level_off;  // offsets of each level in d_level_hps
-  struct Group { int32_t kind, off, count; };
-  std::vector<std::vector<Group>> groups;  // per level, hps grouped by lpdf kind
   // device buffers
   tpe_hp *d_hps = nullptr;
   int32_t *d_cp = nullptr, *d_cb = nullptr, *d_level_hps = nullptr, *d_all_hps = nullptr;
@@ -177,7 +73,6 @@ struct tpe_plan {
   unsigned long long *d_screen_stats = nullptr;  // [2] tpe_plan_draw_screen_stats
   bool tab_built = false;
   bool graph_tab = false;       // the captured graph holds the build
-  std::vector<double> act_frac;  // per hp: expected share of the trials it is active in
   int64_t n = 0;  // history length
   // suggestion state
   int64_t s_cap = 0;
@@ -186,9 +81,8 @@ struct tpe_plan {
   size_t h_results_cap = 0;
   uint64_t *h_flag = nullptr;       // pinned completion word of k_publish
   uint64_t seq = 0;
-  // this call's results go to the host and its last launch may publish them
-  // itself (tpe_plan_fit_suggest); pub_fired: it does, with sequence seq
-  bool pub_arm = false;
+  // this call's last launch publishes its results itself (StepShape::publish,
+  // tpe_plan_fit_suggest), with sequence seq
   bool pub_fired = false;
   uint64_t *d_seeds = nullptr;
   Partial *d_partial = nullptr;
@@ -198,8 +92,7 @@ struct tpe_plan {
   uint32_t *d_ticket = nullptr;
   std::vector<uint64_t> h_seeds;  // this call's seeds (inline kernel args when <= 8)
   bool has_erf = false;
-  // value lattices of the bounded quantized hps (KIND_LAT, k_lattice)
-  std::vector<LatInfo> lat;
+  // value lattices of the bounded quantized hps (KIND_LAT, k_lattice; PlanShape::lat)
   LatInfo *d_lat_info = nullptr;
   double2 *d_lat = nullptr;
   bool lattice_on = true;
@@ -232,31 +125,22 @@ struct tpe_plan {
   // fit + suggest captured as one hipGraph (tpe_plan_fit_suggest): replayed
   // with the history length / n_below of the fit node and the seeds of the
   // draw nodes patched per call
+  // The key of a captured step: the arguments baked into its nodes, and the
+  // StepShape (capturing) every launch decision of the step is a function of
+  // -- with the fit variant in it (mom_width grows with the history: a replay
+  // must not keep the captured width)
   struct StepKey {
     double prior_weight = 0;
     int32_t lf = 0;
-    int64_t n_sug = 0, n_cand = 0;
     void *stream = nullptr;
-    bool table = false;  // below mixtures fit the LDS draw table (kTabCap)
-    bool fuse = false;   // ... and the fused k_lattice draw rows' table (kFuseTab)
-    bool small = false;  // k_fit<true> serves the history (fit_small)
-    int32_t mom_w = 0;   // the moment table the step's fit writes (mom_width grows with
-                         // the history: a replay must not keep the captured width)
-    bool tab = false;    // the step builds and scores from the Chebyshev tables
-    bool pref = false;   // ... behind the prefilter (k_table_pilot is a node of the step)
-    bool dprune = false; // ... with the pruning draw (k_draw_sorted_prune, the pilot ahead of it)
-    int32_t dscreen = -1; // ... screened (k_draw_zone, k_draw_sorted_screen): the zones'
-                          // widening in pilot wave tiles; -1: not screened
+    StepShape shape;
     bool operator==(const StepKey &o) const {
-      return prior_weight == o.prior_weight && lf == o.lf && n_sug == o.n_sug &&
-             n_cand == o.n_cand && stream == o.stream && table == o.table && fuse == o.fuse &&
-             small == o.small && mom_w == o.mom_w && tab == o.tab && pref == o.pref &&
-             dprune == o.dprune && dscreen == o.dscreen;
+      return prior_weight == o.prior_weight && lf == o.lf && stream == o.stream &&
+             shape == o.shape;
     }
   };
   StepKey graph_key, pending_key;
   bool graph_ok = false, pending = false;
-  bool capturing = false;  // enqueue_step under graph capture (no per-call patch of score seeds)
   int32_t mom_w = 0;       // moment table the last fit wrote: 16 (CoefM), 8 (CoefM8), 0 none
   bool mom_h = false;      // ... and with 16, the degree-15 table (CoefMH)
   bool graph_mom_h = false;
@@ -439,19 +323,8 @@ int compute_levels(tpe_engine *h, tpe_plan *p) {
     for (int i = 0; i < p->P; ++i)
       if (score_kind(p->hps[i]) == kind) p->levels[lev[i]].push_back(i);
   p->level_off.assign(nl + 1, 0);
-  p->groups.assign(nl, {});
-  for (int l = 0; l < nl; ++l) {
+  for (int l = 0; l < nl; ++l)
     p->level_off[l + 1] = p->level_off[l] + (int)p->levels[l].size();
-    int j = 0;
-    const auto &L = p->levels[l];
-    while (j < (int)L.size()) {
-      const int kind = score_kind(p->hps[L[j]]);
-      int k = j;
-      while (k < (int)L.size() && score_kind(p->hps[L[k]]) == kind) ++k;
-      p->groups[l].push_back({kind, p->level_off[l] + j, k - j});
-      j = k;
-    }
-  }
   return TPE_OK;
 }
 
@@ -536,6 +409,7 @@ int plan_build(tpe_engine *h, const tpe_space *sp, int64_t max_trials, tpe_plan 
       }
       p->act_frac[i] = std::min(1.0, f);
     }
+  p->finish();  // (the per-level data of plan_level)
   CKH(hipEventCreate(&p->ev0));
   CKH(hipEventCreate(&p->ev1));
   CKH(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
@@ -625,92 +499,10 @@ int ensure_ext(tpe_engine *h, tpe_plan *p, size_t n) {
   return TPE_OK;
 }
 
-// Scoring grid of one launch over n_slots slots whose lpdf kinds are `kinds`
-// (consecutive slots of one kind form a group, tiles of 64 * tile_rows(kind)
-// candidates).  Returns the partial-record stride (max tiles per slot), or -1
-// when the slots are not grouped by kind.
-// Runs of equal-kind slots become groups of the 1-D scoring grid, emitted
-// heaviest kind first (per-candidate erf, then log-sum-exp, then the lattice /
-// categorical lookups): the dispatcher hands out the long blocks first and the
-// short ones fill the CUs that finish early.
-// rows(b, e) (optional, compact grids): block rows for the slots [b, e) of a
-// group (active_bound), else one row per slot.
-template <typename Rows>
-int32_t set_score_groups(ScoreArgs &a, const int *kinds, int n_slots, int64_t cn, Rows rows) {
-  a.n_groups = 0;
-  int32_t blocks = 0, pstride = 1;
-  auto weight = [](int kind) {
-    switch (kind) {
-      case KIND_ERF_G: case KIND_ERF_L: return 0;
-      case KIND_LSE_G: case KIND_LSE_L: case KIND_LSE_G1: case KIND_LSE_L1:
-      case KIND_LSE_GW: case KIND_LSE_LW: case KIND_LSE_GW1: case KIND_LSE_LW1: return 1;
-      case KIND_LAT: return 2;
-      default: return 3;
-    }
-  };
-  for (int pass = 0; pass < 4; ++pass) {
-    for (int j = 0; j < n_slots;) {
-      int k = j;
-      while (k < n_slots && kinds[k] == kinds[j]) ++k;
-      if (weight(kinds[j]) != pass) { j = k; continue; }
-      if (a.n_groups == kMaxGroups) return -1;
-      const int g = a.n_groups++;
-      const int64_t tc = tile_cands(kinds[j]);
-      const int32_t nt = (int32_t)((std::max<int64_t>(cn, 0) + tc - 1) / tc);
-      a.grp_kind[g] = kinds[j];
-      a.grp_slot0[g] = j;
-      a.grp_slots[g] = k - j;
-      a.grp_tiles[g] = nt;
-      a.grp_block0[g] = blocks;
-      blocks += nt * std::min<int32_t>(k - j, rows(j, k));
-      pstride = std::max(pstride, nt);
-      j = k;
-    }
-  }
-  a.grp_block0[a.n_groups] = blocks;
-  return pstride;
-}
-int32_t set_score_groups(ScoreArgs &a, const int *kinds, int n_slots, int64_t cn) {
-  return set_score_groups(a, kinds, n_slots, cn, [](int b, int e) { return e - b; });
-}
-
-// The most hps of hps[b, e) active together in one suggestion: the
-// unconditional ones, plus, for every condition parent, the most hps that
-// share one of its branch values.  (A parent takes one value per suggestion
-// and an active hp has a true condition: charge it to that condition's
-// parent; the hps charged to a parent share the branch it took.)
-int32_t active_bound(const tpe_plan *p, const int32_t *hps, int b, int e) {
-  int32_t n = 0;
-  std::vector<std::pair<int32_t, int32_t>> pb;  // (parent, branch) of every condition
-  for (int i = b; i < e; ++i) {
-    const tpe_hp &x = p->hps[hps[i]];
-    if (x.cond_count == 0) { ++n; continue; }
-    std::vector<std::pair<int32_t, int32_t>> mine;
-    for (int c = 0; c < x.cond_count; ++c)
-      mine.emplace_back(p->cond_parent[x.cond_begin + c], p->cond_branch[x.cond_begin + c]);
-    std::sort(mine.begin(), mine.end());
-    mine.erase(std::unique(mine.begin(), mine.end()), mine.end());
-    pb.insert(pb.end(), mine.begin(), mine.end());
-  }
-  std::sort(pb.begin(), pb.end());
-  for (size_t i = 0; i < pb.size();) {
-    int32_t best = 0;
-    size_t j = i;
-    while (j < pb.size() && pb[j].first == pb[i].first) {
-      size_t k = j;
-      while (k < pb.size() && pb[k] == pb[j]) ++k;
-      best = std::max<int32_t>(best, (int32_t)(k - j));
-      j = k;
-    }
-    n += best;
-    i = j;
-  }
-  return std::min<int32_t>(n, e - b);
-}
-
-void copy_groups(ScoreArgs &a, const ScoreArgs &g) {
+// a launch's scoring grid (score_grid, tpe_level_plan.hpp) into its arguments
+void copy_groups(ScoreArgs &a, const ScoreGrid &g) {
   a.n_groups = g.n_groups;
-  a.compact = g.compact;
+  a.pstride = g.pstride;
   for (int i = 0; i < kMaxGroups; ++i) {
     a.grp_slots[i] = g.grp_slots[i];
     a.grp_kind[i] = g.grp_kind[i];
@@ -732,13 +524,6 @@ int ensure_cand(tpe_engine *h, tpe_plan *p, size_t n) {
     p->cand_cap = n;
   }
   return TPE_OK;
-}
-
-// Pairs a scoring launch evaluates if every hp of the group is active: uses
-// the host copy of the mixture sizes refreshed by tpe_plan_profile_read.
-double group_pairs(tpe_plan *p, int kind, int32_t n_slots, int64_t cn, int64_t n_sug) {
-  (void)p; (void)kind; (void)n_slots;
-  return (double)cn * (double)n_sug;  // x (K_b + K_a) applied at read time
 }
 
 ScoreArgs base_args(tpe_plan *p, int64_t n_sug) {
@@ -769,53 +554,37 @@ ScoreArgs base_args(tpe_plan *p, int64_t n_sug) {
   a.lat = p->d_lat;
   a.lse_mom = p->mom_w;
   a.lse_momh = p->mom_w == 16 && p->mom_h ? 1 : 0;
-  a.l2_warm = l2_warm_on() ? 1 : 0;
-  a.lse_tight = tighten_on() ? 1 : 0;
+  // (round 2's L2 warm-up is off since round 6: the same-box A/B gave config 4
+  // 127.3 -> 124.2 ms and config 5 543 -> 536 ms per step without it -- the
+  // waves' first envelope reads waited on those loads, and the tables are
+  // L2-resident after the first blocks anyway; the wave tiles always tighten
+  // the skip threshold from the block of the highest bound)
+  a.l2_warm = 0;
+  a.lse_tight = 1;
   a.tab_hdr = p->d_tab_hdr;
   a.tab = p->d_tab;
   a.tab_max = p->d_tab_max;
   a.tab_wmax = p->d_tab_wmax;
   a.tie_list = p->d_tie_list;
   a.tie_cnt = p->d_tie_cnt;
-  a.tab_tie = table_tie();
+  a.tab_tie = switches().table_tie();
   a.tab_bound = p->d_tab_bound;
   a.tab_hot = p->d_tab_hot;
   return a;
 }
 
-// The moment width of the plan's log-sum-exp mixtures (tpe_internal.hpp
-// CoefM8): 16 when the largest expected above-side mixture (history length
-// x the hp's expected activity) has >= kMom16MinK components (neighbour gaps
-// << sigma floor: 16-component chunks qualify), 8 from the one-exponent size
-// (lse_shift_min) up, else 0.  (tools/moment_error.py: at N = 5000 the 16-wide
-// form covers 72 % of the live chunks at 0.6 VALU per pair, the 8-wide 99 %
-// at ~1.7; at N = 3000, 36 % against 98 %.)  A function of the plan and its
-// history length only, so tpe_plan_fit and fit_suggest write the same table.
-// TPE_MOM16_MIN_K: the 16-wide threshold (A/B; default kMom16MinK)
-static double mom16_min_k() {
-  static const double v = [] {
-    const char *e = std::getenv("TPE_MOM16_MIN_K");
-    return e ? std::atof(e) : (double)kMom16MinK;
-  }();
-  return v;
-}
-int32_t mom_width(const tpe_plan *p) {
-  if (!moment_on()) return 0;
-  double kmax = 0.0;
-  for (int i = 0; i < p->P; ++i) {
-    const int k = score_kind(p->hps[i]);
-    if (k == KIND_LSE_G || k == KIND_LSE_L) kmax = std::max(kmax, (double)p->n * p->act_frac[i]);
-  }
-  if (kmax >= mom16_min_k()) return 16;
-  if (kmax >= (double)lse_shift_min()) return 8;
-  return 0;
+// the fit variant a call takes (fit_variant, tpe_level_plan.hpp)
+FitVariant plan_fit_variant(const tpe_plan *p, bool moments) {
+  return fit_variant(*p, switches(), p->n, fit_small(p->n), moments);
 }
 
-// mom: write the moment table of the plan's width (mom_width) -- only the
-// wave tiles of sorted draws read it; plan.mom_w records which one the tables
-// hold (the scoring launches read that one: base_args)
-FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf, bool mom = true) {
-  p->mom_w = mom ? mom_width(p) : 0;
+// f: the step's fit variant -- its moment table is written (only the wave
+// tiles of sorted draws read it); plan.mom_w / mom_h record which tables the
+// plan holds (the scoring launches read those: base_args)
+FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf,
+                 const FitVariant &f) {
+  p->mom_w = f.mom_w;
+  p->mom_h = f.mom_h;
   p->tab_built = false;  // a new fit epoch
   FitArgs a{};
   a.hps = p->d_hps;
@@ -836,8 +605,7 @@ FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf, 
   a.coef32 = p->d_coef32;
   a.coefm = p->mom_w == 16 ? p->d_coefm : nullptr;
   a.coefm8 = p->mom_w == 8 ? p->d_coefm8 : nullptr;
-  a.coefmh = p->mom_w == 16 && moment_h_on() ? p->d_coefmh : nullptr;
-  p->mom_h = a.coefmh != nullptr;
+  a.coefmh = p->mom_h ? p->d_coefmh : nullptr;
   a.coefe = p->d_coefe;
   a.kcap = p->kcap;
   a.ob = p->d_scratch;
@@ -868,7 +636,7 @@ int table_build(tpe_engine *h, tpe_plan *p, hipStream_t st) {
   if (p->tab_built) return TPE_OK;
   CKH(launch_table_build(p->d_hps, p->P, p->d_info, p->d_coef, p->kcap, p->d_tab_hdr, p->d_tab,
                          p->census ? p->d_census : nullptr, st,
-                         table_prefilter_on() ? p->d_tab_bound : nullptr));
+                         switches().table_prefilter ? p->d_tab_bound : nullptr));
   p->tab_built = true;
   return TPE_OK;
 }
@@ -890,7 +658,7 @@ int score_launch(tpe_engine *h, tpe_plan *p, ScoreArgs a, bool has_erf, int64_t 
   }
   // (a level mixing wave-tile log-sum-exp slots with other kinds: those run
   // beside it on an auxiliary stream; the events are free at scoring time)
-  CKH(launch_score(a, has_erf, sg, side_streams_on() ? h->aux[1] : nullptr, p->ev_join[1],
+  CKH(launch_score(a, has_erf, sg, switches().side_streams ? h->aux[1] : nullptr, p->ev_join[1],
                    p->ev_join[2], classes));
   if (pr) {
     CKH(hipEventRecord(pr->b[pr->n], sg));
@@ -900,17 +668,32 @@ int score_launch(tpe_engine *h, tpe_plan *p, ScoreArgs a, bool has_erf, int64_t 
   return TPE_OK;
 }
 
+// what a call contributes to plan_level's decisions (StepShape): f: the tables
+// in place when its levels run
+StepShape step_shape(const tpe_plan *p, int64_t n_sug, int64_t n_cand, int64_t cand_begin,
+                     int64_t n_total, int32_t last_nb, const FitVariant &f) {
+  StepShape s;
+  s.n_sug = n_sug;
+  s.n_cand = n_cand;
+  s.cand_begin = cand_begin;
+  s.n_total = n_total;
+  s.below = below_class(last_nb >= 0 ? (int64_t)last_nb + 1 : p->kcap);
+  s.fit = f;
+  s.prune_mode = p->prune_mode;
+  s.lattice_on = p->lattice_on;
+  return s;
+}
+
 // One level of conditional hps: one draw(+bucket) launch and one scoring
-// launch (every lpdf kind) for all of its hps.  Candidates are processed in
-// chunks so the buffer stays <= 2 GB (chunk_budget).
-// n_total: the candidates of the whole suggestion this call scores [cand_begin,
-// cand_begin + n_cand) of (a shard's is the unsharded count): it picks the
-// wave-tile shape, so every shard and batch of one suggestion takes the same
-int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_cand,
-              int64_t cand_begin, int64_t n_total, hipStream_t st) {
-  const int32_t n_level = (int32_t)p->levels[level].size();
+// launch (every lpdf kind) for all of its hps, chunk by chunk, as
+// plan_level lays them out (tpe_level_plan.hpp): this function only executes
+// the plan -- buffers, arguments, streams, profiling brackets, launches.
+int run_level(tpe_engine *h, tpe_plan *p, int level, const StepShape &s, hipStream_t st) {
+  const LevelPlan lp = plan_level(*p, switches(), s, level);
+  const int64_t n_sug = s.n_sug;
+  const int32_t n_level = lp.n_level, n_lat = lp.n_lat;
   const int32_t *lvl = p->d_level_hps + p->level_off[level];
-  if (n_cand == 0) {
+  if (lp.empty) {
     // no candidates (an empty shard of a small suggest, n_EI_candidates = 0):
     // broadcast_best of no samples is [] (tpe.py:750-759) -- every hp of the
     // level gets the neutral record (NaN, NaN, -1, inactive), which k_merge
@@ -918,90 +701,17 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
     if (n_level > 0) CKH(launch_merge(lvl, n_level, (int32_t)n_sug, p->P, 0, nullptr, p->d_results, st));
     return TPE_OK;
   }
-  bool erf_level = false;
-  std::vector<int> kinds;
-  // largest below mixture the draw can meet: the LDS table sampler fits it?
-  int64_t kmax = p->last_nb >= 0 ? (int64_t)p->last_nb + 1 : p->kcap;
-  for (int hp : p->levels[level]) {
-    const int k = score_kind(p->hps[hp]);
-    kinds.push_back(k);
-    erf_level |= k == KIND_ERF_G || k == KIND_ERF_L;
-    if (k == KIND_CAT) kmax = std::max<int64_t>(kmax, p->hps[hp].upper);
-  }
-  const bool table_draw = kmax <= kTabCap;
-  // the level's leading quantized hps with a value lattice are scored on it
-  // (k_lattice once per call, then lookups) when no lattice is larger than
-  // the candidate count; the other quantized hps per candidate (bucketed)
-  int32_t n_lat = 0;
-  int64_t rmax = 0;
-  while (n_lat < n_level && (kinds[n_lat] == KIND_ERF_G || kinds[n_lat] == KIND_ERF_L) &&
-         p->lat[p->levels[level][n_lat]].R > 0) {
-    rmax = std::max<int64_t>(rmax, p->lat[p->levels[level][n_lat]].R);
-    ++n_lat;
-  }
-  const bool lat_level = n_lat > 0 && p->lattice_on && rmax <= n_cand * n_sug &&
-                         2 * ((p->kcap + 15) / 16) <= (int64_t)kLatChunks;
-  if (!lat_level) n_lat = 0;
-  // conditional level: grids sized for the hps that can be active together
-  // (ScoreArgs::compact), not one row per hp -- the other branches of a
-  // choice cost no blocks
-  const int32_t *hl = p->levels[level].data();
-  const int32_t lvl_rows = active_bound(p, hl, 0, n_level);
-  const bool compact = lvl_rows < n_level;
-  const int32_t slot_rows = compact ? lvl_rows : n_level;
-  const int32_t lat_rows =
-      compact ? (int32_t)std::min<int64_t>(n_lat, n_sug * (int64_t)active_bound(p, hl, 0, n_lat))
-              : n_lat;
-  const int64_t budget = chunk_budget();  // doubles
-  int64_t chunk = std::max<int64_t>(
-      1, std::min<int64_t>(std::max<int64_t>(n_cand, 1),
-                           budget / std::max<int64_t>(1, n_sug * n_level)));
-  // several chunks: each a whole number of sorted-draw blocks, so the blocks
-  // (and with them every pruned log-sum-exp) sit at the same global candidate
-  // indices however [0, n) is chunked or sharded (TPE_SHARD_ALIGN)
-  if (chunk < n_cand) chunk = std::max<int64_t>(kSortedBlock, chunk / kSortedBlock * kSortedBlock);
-  // a small one-chunk draw whose tables fit kFuseTab runs in extra blocks of
-  // the lattice launch (both only need the fitted mixtures): one launch less
-  // and the draw hidden behind the lattice points
-  const bool fuse_draw = lat_level && n_lat <= kLatJobs && table_draw &&
-                         kmax <= kFuseTab && chunk >= n_cand &&
-                         n_cand * n_sug * n_level < ((int64_t)1 << 22);
-  if (lat_level) {
-    for (int i = 0; i < n_lat; ++i) kinds[i] = KIND_LAT;
-    erf_level = false;  // per-candidate quantized slots left after the lattice ones?
-    for (int i = n_lat; i < n_level; ++i)
-      erf_level |= kinds[i] == KIND_ERF_G || kinds[i] == KIND_ERF_L;
-  }
-  // the lattice needs only the fitted mixtures: with TPE_SIDE_STREAMS=1 (and
-  // unless it carries the draw, fuse_draw) it runs on a side stream beside the
-  // candidate draw (fork / join events; a parallel branch of the captured
-  // graph), and the scoring launch waits for it.  Default: in order on the
-  // suggest stream -- round 5, config 3: 0.193 ms per suggest in order against
-  // 0.201 ms forked (the cross-stream joins cost more than the overlap saves;
-  // configs 2 and 5 unchanged, profiles/rd5h_*)
-  const bool lat_side = lat_level && !fuse_draw && side_streams_on();
-  // the lattice's readers are the lookup tiles: when those are forked beside
-  // a sorted draw (below), the lattice goes first on the same auxiliary
-  // stream -- in order before its readers, beside the draw and the
-  // log-sum-exp scoring, one join after them (lat_defer; no fork of its own)
-  bool has_other = false;
-  for (int i = 0; i < n_level; ++i) has_other |= !(kinds[i] == KIND_LAT || kinds[i] == KIND_CAT);
-  const bool sorted0 = !fuse_draw && table_draw &&
-                       std::min(chunk, n_cand) * n_sug * n_level >= ((int64_t)1 << 22);
-  const bool lk_inline = sorted0 && kmax <= kFuseTab && !p->capturing && lookup_draw_on();
-  const bool lat_defer = lat_level && !fuse_draw && !lat_side && has_other && lk_inline &&
-                         lookup_fork_on();
   ScoreArgs la = base_args(p, n_sug);
   la.level_hps = lvl;
   la.n_slots = n_level;
-  la.slot_rows = slot_rows;
-  la.compact = compact ? 1 : 0;
-  auto lattice = [&](hipStream_t sl) -> int {
+  la.slot_rows = lp.slot_rows;
+  la.compact = lp.compact ? 1 : 0;
+  // profiling bracket of the lattice launches
+  auto lat_bracket = [&](hipStream_t sl, auto launch) -> int {
     tpe_plan::Prof *pr = nullptr;
     if (p->prof_cap > 0 && p->prof[1].n < p->prof_cap) pr = &p->prof[1];
     if (pr) CKH(hipEventRecord(pr->a[pr->n], sl));
-    CKH(launch_lattice(la, p->levels[level].data(), p->hps.data(), p->lat.data(), n_lat,
-                       p->d_lat, sl, lat_rows));
+    CKH(launch());
     if (pr) {
       CKH(hipEventRecord(pr->b[pr->n], sl));
       pr->pairs[pr->n] = (double)level;
@@ -1009,8 +719,15 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
     }
     return TPE_OK;
   };
-  bool lat_pending = lat_defer;
-  if (lat_level && !fuse_draw && !lat_defer) {
+  auto lattice = [&](hipStream_t sl) -> int {
+    return lat_bracket(sl, [&] {
+      return launch_lattice(la, p->levels[level].data(), p->hps.data(), p->lat.data(), n_lat,
+                            p->d_lat, sl, lp.lat_rows);
+    });
+  };
+  const bool lat_side = lp.lat == LatRun::Side;
+  bool lat_pending = lp.lat == LatRun::Deferred;
+  if (lp.lat == LatRun::InOrder || lat_side) {
     hipStream_t sl = st;
     if (lat_side) {
       sl = h->aux[0];
@@ -1033,125 +750,40 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
     }
   }
   bool joined = !lat_side;
-  // log-sum-exp tiles: two candidate rows per lane, unless that leaves fewer
-  // than ~3 blocks per CU (then whole-block work units are few and coarse, and
-  // a CU with one more of them than its neighbours sets the launch time):
-  // one-row tiles double the count at the same per-pair arithmetic
-  {
-    int64_t lse_slots = 0;
-    for (int j = 0; j < n_level;) {  // active rows of the log-sum-exp runs
-      int k = j;
-      while (k < n_level && kinds[k] == kinds[j]) ++k;
-      if (kinds[j] == KIND_LSE_G || kinds[j] == KIND_LSE_L)
-        lse_slots += compact ? active_bound(p, hl, j, k) : k - j;
-      j = k;
-    }
-    const int64_t blocks2 = n_sug * lse_slots * ((n_cand + 127) / 128);
-    if (lse_slots > 0 && blocks2 < 3 * kNumCUs)
-      for (int &k : kinds)
-        k = k == KIND_LSE_G ? KIND_LSE_G1 : k == KIND_LSE_L ? KIND_LSE_L1 : k;
-  }
   // every exit of the chunk loop (errors included) joins the lattice side
   // stream back, so a failed call never leaves a captured graph forked
   auto chunks = [&]() -> int {
-  int64_t c0 = 0;
-  do {
-    const int64_t cn = std::min(chunk, n_cand - c0);
-    // large draws: each draw block writes its candidates value-bucketed (LSE
-    // and per-candidate erf slots) with their positions; the log-sum-exp
-    // tiles then skip the component blocks that are exact zeros for them,
-    // on wave tiles when the wave-wide exponent is on (prune mode 2)
-    const bool sorted_draw = !fuse_draw && table_draw &&
-                             cn * n_sug * n_level >= ((int64_t)1 << 22);
-    // small draws of >= kSmallSortMin candidates: the log-sum-exp slots are
-    // value-bucketed too (k_bucket, stable, <= 8192 per bucketing chunk) and
-    // pruned on the 8-wave tiles
-    bool small_sort = false;
-    if (!sorted_draw && small_sort_on() && cn >= kSmallSortMin)
-      for (int k : kinds) small_sort |= k == KIND_LSE_G || k == KIND_LSE_L || k == KIND_LSE_G1 ||
-                                        k == KIND_LSE_L1;
-    std::vector<int> ck(kinds);
-    if (sorted_draw && p->prune_mode > 1)
-      // pruned log-sum-exp slots on wave tiles: each wave its own 128
-      // candidates and every live block, so its one exponent and its accuracy
-      // guard see the whole sum.  (Round 4, config 3: 8-wave component-split
-      // tiles below 2^18 candidates measured 0.265 ms with the one-exponent
-      // form -- a wave's guard sees 1/8 of the components and 3e7 pairs per
-      // launch were retried -- and 0.236 ms without it, against 0.234 ms here.)
-      // (suggestions of <= kWaveRowSplitMax candidates: one-row wave tiles,
-      // 64 candidates per wave -- the dense windows' waves carry half the
-      // pairs; a small level leaves the GPU room for twice the waves)
-      for (int &k : ck) {
-        const bool one = n_total <= kWaveRowSplitMax;
-        k = (k == KIND_LSE_G || k == KIND_LSE_G1) ? (one ? KIND_LSE_GW1 : KIND_LSE_GW)
-          : (k == KIND_LSE_L || k == KIND_LSE_L1) ? (one ? KIND_LSE_LW1 : KIND_LSE_LW) : k;
-      }
-    else if (small_sort)
-      // one-row tiles whatever the batch size: the pruned sums depend on the
-      // tile's candidate window, so a batched suggestion stays bit-identical
-      // to the same seed's single one
-      for (int &k : ck)
-        k = k == KIND_LSE_G ? KIND_LSE_G1 : k == KIND_LSE_L ? KIND_LSE_L1 : k;
-    ScoreArgs grid{};
-    grid.compact = compact ? 1 : 0;
-    const int32_t pstride = set_score_groups(grid, ck.data(), n_level, cn, [&](int b, int e) {
-      return compact ? active_bound(p, hl, b, e) : e - b;
-    });
-    if (pstride < 0) return fail(h, TPE_E_INVALID, "level slots not grouped by lpdf kind");
-    int rc = ensure_suggest_state(h, p, n_sug, (size_t)n_sug * p->P * pstride);
+  for (const ChunkPlan &c : lp.chunks) {
+    const int64_t cn = c.cn;
+    if (c.grid.pstride < 0) return fail(h, TPE_E_INVALID, "level slots not grouped by lpdf kind");
+    int rc = ensure_suggest_state(h, p, n_sug, (size_t)n_sug * p->P * c.grid.pstride);
     if (rc) return rc;
     rc = ensure_cand(h, p, (size_t)std::max<int64_t>(1, n_sug * n_level * cn));
     if (rc) return rc;
     // buffers (re)allocated above: take their pointers only now
     ScoreArgs a = base_args(p, n_sug);
-    copy_groups(a, grid);
+    copy_groups(a, c.grid);
+    a.compact = lp.compact ? 1 : 0;
     a.cand = p->d_cand;
     a.cand_sstride = (int64_t)n_level * cn;
     a.n_cand = cn;
-    a.cand_begin = cand_begin + c0;
-    a.pstride = pstride;
-    a.accumulate = c0 > 0 ? 1 : 0;
+    a.cand_begin = s.cand_begin + c.c0;
+    a.accumulate = c.accumulate ? 1 : 0;
     a.level_hps = lvl;
     a.n_slots = n_level;
-    a.slot_rows = slot_rows;
+    a.slot_rows = lp.slot_rows;
     a.cand_slot0 = 0;
     for (int i = 0; i < kInlineSeeds && i < n_sug; ++i) a.seed_inline[i] = p->h_seeds[i];
     a.n_inline_seeds = (int32_t)std::min<int64_t>(n_sug, kInlineSeeds);
-    a.lse_pos = (sorted_draw || small_sort) ? 1 : 0;
-    a.sort_log2 = sort_log2_for(n_total);  // (the whole suggestion's: shards agree)
-    // lookup slots drawn by their scoring tiles (no write / read-back of their
-    // candidates); not in a captured graph, whose replays patch the seeds of
-    // the draw nodes only
-    // (every lookup slot's below mixture within the tile's LDS table, so all
-    // of them are drawn in their tiles and none reads the draw's output)
-    a.lookup_draw = sorted_draw && kmax <= kFuseTab && !p->capturing && lookup_draw_on() ? 1 : 0;
-    a.lse_prune = (sorted_draw || small_sort) ? p->prune_mode : 0;
-    a.lse_shift_min = lse_shift_min();
-    // prune mode 3's block-local fp32 pairs on every log-sum-exp slot of the
-    // suggest, pruned (large draws) or not (small draws: every pair, 8-wave
-    // component-split tiles)
-    a.lse_f32 = p->prune_mode == 3 ? 1 : 0;
-    // Chebyshev tables (TabHdr): suggests of > kWaveRowSplitMax candidates
-    // (n_total: shards agree) in prune mode 3 whose mixtures are in the
-    // 16-wide moment class, for the level's bounded continuous hps -- the
-    // slots whose two tables are certified go through k_score_table, and
-    // k_score_wave_tie scores directly only the waves near the best table
-    // score (TPE_TABLE=0: off)
-    {
-      bool any = false;
-      for (int i = 0; i < n_level; ++i)
-        any |= (ck[i] == KIND_LSE_GW || ck[i] == KIND_LSE_LW) && table_hp(p->hps[hl[i]]);
-      a.tab_on = any && sorted_draw && p->prune_mode == 3 && n_total > kWaveRowSplitMax &&
-                         a.lse_mom == 16 && table_on() ? 1 : 0;
-      a.tab_pref = a.tab_on && table_prefilter_on() ? 1 : 0;
-    }
-    // lookup tiles drawing their own candidates need nothing from this
-    // chunk's draw: forked onto an auxiliary stream, they run beside the draw
-    // and the log-sum-exp scoring, and st waits for them before the next
-    // chunk (TPE_LOOKUP_FORK=0: in order on st)
-    const int cls = score_classes(a);
-    const bool lk_fork = (cls & 2) && (cls & ~2) && lookup_fork_on();
-    if (lk_fork) {
+    a.lse_pos = c.lse_pos;
+    a.sort_log2 = c.sort_log2;
+    a.lookup_draw = c.lookup_draw;
+    a.lse_prune = c.lse_prune;
+    a.lse_shift_min = lp.lse_shift_min;
+    a.lse_f32 = c.lse_f32;
+    a.tab_on = c.tab_on;
+    a.tab_pref = c.tab_pref ? 1 : 0;  // (2, behind a pruning draw: once that has run)
+    if (c.lk_fork) {
       CKH(hipEventRecord(p->ev_join[3], st));
       CKH(hipStreamWaitEvent(h->aux[2], p->ev_join[3], 0));
       int lrc = TPE_OK;
@@ -1160,7 +792,7 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
         lat_pending = false;
       }
       const hipError_t el = lrc ? hipErrorUnknown
-                                : launch_score(a, erf_level, h->aux[2], nullptr, nullptr, nullptr, 2);
+                                : launch_score(a, lp.erf_level, h->aux[2], nullptr, nullptr, nullptr, 2);
       CKH(hipEventRecord(p->ev_join[4], h->aux[2]));
       if (el != hipSuccess) {
         (void)hipStreamWaitEvent(st, p->ev_join[4], 0);
@@ -1174,20 +806,10 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
     }
     // (every exit below joins the lookup stream back first)
     auto join_lk = [&]() {
-      if (lk_fork) (void)hipStreamWaitEvent(st, p->ev_join[4], 0);
+      if (c.lk_fork) (void)hipStreamWaitEvent(st, p->ev_join[4], 0);
     };
-    // tiny unsorted draws of levels with no lattice and no per-candidate erf
-    // slots: the scoring tiles draw their own candidates (k_score_tdraw) --
-    // one launch less (the config-1 shape: 24 candidates of one hp)
-    const bool tdraw = !sorted_draw && !small_sort && !fuse_draw && !lat_level && !erf_level &&
-                       table_draw && kmax <= kFuseTab && cn <= 4096 && !p->capturing &&
-                       tile_draw_on();
-    a.tile_draw = tdraw ? 1 : 0;
-    // the call's last launch (its last level, one chunk, a full grid): its
-    // last final record publishes the call's results (k_publish's work)
-    if (tdraw && p->pub_arm && level + 1 == (int)p->levels.size() && cn == n_cand &&
-        cand_begin == 0 && n_total == n_cand && !compact && !lk_fork && a.n_groups > 0 &&
-        a.grp_block0[a.n_groups] > 0 && publish_fuse_on()) {
+    a.tile_draw = c.draw == Draw::Tiles ? 1 : 0;
+    if (c.publish) {
       a.pub_dst = reinterpret_cast<uint64_t *>(p->h_results);
       a.pub_flag = p->h_flag;
       a.pub_ticket = p->d_ticket + (size_t)p->s_cap * p->P;
@@ -1196,80 +818,56 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, int64_t n_sug, int64_t n_ca
       a.pub_events = (int32_t)(n_sug * n_level);
       p->pub_fired = true;
     }
-    if (tdraw) {
-    } else if (fuse_draw) {
-      tpe_plan::Prof *pr = nullptr;
-      if (p->prof_cap > 0 && p->prof[1].n < p->prof_cap) pr = &p->prof[1];
-      if (pr) CKH(hipEventRecord(pr->a[pr->n], st));
-      CKH(launch_lattice_draw(a, p->levels[level].data(), p->hps.data(), p->lat.data(), n_lat,
-                              p->d_lat, st, lat_rows));
-      if (pr) {
-        CKH(hipEventRecord(pr->b[pr->n], st));
-        pr->pairs[pr->n] = (double)level;
-        pr->n++;
-      }
-    } else if (sorted_draw) {
-      // the inline-draw kernel when every slot it draws is bounded continuous
-      // (the lookup slots drawn in their tiles are skipped by it); kmax within
-      // the table (table_draw) holds here
-      bool fast = true;
-      for (int i = 0; i < n_level && fast; ++i) {
-        const tpe_hp &x = p->hps[p->levels[level][i]];
-        const bool lookup = ck[i] == KIND_CAT || ck[i] == KIND_LAT;
-        fast = lookup ? (a.lookup_draw != 0 && kmax <= kFuseTab)
-                      : (x.family != TPE_CAT && (x.flags & TPE_HAS_LOW) && (x.flags & TPE_HAS_HIGH));
-      }
-      // The pruning draw: behind the prefilter the hot intervals
-      // depend on the launch's first sort block alone, so that block is drawn
-      // first (today's kernel, written in full), k_table_pilot reads it -- the
-      // tables and bound lattices built ahead of it -- and the other sort
-      // blocks are drawn by the kernel that drops the wave tiles the intervals
-      // rule out.  A chunk of one sort block has nothing to prune.
-      const bool dprune = a.tab_on == 1 && a.tab_pref && (cls & 1) && draw_prune_on() &&
-                          a.sort_log2 == kSortLog2Large && cn > kSortedBlock;
-      hipError_t e;
-      if (dprune) {
-        rc = table_build(h, p, st);
-        if (rc) { join_lk(); return rc; }
-        p->tab_pstride = a.pstride;
-        e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st, 1);
-        if (e == hipSuccess) e = launch_table_pilot(a, st);
-        // the launches that take k_draw_sorted_prune<kFuseTab, true> screen their
-        // candidates on u1 first (TPE_DRAW_SCREEN=0: today's kernel)
-        // from draw_screen_min() candidate-slots up: below, k_draw_zone's ~33 us
-        // ahead of the draw cost more than the screen saves
-        if (fast && kmax <= kFuseTab && draw_screen_on() &&
-            cn * n_sug * n_level >= draw_screen_min()) {
-          if (e == hipSuccess)
-            e = launch_draw_zone(a, p->d_draw_zone, draw_screen_tiles(), kScreenMargin, st);
-          if (e == hipSuccess)
-            e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats, st);
-        } else if (e == hipSuccess) {
-          e = launch_draw_pruned(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+    switch (c.draw) {
+      case Draw::Tiles:
+        break;
+      case Draw::Fused:
+        rc = lat_bracket(st, [&] {
+          return launch_lattice_draw(a, p->levels[level].data(), p->hps.data(), p->lat.data(),
+                                     n_lat, p->d_lat, st, lp.lat_rows);
+        });
+        if (rc) return rc;
+        break;
+      case Draw::Plain:
+        CKH(launch_draw(a, c.table_draw, st));
+        break;
+      default: {  // the sorted draws
+        hipError_t e;
+        if (c.draw == Draw::Sorted) {
+          e = launch_draw_sorted(a, c.small_table, c.fast, p->d_cpos, st);
+        } else {
+          rc = table_build(h, p, st);
+          if (rc) { join_lk(); return rc; }
+          p->tab_pstride = a.pstride;
+          e = launch_draw_sorted(a, c.small_table, c.fast, p->d_cpos, st, 1);
+          if (e == hipSuccess) e = launch_table_pilot(a, st);
+          if (c.draw == Draw::SortedScreened) {
+            if (e == hipSuccess)
+              e = launch_draw_zone(a, p->d_draw_zone, c.screen_tiles, kScreenMargin, st);
+            if (e == hipSuccess)
+              e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats, st);
+          } else if (e == hipSuccess) {
+            e = launch_draw_pruned(a, c.small_table, c.fast, p->d_cpos, st);
+          }
         }
-        a.tab_pref = 2;
-      } else {
-        e = launch_draw_sorted(a, kmax <= kFuseTab, fast, p->d_cpos, st);
+        if (e != hipSuccess) { join_lk(); return fail(h, TPE_E_HIP, hipGetErrorString(e)); }
+        p->dump_cn = cn;
+        p->dump_sstride = a.cand_sstride;
+        p->dump_level = level;
+        p->dump_nsug = n_sug;
       }
-      if (e != hipSuccess) { join_lk(); return fail(h, TPE_E_HIP, hipGetErrorString(e)); }
-      p->dump_cn = cn;
-      p->dump_sstride = a.cand_sstride;
-      p->dump_level = level;
-      p->dump_nsug = n_sug;
-    } else {
-      CKH(launch_draw(a, table_draw, st));
     }
-    if ((erf_level || small_sort) && !sorted_draw) CKH(launch_bucket(a, n_lat, p->d_cpos, st));
-    a.cand_pos = (erf_level || sorted_draw || small_sort) ? p->d_cpos : nullptr;
+    a.tab_pref = c.tab_pref;
+    if (c.bucket) CKH(launch_bucket(a, n_lat, p->d_cpos, st));
+    a.cand_pos = c.cand_pos ? p->d_cpos : nullptr;
     if (!joined) {
       CKH(hipStreamWaitEvent(st, p->ev_join[0], 0));
       joined = true;
     }
-    rc = score_launch(h, p, a, erf_level, cn, st, true, lk_fork ? 5 : 7);
+    rc = score_launch(h, p, a, lp.erf_level, cn, st, true, c.classes);
     join_lk();
     if (rc) return rc;
-    c0 += cn;
-  } while (c0 < n_cand);
+  }
   return TPE_OK;
   };
   const int rc = chunks();
@@ -1306,9 +904,9 @@ int run_external(tpe_engine *h, tpe_plan *p, int32_t hp, const double *ext, int6
       if (!(t.P > 0 && t.ncert == (uint32_t)t.P))
         return fail(h, TPE_E_INVALID, "Chebyshev table not certified");
   }
-  ScoreArgs grid{};
-  const int32_t pstride = set_score_groups(grid, &kind, 1, n);
-  int rc = ensure_suggest_state(h, p, 1, (size_t)p->P * pstride);
+  const ScoreGrid grid =
+      score_grid([&](int) { return kind; }, 1, n, [](int b, int e) { return e - b; });
+  int rc = ensure_suggest_state(h, p, 1, (size_t)p->P * grid.pstride);
   if (rc) return rc;
   if (sorted) {
     rc = ensure_cand(h, p, (size_t)std::max<int64_t>(1, n));
@@ -1319,7 +917,6 @@ int run_external(tpe_engine *h, tpe_plan *p, int32_t hp, const double *ext, int6
   a.cand = ext;
   a.cand_sstride = n;
   a.n_cand = n;
-  a.pstride = pstride;
   a.level_hps = p->d_all_hps + hp;
   a.n_slots = 1;
   a.slot_rows = 1;
@@ -1333,7 +930,7 @@ int run_external(tpe_engine *h, tpe_plan *p, int32_t hp, const double *ext, int6
     a.cand_pos = p->d_cpos;
     a.lse_pos = 1;
     a.lse_prune = sorted_mode;
-    a.lse_shift_min = lse_shift_min();
+    a.lse_shift_min = (int32_t)switches().lse_shift_min;
     a.tab_on = tab ? 2 : 0;
   }
   return score_launch(h, p, a, kind == KIND_ERF_G || kind == KIND_ERF_L, n, st, false);
@@ -1357,7 +954,7 @@ int copy_results(tpe_engine *h, tpe_plan *p, int64_t n_sug, tpe_result *out, int
   // directly and the host reads them without a runtime copy)
   const int rc = host_results(h, p, n_sug);
   if (rc) return rc;
-  if (!publish_on()) {
+  if (!switches().publish) {
     CKH(hipMemcpyAsync(p->h_results, p->d_results, bytes, hipMemcpyDeviceToHost, st));
     CKH(hipStreamSynchronize(st));
     std::memcpy(out, p->h_results, bytes);
@@ -1405,7 +1002,7 @@ int host_results(tpe_engine *h, tpe_plan *p, int64_t n_sug) {
     CKH(hipHostMalloc((void **)&p->h_results, cap, hipHostMallocCoherent | hipHostMallocMapped));
     p->h_results_cap = cap;
   }
-  if (publish_on() && !p->h_flag) {
+  if (switches().publish && !p->h_flag) {
     CKH(hipHostMalloc((void **)&p->h_flag, 64, hipHostMallocCoherent | hipHostMallocMapped));
     __atomic_store_n(p->h_flag, (uint64_t)0, __ATOMIC_RELEASE);
   }
@@ -1538,7 +1135,8 @@ int tpe_split(tpe_handle_t h, const double *losses, int64_t n, double gamma,
   const int32_t nb = (int32_t)std::min<double>(std::ceil(gamma * std::sqrt((double)n)), gamma_cap);
   CKH(hipMemcpyAsync(p->d_losses, losses, n * 8, hipMemcpyHostToDevice, h->stream));
   p->n = n;
-  CKH(launch_split(fit_args(p, std::max(nb, 0), 1.0, 25), p->d_below, h->stream));
+  CKH(launch_split(fit_args(p, std::max(nb, 0), 1.0, 25, plan_fit_variant(p, true)), p->d_below,
+                   h->stream));
   CKH(hipMemcpyAsync(below_mask, p->d_below, n, hipMemcpyDeviceToHost, h->stream));
   CKH(hipStreamSynchronize(h->stream));
   return TPE_OK;
@@ -1566,7 +1164,8 @@ static int fit_one(tpe_handle_t h, int32_t family, const double *obs, int64_t n,
   }
   if (n > 0) CKH(hipMemsetAsync(p->d_losses, 0, n * 8, h->stream));
   p->n = n;
-  CKH(launch_fit(fit_args(p, (int32_t)n, prior_weight, lf), 1, h->stream));
+  CKH(launch_fit(fit_args(p, (int32_t)n, prior_weight, lf, plan_fit_variant(p, true)), 1,
+                 h->stream));
   *pout = p;
   return TPE_OK;
 }
@@ -1648,7 +1247,7 @@ int tpe_score(tpe_handle_t h, int32_t family, const double *x, int64_t n, const 
   if (rc) return rc;
   CKH(launch_prep(p->d_hps, 1, p->d_mw, p->d_mmu, p->d_msig, p->d_info, p->d_coef, p->d_coef32,
                   p->d_coefm, nullptr, p->d_coefe, p->kcap, p->d_scratch, h->stream));
-  p->mom_w = moment_on() ? 16 : 0;
+  p->mom_w = switches().moment ? 16 : 0;
   p->mom_h = false;
   rc = ensure_ext(h, p, n);
   if (rc) return rc;
@@ -1698,7 +1297,7 @@ int tpe_sample(tpe_handle_t h, int32_t family, const double *w, const double *mu
   if (rc) return rc;
   CKH(launch_prep(p->d_hps, 1, p->d_mw, p->d_mmu, p->d_msig, p->d_info, p->d_coef, p->d_coef32,
                   p->d_coefm, nullptr, p->d_coefe, p->kcap, p->d_scratch, h->stream));
-  p->mom_w = moment_on() ? 16 : 0;
+  p->mom_w = switches().moment ? 16 : 0;
   p->mom_h = false;
   rc = ensure_ext(h, p, n);
   if (rc) return rc;
@@ -1785,8 +1384,6 @@ int tpe_plan_update_history(tpe_plan_t p, int64_t n, int64_t row0, int64_t n_row
       }
     for (int64_t i = 0; i < n_loss; ++i) hp.losses[i] = losses[i];
     p->has_pend = n_rows > 0 || n_loss > 0;
-    if (p->has_pend && !patch_defer_on()) rc = flush_patch(h, p, st);
-    if (rc) return rc;
     p->n = n;
     return TPE_OK;
   }
@@ -1816,7 +1413,8 @@ int tpe_plan_fit(tpe_plan_t p, double gamma, int32_t gamma_cap, double prior_wei
   hipStream_t st = pick_stream(h, stream);
   const double nbf = std::ceil(gamma * std::sqrt((double)p->n));
   const int32_t nb = (int32_t)std::max(0.0, std::min<double>(nbf, gamma_cap));
-  const int rc = fit_launch(h, p, fit_args(p, nb, prior_weight, lf, true), p->P, st);
+  const FitVariant f = plan_fit_variant(p, true);
+  const int rc = fit_launch(h, p, fit_args(p, nb, prior_weight, lf, f), p->P, st);
   if (rc) return rc;
   p->last_nb = nb;
   return TPE_OK;
@@ -1897,8 +1495,11 @@ int tpe_plan_suggest_shard(tpe_plan_t p, const uint64_t *seeds, int64_t n_sug, i
   if (p->prof_cap > 0) CKH(hipEventRecord(p->ev0, st));
   const int l0 = level < 0 ? 0 : level;
   const int l1 = level < 0 ? (int)p->levels.size() : level + 1;
+  // (the tables of the plan's last fit are the ones in place)
+  const StepShape s = step_shape(p, n_sug, n_cand, cand_begin, n_total, p->last_nb,
+                                 FitVariant{fit_small(p->n), p->mom_w, p->mom_h});
   for (int l = l0; l < l1; ++l) {
-    rc = run_level(h, p, l, n_sug, n_cand, cand_begin, n_total, st);
+    rc = run_level(h, p, l, s, st);
     if (rc) return rc;
   }
   if (p->prof_cap > 0) CKH(hipEventRecord(p->ev1, st));
@@ -1914,38 +1515,28 @@ int tpe_plan_suggest_shard(tpe_plan_t p, const uint64_t *seeds, int64_t n_sug, i
 namespace {
 
 // enqueue fit + every level's suggest on st (eager or under capture)
+// s: the step's shape (tpe_plan_fit_suggest), its fit variant included
 int enqueue_step(tpe_engine *h, tpe_plan *p, int32_t nb, double prior_weight, int32_t lf,
-                 int64_t n_sug, int64_t n_cand, hipStream_t st) {
-  // the moment table only for a step whose suggest takes a sorted draw
-  // (run_level's sorted_draw: n_cand x n_sug x level hps >= 2^22) on two-row
-  // wave tiles (> kWaveRowSplitMax candidates per suggestion), the only
-  // launches that read it; the others skip its ~3-5 us in k_fit.  Whenever it
-  // is read, the table is the one tpe_plan_fit writes (mom_width), so a
-  // fit_suggest and a fit + suggest score alike (test_fit_suggest_matches_*)
-  bool sorted = false;
-  for (const auto &l : p->levels)
-    sorted |= n_cand * n_sug * (int64_t)l.size() >= ((int64_t)1 << 22);
+                 const StepShape &s, hipStream_t st) {
   {
-    const bool mom = sorted && n_cand > kWaveRowSplitMax;
-    const int rc = fit_launch(h, p, fit_args(p, nb, prior_weight, lf, mom), p->P, st);
+    const int rc = fit_launch(h, p, fit_args(p, nb, prior_weight, lf, s.fit), p->P, st);
     if (rc) return rc;
   }
   p->last_nb = nb;
   for (int l = 0; l < (int)p->levels.size(); ++l) {
-    const int rc = run_level(h, p, l, n_sug, n_cand, 0, n_cand, st);
+    const int rc = run_level(h, p, l, s, st);
     if (rc) return rc;
   }
   return TPE_OK;
 }
 
-// capture the step, instantiate it and find the nodes patched per call
+// capture the step (s: its shape, capturing), instantiate it and find the
+// nodes patched per call
 int capture_step(tpe_engine *h, tpe_plan *p, int32_t nb, double prior_weight, int32_t lf,
-                 int64_t n_sug, int64_t n_cand, hipStream_t st) {
+                 const StepShape &s, hipStream_t st) {
   graph_reset(p);
   CKH(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  p->capturing = true;
-  const int rc = enqueue_step(h, p, nb, prior_weight, lf, n_sug, n_cand, st);
-  p->capturing = false;
+  const int rc = enqueue_step(h, p, nb, prior_weight, lf, s, st);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(st, &g);
   if (rc || ec != hipSuccess || !g) {
@@ -2048,30 +1639,19 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
   hipStream_t st = pick_stream(h, stream);
   const double nbf = std::ceil(gamma * std::sqrt((double)p->n));
   const int32_t nb = (int32_t)std::max(0.0, std::min<double>(nbf, gamma_cap));
-  // Graph replay is opt-in (TPE_GRAPH=1): on the measured ROCm 7 / MI355X
-  // stack a replayed graph starts ~18 us after the previous one, against
-  // back-to-back eager launches of one call (tools/host_cost.py).
-  static const bool use_graph = std::getenv("TPE_GRAPH") != nullptr;
-  const bool graphable = use_graph && n_sug <= kInlineSeeds && p->prof_cap == 0 && !p->census;
+  // (graph replay is opt-in: Switches::graph)
+  const bool graphable =
+      switches().graph && n_sug <= kInlineSeeds && p->prof_cap == 0 && !p->census;
+  // the step's shape, built once: run_level plans every launch from it, and
+  // with `capturing` set it is the key of the captured graph
+  StepShape shape = step_shape(p, n_sug, n_cand, 0, n_cand, nb,
+                               plan_fit_variant(p, step_reads_moments(*p, n_sug, n_cand)));
   tpe_plan::StepKey key;
   key.prior_weight = prior_weight;
   key.lf = lf;
-  key.n_sug = n_sug;
-  key.n_cand = n_cand;
   key.stream = (void *)st;
-  key.table = (int64_t)nb + 1 <= kTabCap;
-  key.fuse = (int64_t)nb + 1 <= kFuseTab;
-  key.small = fit_small(p->n);
-  {
-    bool sorted = false;  // (enqueue_step's condition for the moment table)
-    for (const auto &l : p->levels)
-      sorted |= n_cand * n_sug * (int64_t)l.size() >= ((int64_t)1 << 22);
-    key.mom_w = sorted && n_cand > kWaveRowSplitMax ? mom_width(p) : 0;
-    key.tab = key.mom_w == 16 && p->prune_mode == 3 && table_on();
-    key.pref = key.tab && table_prefilter_on();
-    key.dprune = key.pref && draw_prune_on();
-    key.dscreen = key.dprune && draw_screen_on() ? draw_screen_tiles() : -1;
-  }
+  key.shape = shape;
+  key.shape.capturing = true;
   int rc = ensure_suggest_state(h, p, n_sug, 1);
   if (rc) return rc;
   p->h_seeds.assign(seeds, seeds + n_sug);
@@ -2087,13 +1667,12 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
     // results to the host: the step's last launch may publish them itself
     // (run_level, tile_draw levels), with the pinned buffers in place first
     p->pub_fired = false;
-    p->pub_arm = out && !out_on_device && publish_on() && p->prof_cap == 0 && !p->census;
-    if (p->pub_arm) {
+    shape.publish = out && !out_on_device && switches().publish && p->prof_cap == 0 && !p->census;
+    if (shape.publish) {
       rc = host_results(h, p, n_sug);
-      if (rc) { p->pub_arm = false; return rc; }
+      if (rc) return rc;
     }
-    rc = enqueue_step(h, p, nb, prior_weight, lf, n_sug, n_cand, st);
-    p->pub_arm = false;
+    rc = enqueue_step(h, p, nb, prior_weight, lf, shape, st);
     if (rc) {
       // (a publishing launch that went out counts its arrivals: clear the
       // ticket for the plan's next fused publish)
@@ -2109,7 +1688,7 @@ int tpe_plan_fit_suggest(tpe_plan_t p, double gamma, int32_t gamma_cap, double p
     }
   } else {
     if (!(p->graph_ok && p->graph_key == key)) {
-      rc = capture_step(h, p, nb, prior_weight, lf, n_sug, n_cand, st);
+      rc = capture_step(h, p, nb, prior_weight, lf, key.shape, st);
       if (rc) return rc;
       p->graph_key = key;
     }
@@ -2361,7 +1940,7 @@ int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out) {
   tpe_engine *h = p->eng;
   if (hp < 0 || hp >= p->P) return fail(h, TPE_E_INVALID, "bad args");
   if (!table_hp(p->hps[hp])) return fail(h, TPE_E_INVALID, "hp has no Chebyshev table");
-  if (!table_prefilter_on()) return fail(h, TPE_E_INVALID, "no bound lattice: the prefilter is off");
+  if (!switches().table_prefilter) return fail(h, TPE_E_INVALID, "no bound lattice: the prefilter is off");
   CKH(hipSetDevice(h->device));
   CKH(hipDeviceSynchronize());
   const int rc = table_build(h, p, h->stream);  // (this fit epoch's, if no launch has built them)
@@ -2561,135 +2140,6 @@ int tpe_plan_anneal_trace(tpe_plan_t p, int32_t n_suggest, tpe_anneal_trace *out
     CKH(hipMemcpy(out, p->d_an_trace, (size_t)n_suggest * p->P * sizeof(AnnealTrace),
                   hipMemcpyDeviceToHost));
   return TPE_OK;
-}
-
-// value-bucketed, pruned log-sum-exp slots on small draws: opt-in
-// (TPE_SMALL_SORT=1, test_gpu_suggest.py).  Measured at config 2 (4096
-// candidates): the skip drops 80 % of the pairs and k_score from 33 to 23 us,
-// but the extra k_bucket launch costs more than that (suggest 70 -> 78 us)
-static bool small_sort_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_SMALL_SORT");
-    return e && std::atoi(e) != 0;
-  }();
-  return v;
-}
-
-// the moment form of equal-sigma 16-component chunks in prune mode 3
-// (CoefM; TPE_MOMENT=0 switches it off: A/B and the parity tests' child
-// processes)
-static bool moment_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_MOMENT");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return v;
-}
-
-// large draws scored from certified Chebyshev tables of both mixtures
-// (k_table_build / k_score_table; TPE_TABLE=0 switches them off: A/B and the
-// parity tests' child processes)
-static bool table_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_TABLE");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return v;
-}
-
-// the tie window of the direct pass behind the tables: a wave is scored again
-// when its best table score is within 2^TPE_TABLE_TIE_LOG2 max(1, |best|) of
-// the slot's (default -16, kTabTie; a huge value makes every wave hot: tests)
-static double table_tie() {
-  static const double v = [] {
-    const char *e = std::getenv("TPE_TABLE_TIE_LOG2");
-    return e ? std::ldexp(1.0, (int)std::max(-1074L, std::min(4096L, std::atol(e)))) : kTabTie;
-  }();
-  return v;
-}
-
-// the table pass behind the prefilter: wave tiles that a certified bound of
-// the table score rules out are not scored (k_table_bound / k_table_pilot;
-// TPE_TABLE_PREFILTER=0 switches it off: same-binary A/B and the tests' child
-// processes)
-// the sorted draw behind the prefilter drops the wave tiles the hot intervals
-// rule out before ranking or writing them (k_draw_sorted_prune;
-// TPE_DRAW_PRUNE=0 restores the full draw: same-binary A/B and the tests'
-// child processes)
-static bool draw_prune_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_DRAW_PRUNE");
-    return !(e && *e && std::atoi(e) == 0);
-  }();
-  return v;
-}
-
-// the pruning draw screens its candidates on (component, u1) and inverts only
-// the ones near a hot interval (k_draw_zone, k_draw_sorted_screen;
-// TPE_DRAW_SCREEN=0 restores k_draw_sorted_prune: same-binary A/B and the
-// tests' child processes)
-static bool draw_screen_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_DRAW_SCREEN");
-    return !(e && *e && std::atoi(e) == 0);
-  }();
-  return v;
-}
-// the zones' widening beyond a hot interval, in pilot wave tiles per side
-// (TPE_DRAW_SCREEN_TILES; DESIGN 7: the sweep behind the default)
-static int32_t draw_screen_tiles() {
-  static const int32_t v = [] {
-    const char *e = std::getenv("TPE_DRAW_SCREEN_TILES");
-    return e && *e ? std::max(0, std::min(kPilotWaves, std::atoi(e))) : 2;
-  }();
-  return v;
-}
-
-// the smallest launch (candidates x suggestions x slots) the screen takes: it
-// saves ~1.4 us per 2^20 candidate-slots on an MI355X, k_draw_zone costs ~33 us
-// (TPE_DRAW_SCREEN_MIN overrides: the tests' small launches)
-static int64_t draw_screen_min() {
-  static const int64_t v = [] {
-    const char *e = std::getenv("TPE_DRAW_SCREEN_MIN");
-    return e && *e ? (int64_t)std::atoll(e) : (int64_t)1 << 26;
-  }();
-  return v;
-}
-
-static bool table_prefilter_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_TABLE_PREFILTER");
-    return !(e && *e && std::atoi(e) == 0);
-  }();
-  return v;
-}
-
-// candidate buffer per scoring chunk, in doubles (TPE_CHUNK_MB overrides, A/B)
-static int64_t chunk_budget() {
-  static const int64_t v = [] {
-    const char *e = std::getenv("TPE_CHUNK_MB");
-    // MB -> doubles.  8 GB (+ 4 GB of positions): config 4's 1e9 candidates
-    // of a level in one draw + one scoring launch, config 5's 32-suggestion
-    // calls in one chunk -- each launch's tail paid once (config 4 79.3 ->
-    // 78.8 ms, config 5 461.3 -> 454.4 ms per step against 2 GB,
-    // profiles/rd6/r6_46; 2 GB had been 1-2 % faster than 512 MB)
-    return (e ? std::atoll(e) : 8192) << 17;
-  }();
-  return v;
-}
-
-// smallest mixture (components) scored in the one-exponent form on pruned
-// tiles; smaller ones keep the per-group lift (TPE_SHIFT_MIN_K overrides:
-// A/B and tests).  Round 4: 2048 -> 512 -- config 5 (K_a = 993) 997 -> 885
-// ms per 1024-suggestion step, config 3 (K_a ~ 1.4e3) 0.266 -> 0.255 ms;
-// below ~128 components (the good-side mixtures) the guard's second attempt
-// costs more than the lift saves (0: config 5 905 ms)
-static int lse_shift_min() {
-  static const int v = [] {
-    const char *e = std::getenv("TPE_SHIFT_MIN_K");
-    return e ? std::atoi(e) : 512;
-  }();
-  return v;
 }
 
 int tpe_plan_set_prune(tpe_plan_t p, int32_t mode) {

@@ -211,7 +211,7 @@ __host__ __device__ constexpr int64_t mom_stride(int64_t kcap) {
 // chunk spans too much of sigma for the degree-9 bound (xh ~ 7.5, almost no
 // chunk qualifies), while 8 components at degree 15 cover ~60-90 % of the
 // live blocks (tools/moment_error.py MOM_CH=8 MOM_P=15: 1.0e-7 max relative
-// lpdf error against the oracle).  The per-plan width (tpe_engine.hip
+// lpdf error against the oracle).  The per-plan width (tpe_level_plan.hpp
 // mom_width): 16 for mixtures of >= kMom16MinK components, else 8 from the
 // one-exponent size up; the scoring kernels are instantiated per width, so the
 // 16-wide kernel's register allocation is the round-5 one.  A block of 8 is
@@ -346,7 +346,7 @@ struct ScoreArgs {
   int32_t n_hp;
   int32_t n_slots;            // hps of this launch
   int32_t n_suggest;         // grid.y
-  // scoring grid: kind groups of consecutive slots (set_score_groups)
+  // scoring grid: kind groups of consecutive slots (score_grid, tpe_level_plan.hpp)
   int32_t n_groups;
   int32_t grp_kind[kMaxGroups];
   int32_t grp_slot0[kMaxGroups];
@@ -379,7 +379,7 @@ struct ScoreArgs {
   int64_t lookup_seg;        // candidates per lookup-scan block (set by the lookup launch)
   int32_t l2_warm;           // scoring tiles touch their mixtures' coefficient lines first
   int32_t lse_tight;         // wave tiles tighten the skip threshold from the top block (default 1)
-                             // (one load per 128-B line; TPE_L2_WARM=1, A/B; default off)
+                             // (one load per 128-B line; the host always passes 0)
   int32_t tile_draw;         // tiny unsorted draws: every tile draws its own candidates
                              // (k_score_tdraw; no k_draw launch, nothing written)
   const LatInfo *lat_info;   // [P] value lattices (KIND_LAT slots)

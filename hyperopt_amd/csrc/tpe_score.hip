@@ -33,6 +33,7 @@
 
 #include "tpe_device.hpp"
 #include "tpe_draw.hpp"
+#include "tpe_switches.hpp"
 
 namespace tpe {
 
@@ -3522,29 +3523,15 @@ static ScoreArgs select_groups(const ScoreArgs &a, int cls) {
   return b;
 }
 
-// k_score_wave_tie's persistent blocks per CU (TPE_TIE_BLOCKS: A/B; read once).
-// Config 4, ms per step at 4 / 6 / 8 / 12 / 16 / 32: 26.86 / 26.52 / 26.44 /
-// 26.33 / 26.29 / 26.29, two rounds within 0.07 ms of each other
-// (profiles/tiegather_blocks_sweep.txt)
-static int tie_blocks_per_cu() {
-  static const int v = [] {
-    const char *e = std::getenv("TPE_TIE_BLOCKS");
-    const int n = e ? std::atoi(e) : 0;
-    return n >= 1 && n <= 64 ? n : 16;
-  }();
-  return v;
-}
+// k_score_wave_tie's persistent blocks per CU.  Config 4, ms per step at
+// 4 / 6 / 8 / 12 / 16 / 32: 26.86 / 26.52 / 26.44 / 26.33 / 26.29 / 26.29, two
+// rounds within 0.07 ms of each other (profiles/tiegather_blocks_sweep.txt)
+constexpr int kTieBlocksPerCu = 16;
 
-// The table kernels' form (TPE_TABLE_SCALAR: A/B; read once): the scalar-panel
-// tab_eval -- k_table_map and k_score_table<., false, true> -- unless 0, which
+// The table kernels' form (Switches::table_scalar, A/B): the scalar-panel
+// tab_eval -- k_table_map and k_score_table<., false, true> -- unless off, which
 // takes the per-lane kernels k_score_table<., true> and k_score_table<.>.
-static bool table_scalar_on() {
-  static const bool v = [] {
-    const char *e = std::getenv("TPE_TABLE_SCALAR");
-    return !(e && *e && std::atoi(e) == 0);
-  }();
-  return v;
-}
+static bool table_scalar_on() { return switches().table_scalar; }
 
 // one launch of a single class's groups
 static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStream_t st) {
@@ -3609,10 +3596,10 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
         else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
       }
       k_tie_gather<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
-      // persistent blocks per slot: ~tie_blocks_per_cu() blocks per CU over
+      // persistent blocks per slot: ~kTieBlocksPerCu blocks per CU over
       // the launch's (row, suggestion) pairs, so that a single all-hot slot
       // still fills the chip; never more than the slot has tiles
-      const int64_t per = ((int64_t)tie_blocks_per_cu() * kNumCUs + (int64_t)rows * a.n_suggest - 1) /
+      const int64_t per = ((int64_t)kTieBlocksPerCu * kNumCUs + (int64_t)rows * a.n_suggest - 1) /
                           ((int64_t)rows * a.n_suggest);
       const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntmax, per));
       const dim3 gt(G, (unsigned)rows, a.n_suggest);

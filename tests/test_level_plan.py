@@ -1,0 +1,28 @@
+"""The launch plan of a level (hyperopt_amd/csrc/tpe_level_plan.hpp) and the
+switch table (tpe_switches.hpp) are pure host code: tests/host/level_plan_check.cpp
+builds compiled-space descriptions by hand and checks the plans against values
+written out from the documented rules.  Built host-only with the address and
+undefined-behaviour sanitizers and run as a stand-alone program (no GPU)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+
+
+def test_level_plan_host_checks(tmp_path):
+    if not os.path.exists(HIPCC):
+        pytest.fail('hipcc not found at %s' % HIPCC)
+    exe = str(tmp_path / 'level_plan_check')
+    src = os.path.join(ROOT, 'tests', 'host', 'level_plan_check.cpp')
+    cc = subprocess.run(
+        [HIPCC, '-x', 'hip', '--cuda-host-only', '-std=c++17', '-O1', '-g', '-Wall',
+         '-Xarch_host', '-fsanitize=address,undefined',
+         '-Xarch_host', '-fno-sanitize-recover=undefined', src, '-o', exe],
+        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+    assert cc.returncode == 0, cc.stdout
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       universal_newlines=True)
+    assert r.returncode == 0, r.stdout
