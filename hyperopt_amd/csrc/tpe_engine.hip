@@ -843,9 +843,11 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, const StepShape &s, hipStre
           if (e == hipSuccess) e = launch_table_pilot(a, st);
           if (c.draw == Draw::SortedScreened) {
             if (e == hipSuccess)
-              e = launch_draw_zone(a, p->d_draw_zone, c.screen_tiles, kScreenMargin, st);
+              e = launch_draw_zone(a, p->d_draw_zone, c.screen_tiles, kScreenMargin, c.screen_guide,
+                                   st);
             if (e == hipSuccess)
-              e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats, st);
+              e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats,
+                                       c.screen_guide >= 0, st);
           } else if (e == hipSuccess) {
             e = launch_draw_pruned(a, c.small_table, c.fast, p->d_cpos, st);
           }

@@ -559,24 +559,39 @@ constexpr int kZoneEdges = 2 * kZoneMax - 2;  // interior edges: two per gap bet
 // |draw_bounded_invert's x - the true quantile| / sigma measured over the tail
 // probabilities the screen covers (tools/table_error.py --erfcinv)
 constexpr double kScreenMargin = 1.6e-5;
+constexpr int kGuideBitsMax = 10;  // the pick guide's buckets: at most 2^10
 struct __attribute__((aligned(16))) DrawZone {
   int32_t nz;                    // zones in use (0: do not screen the slot)
-  int32_t pad;
+  int32_t gbits;                 // the integer form's guide bits (unused by the float screen)
   double gap_lo[kZoneMax - 1];   // gap g: the upper edge of zone g ...
   double gap_hi[kZoneMax - 1];   // ... and the lower edge of zone g + 1
   // component k's draw lies strictly inside gap g iff thr[k][2g] <= u1 < thr[k][2g + 1]
   // (nondecreasing in the edge; all 1: the component is always inverted)
   double thr[kFuseTab][kZoneEdges];
+  // The integer form (k_draw_sorted_screen_int): with U0, U1 the 53-bit
+  // integers of u0 = U0 2^-53 and u1 = U1 2^-53,
+  //  - thrI = thr 2^53 (2^53: none), so u1 >= thr iff U1 >= thrI;
+  //  - pickB[j], j < K - 1: the smallest U0 at which the pick passes component
+  //    j, cdf[j] <= fl(u0 cdf[K - 1]) (2^53 from K - 1 up);
+  //  - guide[b], bucket b of the top gbits bits of U0: k_lo = #{j : pickB[j] <=
+  //    the bucket's first U0} in the low byte, the number of boundaries
+  //    strictly inside the bucket -- all of one value -- in the high one: the
+  //    pick is k_lo + (U0 >= pickB[k_lo] ? that number : 0).
+  uint64_t thrI[kFuseTab][kZoneEdges];
+  uint64_t pickB[kFuseTab];
+  uint16_t guide[1 << kGuideBitsMax];
 };
 // the zones of a launch's slots: after k_table_pilot, ahead of the screened draw
-// (tiles: pilot wave tiles of widening per side; margin: |x drawn - x true| / sigma covered)
+// (tiles: pilot wave tiles of widening per side; margin: |x drawn - x true| / sigma covered;
+// guide_bits >= 0: the integer form too, and no zones for a slot whose guide is not valid)
 hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, double margin,
-                            hipStream_t st);
+                            int32_t guide_bits, hipStream_t st);
 // launch_draw_pruned's fast small-table launch with the screen; stats: two
-// counters (blocks screened << 40 | elements inverted; blocks fallen back)
+// counters (blocks screened << 40 | elements inverted; blocks fallen back);
+// integer: the screen on integer uniforms (zones from a guide_bits >= 0 launch_draw_zone)
 hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
-                                unsigned long long *stats, hipStream_t st);
-bool is_screen_draw_kernel_fn(const void *f);  // k_draw_sorted_screen's (tpe_screen.hip)
+                                unsigned long long *stats, bool integer, hipStream_t st);
+bool is_screen_draw_kernel_fn(const void *f);  // k_draw_sorted_screen's, both (tpe_screen.hip)
 // k_table_pilot of the launch's wave-tile class on its own, for the draw that
 // needs the hot intervals (launch_score with tab_pref 2 does not launch it)
 hipError_t launch_table_pilot(const ScoreArgs &a, hipStream_t st);

@@ -290,6 +290,7 @@ struct ChunkPlan {
   bool small_table = false;  // ... and the small one (kFuseTab)
   bool fast = false;         // the sorted draw without the out-of-line draws
   int32_t screen_tiles = 0;  // Draw::SortedScreened: the zones' widening
+  int32_t screen_guide = -1; // ... the integer screen's guide bits; -1: the float screen
   bool bucket = false;       // k_bucket follows the draw
   bool cand_pos = false;     // the scoring launch reads candidate positions
   // the main scoring launch: ScoreArgs::tab_on / tab_pref (2 behind a pruning
@@ -498,6 +499,7 @@ inline LevelPlan plan_level(const PlanShape &ps, const Switches &sw, const StepS
                           c.cn * n_sug * n_level >= sw.draw_screen_min;
       c.draw = screen ? Draw::SortedScreened : prune ? Draw::SortedPruned : Draw::Sorted;
       c.screen_tiles = (int32_t)sw.draw_screen_tiles;
+      c.screen_guide = sw.draw_screen_int ? (int32_t)sw.draw_screen_guide_bits : -1;
       if (prune) c.tab_pref = 2;
     } else {
       c.draw = Draw::Plain;

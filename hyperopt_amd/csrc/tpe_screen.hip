@@ -11,6 +11,9 @@
 // candidate, inverts only the ones inside a zone, and composes the kept tiles
 // from those alone where it can prove that the layout is the full draw's.
 // Where it cannot, the sort block runs sorted_block_prune_body from scratch.
+// k_draw_sorted_screen_int (the default) makes the same decisions on the
+// uniforms' 53-bit integers: the pick from a guide table on the top bits of
+// U0, the class from integer thresholds on U1, no double before the inversion.
 #include <float.h>
 #include <math.h>
 
@@ -70,13 +73,18 @@ __device__ __forceinline__ bool zone_crossed(double u1, double b, double m, int 
 
 // One block per (suggestion, slot row), the grid rows of the draw.  Reads the
 // slot's TabHot and the pilot's sort block (block 0 of A.cand, whole) and
-// writes the slot's DrawZone.
+// writes the slot's DrawZone.  gbits >= 0: its integer form too (thrI, pickB
+// and the guide of 2^gbits buckets), and no zones for a slot whose guide is
+// not valid: the draw's table not finite and nondecreasing with a positive
+// total, or two distinct pick boundaries inside one bucket.
 __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZone *zones,
-                                                            int32_t tiles, double margin) {
+                                                            int32_t tiles, double margin,
+                                                            int32_t gbits) {
   __shared__ DrawTableT<kFuseTab> T;
   __shared__ double tmin[kPilotWaves], tmax[kPilotWaves];
   __shared__ double zlo[kZoneCand], zhi[kZoneCand];
-  __shared__ int nz_s;
+  __shared__ uint64_t pb[kFuseTab];
+  __shared__ int nz_s, bad_s;
   const int s = blockIdx.y;
   const int slot = row_slot(A, s, 0, A.n_slots, blockIdx.x);
   if (slot < 0) return;
@@ -173,6 +181,7 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
     // and the last ends at +inf by the tails)
     if (nz < 2 || zlo[0] != -INFINITY || zhi[nz - 1] != INFINITY) nz = 0;
     nz_s = nz;
+    bad_s = 0;
     Z->nz = nz;
     for (int g = 0; g + 1 < nz; ++g) { Z->gap_lo[g] = zhi[g]; Z->gap_hi[g] = zlo[g + 1]; }
   }
@@ -181,6 +190,56 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
   if (nz == 0) return;
   const double *bw = A.mw + sb * A.kcap, *bmu = A.mmu + sb * A.kcap, *bsg = A.msig + sb * A.kcap;
   build_table(H, K, bw, bmu, bsg, T);
+  if (gbits >= 0) {
+    // pick boundary j: the smallest U in [0, 2^53] with cdf[j] <= fl(U 2^-53
+    // cdf_last) -- the draw's own product, monotone in U -- by bisection
+    const double cl = T.cdf[K - 1];
+    if (t < kFuseTab) {
+      uint64_t lo = 1ull << 53;
+      if (t < K - 1) {
+        const double cj = T.cdf[t];
+        uint64_t hi = lo;
+        lo = 0;
+#pragma unroll 1
+        while (lo < hi) {
+          const uint64_t mid = (lo + hi) >> 1;
+          if (cj <= ((double)mid * 0x1p-53) * cl) hi = mid;
+          else lo = mid + 1;
+        }
+      }
+      pb[t] = lo;
+      if (t < K) {
+        const double c = T.cdf[t];
+        if (!(fabs(c) < INFINITY) || (t > 0 && !(c >= T.cdf[t - 1])) || !(cl > 0.0)) bad_s = 1;
+      }
+    }
+    __syncthreads();
+    const int sh = 53 - gbits;
+    for (int b = t; b < (1 << gbits); b += kZoneThreads) {
+      const uint64_t s0 = (uint64_t)b << sh, s1 = s0 + (1ull << sh);
+      uint32_t kl = 0, c = 0;
+      uint64_t val = 0;
+      bool two = false;
+      for (int j = 0; j < K - 1; ++j) {
+        const uint64_t bj = pb[j];
+        if (bj <= s0) ++kl;
+        else if (bj < s1) {
+          two |= c > 0 && bj != val;
+          val = bj;
+          ++c;
+        }
+      }
+      Z->guide[b] = (uint16_t)(kl | (c << 8));
+      if (two) bad_s = 1;
+    }
+    __syncthreads();
+    if (bad_s) {  // (block-uniform)
+      if (t == 0) Z->nz = 0;
+      return;
+    }
+    if (t < kFuseTab) Z->pickB[t] = pb[t];
+    if (t == 0) Z->gbits = gbits;
+  }
   // threshold (k, e): the smallest u1 = j 2^-53 at which the edge is crossed
   // (1: none), by bisection on j
   const int E = 2 * (nz - 1);
@@ -190,7 +249,7 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
     const double edge = up ? zhi[e >> 1] : zlo[(e >> 1) + 1];
     const double mu = bmu[k], sg = bsg[k], b = T.base[k], m = T.mass[k];
     const int md = T.mode[k];
-    double thr = 1.0;
+    uint64_t thr = 1ull << 53;
     if (m > 0.0 && fabs(m) < INFINITY && fabs(b) < INFINITY && sg > 0.0 && fabs(sg) < INFINITY &&
         fabs(mu) < INFINITY) {
       const double delta = margin * sg + 8.0 * DBL_EPSILON * (fabs(edge) + fabs(mu));
@@ -204,10 +263,11 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
         if (zone_crossed((double)mid * 0x1p-53, b, m, md, z, tail, up)) hi = mid;
         else lo = mid + 1;
       }
-      thr = (double)lo * 0x1p-53;
-      if (!(tail == tail)) thr = 1.0;
+      thr = lo;
+      if (!(tail == tail)) thr = 1ull << 53;
     }
-    Z->thr[k][e] = thr;
+    Z->thr[k][e] = (double)thr * 0x1p-53;
+    if (gbits >= 0) Z->thrI[k][e] = thr;
   }
   __syncthreads();
   // nondecreasing in the edge (the margins of two close edges may cross: that
@@ -219,18 +279,25 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
       run = fmax(run, Z->thr[k][e]);
       Z->thr[k][e] = run;
     }
+    if (gbits >= 0) {
+      uint64_t runI = 0;
+      for (int e = 0; e < E; ++e) {
+        runI = max(runI, Z->thrI[k][e]);
+        Z->thrI[k][e] = runI;
+      }
+    }
   }
 }
 
 hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, double margin,
-                            hipStream_t st) {
+                            int32_t guide_bits, hipStream_t st) {
   const int64_t sbk = (int64_t)1 << a.sort_log2;
   if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
   if (sbk != kSortedBlock || sbk != kPilotWaves * 128 || !zones || !a.tab_hot || !a.tab_hdr ||
-      tiles < 0)
+      tiles < 0 || guide_bits > kGuideBitsMax)
     return hipErrorInvalidValue;
-  k_draw_zone<<<dim3((unsigned)a.slot_rows, a.n_suggest), kZoneThreads, 0, st>>>(a, zones, tiles,
-                                                                                 margin);
+  k_draw_zone<<<dim3((unsigned)a.slot_rows, a.n_suggest), kZoneThreads, 0, st>>>(
+      a, zones, tiles, margin, guide_bits < 0 ? -1 : guide_bits);
   return hipGetLastError();
 }
 
@@ -240,7 +307,10 @@ hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, 
 template <int NT>
 struct ScreenLds {
   DrawTableT<kFuseTab> T;
-  double thr[kFuseTab * kZoneEdges];
+  union {  // (a component's row: 80 bytes, so 16-byte reads of threshold pairs)
+    double thr[kFuseTab * kZoneEdges];
+    uint64_t thrI[kFuseTab * kZoneEdges];
+  };
   uint32_t cnt[NT / 64 * kSortBuckets / 2];  // (SortedDrawLds::cnt)
   double red[2][NT / 64];
   unsigned char hotb[kSortBuckets], liveb[kSortBuckets];  // (PruneDrawLds')
@@ -248,10 +318,14 @@ struct ScreenLds {
   int fail;
   int gapc[NT / 64][kZoneMax - 1];  // a wave's cold elements per gap
   int ncl[NT / 64];                 // a wave's inverted elements
-  // a wave's inverted elements in index order: u1, then the value; the index
-  // in the block with the component, then with the bucket, above bit 16
+  // a wave's inverted elements in index order: u1 (the integer screen: U1's
+  // bits), then the value; the index in the block with the component, then
+  // with the bucket, above bit 16
   double cx[NT / 64][kScreenList];
   uint32_t ci[NT / 64][kScreenList];
+  // the integer screen's pick (DrawZone's)
+  uint64_t pickB[kFuseTab];
+  uint16_t guide[1 << kGuideBitsMax];
 };
 template <int CAP, int NT>
 union ScreenUnion {
@@ -274,7 +348,9 @@ __device__ __forceinline__ int screen_bucket(double key, double lo, double scale
 // kept tiles and tab_wmax marks are written, as that body writes them.
 // False: nothing is written (the caller runs that body).  Every thread of the
 // block calls it; the result is block-uniform.  nexact: the inverted elements.
-template <int CAP, int NT>
+// INT: phase 1 on the integer uniforms (DrawZone's integer form): the same
+// component and the same class of every element, without a double.
+template <int CAP, int NT, bool INT>
 __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int s, int64_t base,
                                                int32_t *__restrict__ pos_out,
                                                const DrawZone *__restrict__ Z, int nz,
@@ -288,7 +364,18 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
   build_table(H, K, bw, bmu, bsg, L.T);
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int E = 2 * (nz - 1);
-  for (int idx = t; idx < K * kZoneEdges; idx += NT) L.thr[idx] = (&Z->thr[0][0])[idx];
+  int gsh = 0;  // (the guide's bucket of r.x: (r.x >> 1) >> gsh)
+  if constexpr (INT) {
+    // (the edges from E up: none, so that phase 1 reads them in fixed groups)
+    for (int idx = t; idx < K * kZoneEdges; idx += NT)
+      L.thrI[idx] = idx % kZoneEdges < E ? (&Z->thrI[0][0])[idx] : 1ull << 53;
+    const int G = min(max(__builtin_amdgcn_readfirstlane(Z->gbits), 0), kGuideBitsMax);
+    gsh = 31 - G;
+    for (int idx = t; idx < (1 << G); idx += NT) L.guide[idx] = Z->guide[idx];
+    if (t < kFuseTab) L.pickB[t] = Z->pickB[t];
+  } else {
+    for (int idx = t; idx < K * kZoneEdges; idx += NT) L.thr[idx] = (&Z->thr[0][0])[idx];
+  }
   if (t < kSortBuckets) L.hotb[t] = 0;
   if (t == 0) { L.keep = 0ull; L.fail = 0; }
   __syncthreads();
@@ -298,7 +385,11 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
   double *out = const_cast<double *>(A.cand) + off;
   // the wave's rows: bucket_bases' [r0, r1)
   const int per = ((n + NW * 64 - 1) / (NW * 64)) * 64;
-  const int r0 = wv * per, r1 = min(n, r0 + per);
+  int r0 = wv * per, r1 = min(n, r0 + per);
+  if constexpr (INT) {  // (wave-uniform: the row loop and its counters stay scalar)
+    r0 = __builtin_amdgcn_readfirstlane(r0);
+    r1 = __builtin_amdgcn_readfirstlane(r1);
+  }
   const double cdf_last = L.T.cdf[K - 1];
   const double high_prev = nextafter(H.high, -INFINITY);
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -318,12 +409,45 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
     const uint64_t gi = (uint64_t)(A.cand_begin + base + i);
     const U4 r = philox(U4{(uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)hp, 0u}, k0, k1);
     double u1;
-    const int k = draw_bounded_pick<CAP>(L.T, K, cdf_last, r, u1);
-    const double *th = L.thr + k * kZoneEdges;
-    int c = 0;
-    for (int e = 0; e < E; ++e) c += u1 >= th[e] ? 1 : 0;
-    const bool exact = v && !(c & 1);
-    const uint64_t bal = __ballot(exact);
+    int k, c = 0;
+    if constexpr (INT) {
+      // u53's integers: u0 = U0 2^-53, u1 = U1 2^-53
+      const uint64_t U0 = ((uint64_t)(r.x >> 5) << 26) | (r.y >> 6);
+      const uint64_t U1 = ((uint64_t)(r.z >> 5) << 26) | (r.w >> 6);
+      const uint32_t ge = L.guide[(r.x >> 1) >> gsh];
+      const uint32_t kl = ge & 0xffu;
+      k = (int)(kl + (U0 >= L.pickB[kl] ? ge >> 8 : 0u));
+      // the first two gaps' edges in one group of reads, the others (wave-
+      // uniform: more than three zones) in a second
+      const ulonglong2 *th = reinterpret_cast<const ulonglong2 *>(L.thrI + k * kZoneEdges);
+      static_assert(kZoneEdges == 10, "five threshold pairs");
+      {
+        const ulonglong2 a = th[0], b = th[1];
+        c = (U1 >= a.x ? 1 : 0) + (U1 >= a.y ? 1 : 0) + (U1 >= b.x ? 1 : 0) + (U1 >= b.y ? 1 : 0);
+      }
+      if (E > 4) {
+        const ulonglong2 a = th[2], b = th[3], d = th[4];
+        c += (U1 >= a.x ? 1 : 0) + (U1 >= a.y ? 1 : 0) + (U1 >= b.x ? 1 : 0) + (U1 >= b.y ? 1 : 0) +
+             (U1 >= d.x ? 1 : 0) + (U1 >= d.y ? 1 : 0);
+      }
+      u1 = __longlong_as_double((long long)U1);  // (the list keeps U1's bits)
+    } else {
+      k = draw_bounded_pick<CAP>(L.T, K, cdf_last, r, u1);
+      const double *th = L.thr + k * kZoneEdges;
+      for (int e = 0; e < E; ++e) c += u1 >= th[e] ? 1 : 0;
+    }
+    // (the integer screen: lane masks of plain compares, combined as scalars,
+    // and the lane's own bit back from the mask)
+    const uint64_t vm = INT ? __builtin_amdgcn_ballot_w64(v) : 0ull;
+    bool exact;
+    uint64_t bal;
+    if constexpr (INT) {
+      bal = __builtin_amdgcn_ballot_w64((c & 1) == 0) & vm;
+      exact = __builtin_amdgcn_inverse_ballot_w64(bal);
+    } else {
+      exact = v && !(c & 1);
+      bal = __ballot(exact);
+    }
     const int pos = ncl + __popcll(bal & below);
     if (exact && pos < kScreenList) {
       cx[pos] = u1;
@@ -332,8 +456,11 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
     ncl += __popcll(bal);
     const int gap = (v && (c & 1)) ? (c >> 1) : -1;
 #pragma unroll
-    for (int g = 0; g < kZoneMax - 1; ++g)
-      if (g < nz - 1) gc[g] += __popcll(__ballot(gap == g));
+    for (int g = 0; g < kZoneMax - 1; ++g) {
+      if (g >= nz - 1) continue;
+      if constexpr (INT) gc[g] += __popcll(__builtin_amdgcn_ballot_w64(c == 2 * g + 1) & vm);
+      else gc[g] += __popcll(__ballot(gap == g));
+    }
   }
   const bool over = ncl > kScreenList;  // (a list overflow: the block falls back)
   if (over) ncl = 0;
@@ -349,7 +476,12 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
   for (int j0 = 0; j0 < ncl; j0 += 64) {
     const int j = j0 + lane;
     const bool v = j < ncl;
-    const double u1 = v ? cx[j] : 0.5;
+    double u1 = v ? cx[j] : 0.5;
+    if constexpr (INT) {  // u53's value of U1, by its operations
+      const uint64_t U1 = v ? (uint64_t)__double_as_longlong(cx[j]) : 1ull << 52;
+      u1 = ((double)(uint32_t)(U1 >> 26) * 67108864.0 + (double)(uint32_t)(U1 & 0x3ffffffu)) *
+           (1.0 / 9007199254740992.0);
+    }
     const int k = v ? (int)(ci[j] >> 16) : 0;
     const double x = draw_bounded_invert<CAP>(L.T, k, u1, bmu, bsg, H.low, H.high, high_prev, false,
                                               false, 0.0);
@@ -463,12 +595,14 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
 // k_draw_sorted_prune with the screen: the same grid, the same slots; a slot
 // k_draw_zone left no zones for, and a sort block whose screen cannot prove
 // its layout, run sorted_block_prune_body.
-template <int CAP, bool FAST>
-__global__ __launch_bounds__(kScreenThreads) __attribute__((amdgpu_waves_per_eu(4)))
-void k_draw_sorted_screen(ScoreArgs A, int32_t *__restrict__ pos_out,
-                          const DrawZone *__restrict__ zones, unsigned long long *stats) {
+template <int CAP, bool FAST, bool INT>
+__device__ __forceinline__ void draw_sorted_screen_body(const ScoreArgs &A,
+                                                        int32_t *__restrict__ pos_out,
+                                                        const DrawZone *__restrict__ zones,
+                                                        unsigned long long *stats) {
   static_assert(CAP == kFuseTab && FAST, "the small-table inline draw only");
-  __shared__ ScreenUnion<CAP, kScreenThreads> U;
+  // (16-byte aligned: the integer screen reads ScreenLds::thrI in pairs)
+  __shared__ __attribute__((aligned(16))) ScreenUnion<CAP, kScreenThreads> U;
   const int s = blockIdx.z;
   const int slot = row_slot(A, s, 0, A.n_slots, blockIdx.y);
   if (slot < 0) return;
@@ -488,8 +622,8 @@ void k_draw_sorted_screen(ScoreArgs A, int32_t *__restrict__ pos_out,
   const int nz = kind == KIND_LSE_GW ? __builtin_amdgcn_readfirstlane(Z->nz) : 0;
   if (nz >= 2 && nz <= kZoneMax) {
     int nexact = 0;
-    const bool done = screened_block<CAP, kScreenThreads>(A, slot, s, base, pos_out, Z, nz, U.S,
-                                                          nexact);
+    const bool done = screened_block<CAP, kScreenThreads, INT>(A, slot, s, base, pos_out, Z, nz,
+                                                               U.S, nexact);
     if (threadIdx.x == 0)
       atomicAdd(stats + (done ? 0 : 1), done ? (1ull << 40) | (unsigned long long)nexact : 1ull);
     if (done) return;
@@ -499,19 +633,36 @@ void k_draw_sorted_screen(ScoreArgs A, int32_t *__restrict__ pos_out,
       A, slot, s, base, kind_lse(kind) || kind == KIND_ERF_G || kind == KIND_ERF_L,
       kind_logn(kind), tabk, pos_out, U.P);
 }
+template <int CAP, bool FAST>
+__global__ __launch_bounds__(kScreenThreads) __attribute__((amdgpu_waves_per_eu(4)))
+void k_draw_sorted_screen(ScoreArgs A, int32_t *__restrict__ pos_out,
+                          const DrawZone *__restrict__ zones, unsigned long long *stats) {
+  draw_sorted_screen_body<CAP, FAST, false>(A, pos_out, zones, stats);
+}
+// ... on the integer uniforms (zones of a k_draw_zone with gbits >= 0)
+template <int CAP, bool FAST>
+__global__ __launch_bounds__(kScreenThreads) __attribute__((amdgpu_waves_per_eu(4)))
+void k_draw_sorted_screen_int(ScoreArgs A, int32_t *__restrict__ pos_out,
+                              const DrawZone *__restrict__ zones, unsigned long long *stats) {
+  draw_sorted_screen_body<CAP, FAST, true>(A, pos_out, zones, stats);
+}
 
 bool is_screen_draw_kernel_fn(const void *f) {
-  return f == reinterpret_cast<const void *>(&k_draw_sorted_screen<kFuseTab, true>);
+  return f == reinterpret_cast<const void *>(&k_draw_sorted_screen<kFuseTab, true>) ||
+         f == reinterpret_cast<const void *>(&k_draw_sorted_screen_int<kFuseTab, true>);
 }
 
 hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
-                                unsigned long long *stats, hipStream_t st) {
+                                unsigned long long *stats, bool integer, hipStream_t st) {
   const int64_t sbk = (int64_t)1 << a.sort_log2;
   if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
   if (sbk != kSortedBlock || !a.tab_wmax || !a.tab_hot || !a.tab_hdr || !zones || !stats)
     return hipErrorInvalidValue;
   const dim3 g((unsigned)((a.n_cand + sbk - 1) / sbk - 1), (unsigned)a.slot_rows, a.n_suggest);
-  k_draw_sorted_screen<kFuseTab, true><<<g, kScreenThreads, 0, st>>>(a, pos_out, zones, stats);
+  if (integer)
+    k_draw_sorted_screen_int<kFuseTab, true><<<g, kScreenThreads, 0, st>>>(a, pos_out, zones, stats);
+  else
+    k_draw_sorted_screen<kFuseTab, true><<<g, kScreenThreads, 0, st>>>(a, pos_out, zones, stats);
   return hipGetLastError();
 }
 

@@ -27,6 +27,9 @@ struct Switches {
   bool table;         // large draws scored from certified Chebyshev tables
   bool draw_prune;    // the sorted draw drops the wave tiles the hot intervals rule out
   bool draw_screen;   // ... and screens its candidates on (component, u1) first
+  // ... on the integer uniforms, the pick from a guide table; 0: the float
+  // screen (k_draw_sorted_screen with k_draw_zone's float thresholds alone)
+  bool draw_screen_int;
   bool table_prefilter;  // wave tiles a certified bound rules out are not table-scored
   bool table_scalar;  // the scalar-panel table kernels; 0: the per-lane ones
   // value-bucketed, pruned log-sum-exp slots on small draws: opt-in.  Measured
@@ -50,6 +53,10 @@ struct Switches {
   // the smallest launch (candidates x suggestions x slots) the screen takes: it
   // saves ~1.4 us per 2^20 candidate-slots, k_draw_zone costs ~33 us
   int64_t draw_screen_min;
+  // the integer screen's pick guide: 2^bits buckets on the top bits of u0; a
+  // slot with two distinct pick boundaries in one bucket is not screened
+  // (the sweep behind the default)
+  int64_t draw_screen_guide_bits;
   // candidate buffer per scoring chunk, MB.  8 GB (+ 4 GB of positions): config
   // 4's 1e9 candidates of a level in one draw + one scoring launch, config 5's
   // 32-suggestion calls in one chunk (config 4 79.3 -> 78.8 ms, config 5 461.3
@@ -103,6 +110,7 @@ inline const SwitchDef *switch_table(int *n) {
       {"TPE_TABLE", R::OffIfZero, 1, &S::table, nullptr, 0, 0},
       {"TPE_DRAW_PRUNE", R::OffIfNonEmptyZero, 1, &S::draw_prune, nullptr, 0, 0},
       {"TPE_DRAW_SCREEN", R::OffIfNonEmptyZero, 1, &S::draw_screen, nullptr, 0, 0},
+      {"TPE_DRAW_SCREEN_INT", R::OffIfNonEmptyZero, 1, &S::draw_screen_int, nullptr, 0, 0},
       {"TPE_TABLE_PREFILTER", R::OffIfNonEmptyZero, 1, &S::table_prefilter, nullptr, 0, 0},
       {"TPE_TABLE_SCALAR", R::OffIfNonEmptyZero, 1, &S::table_scalar, nullptr, 0, 0},
       {"TPE_SMALL_SORT", R::OnIfNonZero, 0, &S::small_sort, nullptr, 0, 0},
@@ -113,6 +121,8 @@ inline const SwitchDef *switch_table(int *n) {
        kPilotWaves},
       {"TPE_DRAW_SCREEN_MIN", R::ValueIfNonEmpty, kDrawScreenMin, nullptr, &S::draw_screen_min, lo,
        hi},
+      {"TPE_DRAW_SCREEN_GUIDE_BITS", R::ValueIfNonEmpty, 9, nullptr, &S::draw_screen_guide_bits, 0,
+       kGuideBitsMax},
       {"TPE_CHUNK_MB", R::ValueIfSet, 8192, nullptr, &S::chunk_mb, lo, hi},
       {"TPE_SHIFT_MIN_K", R::ValueIfSet, 512, nullptr, &S::lse_shift_min, lo, hi},
   };

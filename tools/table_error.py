@@ -472,10 +472,11 @@ def zone_crossed(u1, base, mass, mode, z, tail, up):
     return deep_hi | (ok_lo & np.where(up, above, ~below))
 
 
-def zone_thresholds(zlo, zhi, base, mass, mode, mu, sigma, margin=None):
+def zone_thresholds(zlo, zhi, base, mass, mode, mu, sigma, margin=None, integer=False):
     """k_draw_zone's u1 thresholds thr[K][2 (nz - 1)] of the disjoint value
     zones [zlo[i], zhi[i]] (ascending, the first from -inf, the last to +inf):
-    component k's draw is cold in gap g iff thr[k][2g] <= u1 < thr[k][2g + 1]."""
+    component k's draw is cold in gap g iff thr[k][2g] <= u1 < thr[k][2g + 1].
+    integer: its thrI = thr 2^53 as uint64 (2^53: none), for U1 = u1 2^53."""
     from scipy.special import erfc
     margin = SCREEN_MARGIN if margin is None else margin
     nz, K = len(zlo), len(mu)
@@ -499,11 +500,10 @@ def zone_thresholds(zlo, zhi, base, mass, mode, mu, sigma, margin=None):
         act = lo < hi
         hi = np.where(act & c, mid, hi)
         lo = np.where(act & ~c, mid + np.uint64(1), lo)
-    thr = lo.astype(np.float64) * 2.0 ** -53
     bad = ~((m > 0.0) & np.isfinite(m) & np.isfinite(b) & (sg > 0.0) & np.isfinite(sg) &
             np.isfinite(mu_) & ~np.isnan(tail))
-    thr = np.where(bad, 1.0, thr)
-    return np.maximum.accumulate(thr, axis=1)
+    thr_i = np.maximum.accumulate(np.where(bad, np.uint64(1 << 53), lo), axis=1)
+    return thr_i if integer else thr_i.astype(np.float64) * 2.0 ** -53
 
 
 def screen_gap(thr_k, u1):
@@ -513,14 +513,117 @@ def screen_gap(thr_k, u1):
     return np.where(c % 2 == 1, c // 2, -1)
 
 
-def draw_picks(w, mu, sigma, low, high, n, rs):
-    """n draws of the table sampler: (component, u1, value)."""
+ONE53 = 1 << 53
+FUSE_TAB = 32          # kFuseTab: the pick ladder's table
+
+
+def u53_int(u):
+    """U of a uniform u = U 2^-53 (u53's integer; exact)."""
+    return (np.asarray(u, dtype=np.float64) * 2.0 ** 53).astype(np.uint64)
+
+
+def pick_predicate(cdf, j, U):
+    """The draw's own test of component j at U0 = U: cdf[j] <= fl(u0 cdf_last),
+    u0 = U 2^-53 exact, one rounding in the product."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    u0 = np.asarray(U, dtype=np.uint64).astype(np.float64) * 2.0 ** -53
+    with np.errstate(invalid='ignore'):
+        return cdf[j] <= u0 * cdf[-1]
+
+
+def pick_cdf_emul(cdf, U0):
+    """pick_cdf: the first k with cdf[k] > t, capped at K - 1 (binary search)."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    t = np.asarray(U0, dtype=np.uint64).astype(np.float64) * 2.0 ** -53 * cdf[-1]
+    lo = np.zeros(t.shape, dtype=np.int64)
+    hi = np.full(t.shape, cdf.size - 1, dtype=np.int64)
+    while (lo < hi).any():
+        act = lo < hi
+        mid = (lo + hi) >> 1
+        le = cdf[mid] <= t
+        lo = np.where(act & le, mid + 1, lo)
+        hi = np.where(act & ~le, mid, hi)
+    return lo
+
+
+def pick_ladder_emul(cdf, U0, cap=FUSE_TAB):
+    """pick_cdf_ladder<cap>, step for step."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    K = cdf.size
+    t = np.asarray(U0, dtype=np.uint64).astype(np.float64) * 2.0 ** -53 * cdf[-1]
+    pad = np.concatenate([cdf, np.zeros(cap - K)])
+    lo = np.zeros(t.shape, dtype=np.int64)
+    step = cap // 2
+    while step > 0:
+        j = lo + step
+        ok = (j <= K - 1) & (pad[np.minimum(j, cap) - 1] <= t)
+        lo = np.where(ok, j, lo)
+        step >>= 1
+    return lo
+
+
+def pick_thresholds(cdf):
+    """k_draw_zone's pick boundaries B[K] (uint64): for j < K - 1 the smallest
+    U in [0, 2^53] with cdf[j] <= fl(U 2^-53 cdf_last), by the 53-step
+    bisection on the float predicate; B[K - 1] = 2^53.  With a nondecreasing
+    cdf the pick of U0 is #{j < K - 1 : U0 >= B[j]}."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    K = cdf.size
+    B = np.full(K, ONE53, dtype=np.uint64)
+    j = np.arange(K - 1)
+    lo = np.zeros(K - 1, dtype=np.uint64)
+    hi = np.full(K - 1, ONE53, dtype=np.uint64)
+    for _ in range(54):
+        act = lo < hi
+        mid = (lo + hi) >> np.uint64(1)
+        c = pick_predicate(cdf, j, mid)
+        hi = np.where(act & c, mid, hi)
+        lo = np.where(act & ~c, mid + np.uint64(1), lo)
+    B[:K - 1] = lo
+    return B
+
+
+def guide_table(cdf, gbits):
+    """k_draw_zone's guide over the 2^gbits buckets of the top bits of U0:
+    dict with B (pick_thresholds), k_lo[b] = #{j : B[j] <= the bucket's first
+    U0}, c[b] = the boundaries strictly inside the bucket, and valid: cdf
+    finite, nondecreasing, cdf_last > 0 and no bucket with two distinct
+    interior boundaries."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    B = pick_thresholds(cdf)
+    bj = B[:-1]
+    sh = np.uint64(53 - gbits)
+    s0 = np.arange(1 << gbits, dtype=np.uint64) << sh
+    s1 = s0 + (np.uint64(1) << sh)
+    k_lo = (bj[None, :] <= s0[:, None]).sum(axis=1)
+    inside = (bj[None, :] > s0[:, None]) & (bj[None, :] < s1[:, None])
+    c = inside.sum(axis=1)
+    two = np.zeros(s0.size, dtype=bool)
+    for b in np.flatnonzero(c > 1):
+        two[b] = np.unique(bj[inside[b]]).size > 1
+    ok = bool(np.isfinite(cdf).all() and (np.diff(cdf) >= 0.0).all() and cdf[-1] > 0.0)
+    return dict(B=B, k_lo=k_lo, c=c, gbits=gbits, valid=ok and not two.any(), two=two)
+
+
+def guide_pick(g, U0):
+    """The integer pick: k_lo + (U0 >= B[k_lo] ? c : 0) of U0's bucket."""
+    U0 = np.asarray(U0, dtype=np.uint64)
+    b = (U0 >> np.uint64(53 - g['gbits'])).astype(np.int64)
+    kl = g['k_lo'][b]
+    return kl + np.where(U0 >= g['B'][kl], g['c'][b], 0)
+
+
+def draw_picks(w, mu, sigma, low, high, n, rs, integers=False):
+    """n draws of the table sampler: (component, u1, value); integers: and
+    (U0, U1), the 53-bit integers of the pick's and the inversion's uniforms."""
     pw, base, mass, mode = draw_table(w, mu, sigma, low, high)
     cdf = np.cumsum(pw)
-    k = np.minimum(np.searchsorted(cdf, rs.random_sample(n) * cdf[-1], side='right'), cdf.size - 1)
+    u0 = rs.random_sample(n)
+    k = np.minimum(np.searchsorted(cdf, u0 * cdf[-1], side='right'), cdf.size - 1)
     u1 = np.floor(rs.random_sample(n) * 2.0 ** 53) * 2.0 ** -53
     mu, sigma = np.asarray(mu), np.asarray(sigma)
-    return k, u1, draw_invert_emul(base[k], mass[k], mode[k], mu[k], sigma[k], low, high, u1)
+    x = draw_invert_emul(base[k], mass[k], mode[k], mu[k], sigma[k], low, high, u1)
+    return (k, u1, x, u53_int(u0), u53_int(u1)) if integers else (k, u1, x)
 
 
 def _block_bytes(x, lo, hi):
@@ -584,14 +687,18 @@ def draw_zones(pilot, intervals, y_lo, y_hi, center, tiles, zone_max=6):
     return np.array([a for a, _ in out]), np.array([b for _, b in out])
 
 
-def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cells=CELLS):
+def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cells=CELLS,
+                integers=None, gbits=9):
     """The screened draw on the draws (k, u1, x) of one launch (draw_picks),
     block by block behind the pilot's, beside the full computation on all
     elements: dict with `blocks`, `fallback` (blocks that would run the full
     body), `exact` (share of the screened blocks' elements inverted) and
     `mismatch`: the blocks that do not fall back and whose key range, kept
     mask, live buckets, their counts and bases, or the bucket bytes of the
-    inverted elements differ from the full computation's (must be empty)."""
+    inverted elements differ from the full computation's (must be empty).
+    integers = (U0, U1): the integer screen -- the component from the guide
+    pick of U0 (k only draws x), the class from U1 against thrI; a slot whose
+    guide is not valid is not screened (`valid` False, no blocks)."""
     w, mu, sigma = mix
     r = prefilter(tb, ta, x - center, tie, cells)
     y_lo = tb['y_lo']
@@ -601,9 +708,19 @@ def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cell
     if zones is None:
         return out
     zlo, zhi = zones
-    _, base, mass, mode = draw_table(w, mu, sigma, low, high)
-    thr = zone_thresholds(zlo, zhi, base, mass, mode, np.asarray(mu), np.asarray(sigma))
-    c = (u1[:, None] >= thr[k]).sum(axis=1)
+    pw, base, mass, mode = draw_table(w, mu, sigma, low, high)
+    thr = zone_thresholds(zlo, zhi, base, mass, mode, np.asarray(mu), np.asarray(sigma),
+                          integer=integers is not None)
+    if integers is None:
+        c = (u1[:, None] >= thr[k]).sum(axis=1)
+    else:
+        g = guide_table(np.cumsum(pw), gbits)
+        out['valid'] = g['valid']
+        if not g['valid']:
+            return out
+        ki = guide_pick(g, integers[0])
+        out['pick_mismatch'] = int((ki != k).sum())
+        c = (integers[1][:, None] >= thr[ki]).sum(axis=1)
     cold, gap = c % 2 == 1, c // 2
     yc = np.clip(x - center, y_lo, y_hi)
     hit = np.isnan(x)
