@@ -14,5 +14,6 @@ from .fmin import fmin, fmin_pass_expr_memo_ctrl, FMinIter, partial, space_eval 
 from .workers import ThreadTrials  # noqa: F401
 from .expr import scope  # noqa: F401
 from . import hp, rand, tpe, anneal, mix  # noqa: F401
+from .tpe import score_configs, suggest_from_pool  # noqa: F401
 
 __version__ = '0.1.0'

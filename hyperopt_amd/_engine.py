@@ -44,7 +44,7 @@ EXPORTS = (
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
     'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
     'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
-    'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats',
+    'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats', 'tpe_plan_score_points',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -153,6 +153,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_score_candidates': (C.c_int, [vp, i32, _D, i64, _D, _D, C.POINTER(i64), _D]),
             'tpe_plan_score_candidates_sorted': (C.c_int, [vp, i32, i32, _D, i64, _D, _D,
                                                            C.POINTER(i64), _D]),
+            'tpe_plan_score_points': (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -339,6 +340,65 @@ class Engine(object):
                 float(q) if q is not None else 0.0, self._flags(low, high, q),
                 int(seed) & (2 ** 64 - 1), int(stream), int(offset), int(n), _dp(out)))
         return out
+
+
+class DeviceBuffer(object):
+    """A plain device allocation on ``engine``'s GPU, through the HIP runtime
+    the engine library itself is linked against (resolved through the library's
+    handle, so both use one runtime).  For data that stays on the device
+    between engine calls -- a candidate pool -- without PyTorch.  ``upload`` /
+    ``download`` are blocking copies; call ``engine.synchronize()`` before
+    reading what a stream-ordered engine call wrote."""
+
+    def __init__(self, engine: Engine, nbytes: int):
+        self.engine = engine
+        self.nbytes = int(nbytes)
+        lib = engine.lib
+        lib.hipMalloc.restype = C.c_int
+        lib.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        lib.hipFree.restype = C.c_int
+        lib.hipFree.argtypes = [C.c_void_p]
+        lib.hipMemcpy.restype = C.c_int
+        lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        p = C.c_void_p()
+        with engine.lock:
+            engine.check(lib.tpe_synchronize(engine.h))     # (makes the engine's device current)
+            rc = lib.hipMalloc(C.byref(p), max(self.nbytes, 1))
+        if rc != 0 or not p.value:
+            raise EngineError('hipMalloc of %d bytes failed (%d)' % (self.nbytes, rc))
+        self.ptr = p.value
+
+    def _copy(self, dst, src, nbytes, kind):
+        if nbytes > self.nbytes:
+            raise ValueError('copy of %d bytes exceeds the buffer (%d)' % (nbytes, self.nbytes))
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_synchronize(e.h))
+            rc = e.lib.hipMemcpy(dst, src, nbytes, kind)
+        if rc != 0:
+            raise EngineError('hipMemcpy failed (%d)' % rc)
+
+    def upload(self, arr):
+        arr = np.ascontiguousarray(arr)
+        self._copy(self.ptr, arr.ctypes.data, arr.nbytes, 1)     # hipMemcpyHostToDevice
+        return self
+
+    def download(self, out):
+        assert out.flags.c_contiguous
+        self._copy(out.ctypes.data, self.ptr, out.nbytes, 2)     # hipMemcpyDeviceToHost
+        return out
+
+    def close(self):
+        if getattr(self, 'ptr', None):
+            if getattr(self.engine, 'h', None):     # (a closed engine has released its device)
+                self.engine.lib.hipFree(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Plan(object):
@@ -588,6 +648,40 @@ class Plan(object):
                 self.p, int(hp), mode, _dp(x), x.size, _dp(lb) if want_llik else None,
                 _dp(la) if want_llik else None, C.byref(bi), C.byref(bs)))
         return lb, la, bi.value, bs.value
+
+    def score_points(self, vals, want_terms=False, want_active=False, stream=None):
+        """EI of M whole configurations under the last fit
+        (tpe_plan_score_points): ``vals`` float64 [n_hp, M] in the history's
+        columnar layout, values of inactive hps ignored (NaN allowed).
+        Returns total[M], or (total[, terms[n_hp, M]][, active[n_hp, M]
+        uint8]) with the ``want_`` flags: terms[i] = below_llik - above_llik
+        of hp i (+0.0 where inactive), total their sum in hp order."""
+        e = self.engine
+        vals = _f64(vals)
+        if vals.ndim != 2 or vals.shape[0] != self.n_hp:
+            raise ValueError('configurations must be a [n_hp, M] array')
+        m = vals.shape[1]
+        total = np.empty(m)
+        terms = np.empty((self.n_hp, m)) if want_terms else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_score_points(
+                self.p, vals.ctypes.data, m, m, total.ctypes.data,
+                terms.ctypes.data if want_terms else None,
+                active.ctypes.data if want_active else None, 0, stream))
+        out = (total,) + ((terms,) if want_terms else ()) + ((active,) if want_active else ())
+        return out[0] if len(out) == 1 else out
+
+    def score_points_device(self, vals_ptr, m, ld, total_ptr, terms_ptr=0, active_ptr=0,
+                            stream=None):
+        """The same on device memory (e.g. torch tensors' data_ptr()):
+        vals[n_hp][ld] float64, total[m], optional terms[n_hp][ld] float64 and
+        active[n_hp][ld] uint8.  Stream-ordered, no host synchronisation."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_score_points(
+                self.p, vals_ptr, int(m), int(ld), total_ptr, terms_ptr or None,
+                active_ptr or None, 1, stream))
 
     def profile(self, capacity):
         e = self.engine

@@ -102,6 +102,13 @@ struct tpe_plan : PlanShape {
   hipEvent_t ev_fork = nullptr, ev_join[8] = {};
   double *d_ext = nullptr, *d_lb = nullptr, *d_la = nullptr;
   size_t ext_cap = 0;
+  // tpe_plan_score_points scratch: [P][m] values (host mode), terms and
+  // activity (where the caller wants none back), [m] totals (host mode)
+  double *d_pt_vals = nullptr, *d_pt_terms = nullptr, *d_pt_total = nullptr;
+  uint8_t *d_pt_act = nullptr;
+  int32_t *d_pt_idx = nullptr;     // [P][m] each hp's active configurations, compacted
+  uint32_t *d_pt_count = nullptr;  // [P] their number
+  size_t pt_cap = 0;  // configurations the scratch holds
   double *d_cand = nullptr;
   int32_t *d_cpos = nullptr;
   size_t cand_cap = 0;
@@ -216,7 +223,8 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_ticket, p->d_sortbuf, p->d_census, p->d_lat_info, p->d_lat, p->d_coef32, p->d_coefm,
                   p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
                   p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt, p->d_tab_bound,
-                  p->d_tab_hot, p->d_draw_zone, p->d_screen_stats};
+                  p->d_tab_hot, p->d_draw_zone, p->d_screen_stats, p->d_pt_vals, p->d_pt_terms,
+                  p->d_pt_total, p->d_pt_act, p->d_pt_idx, p->d_pt_count};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -495,6 +503,26 @@ int ensure_ext(tpe_engine *h, tpe_plan *p, size_t n) {
     CKH(dalloc(&p->d_lb, n));
     CKH(dalloc(&p->d_la, n));
     p->ext_cap = n;
+  }
+  return TPE_OK;
+}
+
+// scratch of tpe_plan_score_points for m configurations (grows, never shrinks)
+int ensure_points(tpe_engine *h, tpe_plan *p, size_t m) {
+  if (m > p->pt_cap) {
+    dfree(p->d_pt_vals); dfree(p->d_pt_terms); dfree(p->d_pt_total); dfree(p->d_pt_act);
+    dfree(p->d_pt_idx);
+    p->d_pt_vals = p->d_pt_terms = p->d_pt_total = nullptr;
+    p->d_pt_act = nullptr;
+    p->d_pt_idx = nullptr;
+    p->pt_cap = 0;
+    CKH(dalloc(&p->d_pt_vals, m * p->P));
+    CKH(dalloc(&p->d_pt_terms, m * p->P));
+    CKH(dalloc(&p->d_pt_act, m * p->P));
+    CKH(dalloc(&p->d_pt_idx, m * p->P));
+    CKH(dalloc(&p->d_pt_total, m));
+    if (!p->d_pt_count) CKH(dalloc(&p->d_pt_count, (size_t)p->P));
+    p->pt_cap = m;
   }
   return TPE_OK;
 }
@@ -1781,6 +1809,76 @@ int tpe_plan_score_candidates_sorted(tpe_plan_t p, int32_t hp, int32_t mode, con
   CKH(hipStreamSynchronize(st));
   if (best_index) *best_index = r.index;
   if (best_score) *best_score = r.score;
+  return TPE_OK;
+}
+
+// Whole configurations under the last fit (tpe_points.hip).  Reads the fitted
+// tables only: the history, a pending history patch, d_results and every other
+// suggest state stay as they are.  Device mode enqueues three launches and
+// returns; host mode stages through the plan's scratch and waits for its own
+// stream only.
+int tpe_plan_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld, double *total,
+                          double *terms, uint8_t *active, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, "score_points: need 0 <= m <= ld");
+  if (m > 0 && (!vals || !total))
+    return fail(h, TPE_E_INVALID, "score_points: vals and total must not be null");
+  if (m > (int64_t)INT32_MAX) return fail(h, TPE_E_INVALID, "score_points: too many configurations");
+  if (m == 0) return TPE_OK;
+  if (p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, "score_points: the plan has not been fitted (tpe_plan_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    const int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+  PointsArgs a{};
+  a.idx = p->d_pt_idx;
+  a.count = p->d_pt_count;
+  a.hps = p->d_hps;
+  a.level_hps = p->d_level_hps;
+  a.cond_parent = p->d_cp;
+  a.cond_branch = p->d_cb;
+  a.info = p->d_info;
+  a.coef = p->d_coef;
+  a.kcap = p->kcap;
+  a.m = m;
+  a.n_hp = p->P;
+  if (dev) {
+    a.vals = vals;
+    a.ld = ld;
+    a.total = total;
+    a.terms = terms ? terms : p->d_pt_terms;
+    a.term_ld = terms ? ld : m;
+    a.active = active ? active : p->d_pt_act;
+    a.act_ld = active ? ld : m;
+    CKH(launch_points(a, st));
+    return TPE_OK;
+  }
+  if (ld == m)  // (contiguous: one plain copy)
+    CKH(hipMemcpyAsync(p->d_pt_vals, vals, (size_t)m * p->P * 8, hipMemcpyHostToDevice, st));
+  else
+    CKH(hipMemcpy2DAsync(p->d_pt_vals, (size_t)m * 8, vals, (size_t)ld * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyHostToDevice, st));
+  a.vals = p->d_pt_vals;
+  a.ld = m;
+  a.total = p->d_pt_total;
+  a.terms = p->d_pt_terms;
+  a.active = p->d_pt_act;
+  a.term_ld = a.act_ld = m;
+  CKH(launch_points(a, st));
+  CKH(hipMemcpyAsync(total, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (terms)
+    CKH(hipMemcpy2DAsync(terms, (size_t)ld * 8, p->d_pt_terms, (size_t)m * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyDeviceToHost, st));
+  if (active)
+    CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
+                         hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
   return TPE_OK;
 }
 

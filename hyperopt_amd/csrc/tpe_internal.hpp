@@ -656,4 +656,30 @@ struct PriorArgs {
 };
 hipError_t launch_prior(const PriorArgs &a, int32_t n_suggest, hipStream_t st);
 
+// EI of whole configurations under the fitted mixtures (tpe_points.hip,
+// tpe_plan_score_points): vals[n_hp][ld], m <= ld configurations
+struct PointsArgs {
+  const tpe_hp *hps;
+  const int32_t *level_hps;   // every hp id, level by level (parents first)
+  const int32_t *cond_parent;
+  const int32_t *cond_branch;
+  const MixInfo *info;        // [2*P]
+  const Coef *coef;           // [2*P][kcap]
+  int64_t kcap;
+  const double *vals;         // [P][ld]
+  int64_t m, ld;
+  uint8_t *active;            // [P][act_ld] out
+  double *terms;              // [P][term_ld] out (+0.0 where inactive)
+  double *total;              // [m] out
+  int64_t act_ld, term_ld;    // >= m
+  // per hp, its active configurations compacted into a dense list (scratch):
+  // k_points_active appends, k_score_points' waves take 64 entries each
+  int32_t *idx;               // [P][m] configuration indices
+  uint32_t *count;            // [P] entries per hp (zero before the call)
+  int32_t n_hp;
+  int32_t pad;
+};
+// k_points_active, k_score_points, k_points_sum in stream order
+hipError_t launch_points(const PointsArgs &a, hipStream_t st);
+
 }  // namespace tpe

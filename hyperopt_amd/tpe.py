@@ -213,6 +213,229 @@ def _suggest_numpy_stream(cs, plan, seed, n_ei):
 
 
 # --------------------------------------------------------------------------
+# whole configurations under the fitted model: score_configs / suggest_from_pool
+# --------------------------------------------------------------------------
+def config_columns(cs, configs):
+    """``configs`` as the history's columns: (vals[P, M] float64 in
+    ``cs.labels`` order with NaN for absent, present[P, M] bool).  Accepts a
+    sequence of ``{label: value}`` dicts (choices as option indices: what fmin
+    returns and space_eval takes; absent labels are inactive) or a float array
+    [P, M] with NaN for absent."""
+    P = len(cs.labels)
+    if isinstance(configs, np.ndarray):
+        vals = np.ascontiguousarray(configs, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[0] != P:
+            raise ValueError('a configuration array must be [%d, M] in domain.space.labels '
+                             'order' % P)
+        return vals, ~np.isnan(vals)
+    configs = list(configs)
+    vals = np.full((P, len(configs)), np.nan)
+    index = {lab: i for i, lab in enumerate(cs.labels)}
+    for j, cfg in enumerate(configs):
+        for lab, v in cfg.items():
+            i = index.get(lab)
+            if i is None:
+                raise ValueError('configuration %d: unknown label %r' % (j, lab))
+            vals[i, j] = float(v)
+    return vals, ~np.isnan(vals)
+
+
+def columns_to_configs(cs, vals, active):
+    """The ``{label: value}`` dicts of the columns' configurations (active
+    labels only; categorical values as ints)."""
+    vals, active = np.asarray(vals), np.asarray(active).astype(bool)
+    vl, al = vals.T.tolist(), active.T.tolist()
+    return [{lab: (int(round(v[i])) if cat else v[i]) for lab, i, cat in cs.pick_order if a[i]}
+            for v, a in zip(vl, al)]
+
+
+def active_columns(cs, vals):
+    """active[P, M] implied by the configurations' own values, as
+    ``CompiledSpace.is_active`` states it: an hp is active iff it has no
+    condition, or some condition has its parent active with value == branch
+    (vectorised over the configurations; what the engine derives on the
+    device)."""
+    hps, conds, _ = cs.engine_tables()
+    P, M = vals.shape
+    act = np.zeros((P, M), dtype=bool)
+    done = [False] * P
+
+    def visit(i):
+        if done[i]:
+            return
+        done[i] = True          # (conditions are acyclic: plan_build checks)
+        t = hps[i]
+        if t.cond_count == 0:
+            act[i] = True
+            return
+        for par, br in conds[t.cond_begin:t.cond_begin + t.cond_count]:
+            visit(par)
+            act[i] |= act[par] & (vals[par] == float(br))
+
+    for i in range(P):
+        visit(i)
+    return act
+
+
+def _check_consistent(cs, present, active):
+    """A dict's labels must be exactly the hps its own choices activate."""
+    bad = np.argwhere(present != np.asarray(active).astype(bool))
+    if len(bad):
+        i, j = (int(x) for x in bad[0])
+        raise ValueError('configuration %d: label %r is %s, but its choices make it %s'
+                         % (j, cs.labels[i], 'present' if present[i, j] else 'missing',
+                            'inactive' if present[i, j] else 'active'))
+
+
+def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma):
+    """Push the history and fit, exactly as ``suggest`` does (st.lock held)."""
+    engine = engine or E.default_engine()
+    plan = st.plan_for(domain, hist.n, engine)
+    hist.push(plan)
+    plan.fit(gamma=gamma, prior_weight=prior_weight, lf=DEFAULT_LF)
+    return plan
+
+
+def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
+                  gamma=_default_gamma, engine=None, return_terms=False):
+    """What the fitted TPE model thinks of configurations the caller holds.
+
+    The history of ``trials`` is synced, pushed and fitted as ``suggest``
+    does; every configuration c is then scored on the device as
+    ``EI(c) = sum over its active hps of below_llik(v) - above_llik(v)`` --
+    per hp the score the reference's broadcast_best ranks (tpe.py:749-759),
+    added in float64 in ``domain.space.labels`` order.  ``configs``: a
+    sequence of ``{label: value}`` dicts (absent labels inactive) or a float
+    array [P, M] (NaN for absent).  Returns EI[M]; with ``return_terms`` also
+    ``{label: term[M]}`` and ``{label: active[M]}``.  Non-finite lpdfs
+    propagate (nothing is clamped); an active categorical value that is not
+    an option index scores NaN.  ValueError: an empty history, or a dict whose
+    labels contradict the activity its own choices imply."""
+    cs = domain.space
+    as_dicts = not isinstance(configs, np.ndarray)
+    vals, present = config_columns(cs, configs)
+    st = _state(domain)
+    with st.lock:
+        hist = st.history(domain, trials).sync(trials)
+        if hist.n == 0:
+            raise ValueError('score_configs needs a history: trials holds no usable trial')
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
+        total, terms, active = plan.score_points(vals, want_terms=True, want_active=True)
+    if as_dicts:
+        _check_consistent(cs, present, active)
+    if not return_terms:
+        return total
+    return (total, {lab: terms[i] for i, lab in enumerate(cs.labels)},
+            {lab: active[i].astype(bool) for i, lab in enumerate(cs.labels)})
+
+
+class _Pool(object):
+    """A candidate pool as columns, with its host-derived activity."""
+
+    def __init__(self, cs, pool):
+        self.source = pool          # (keeps an array pool alive: the cache key is its identity)
+        self.vals, present = config_columns(cs, pool)
+        self.active = active_columns(cs, self.vals)
+        if not isinstance(pool, np.ndarray):
+            _check_consistent(cs, present, self.active)
+        self.m = self.vals.shape[1]
+        self._dev = None            # (engine, values, totals) device buffers of an array pool
+
+    def totals(self, plan):
+        """EI of every pool configuration under ``plan``'s fit."""
+        if not isinstance(self.source, np.ndarray) or self.m == 0:
+            return plan.score_points(self.vals)
+        # an array pool lives on the device: uploaded once, scored in place
+        eng = plan.engine
+        if self._dev is None or self._dev[0] is not eng:
+            self._dev = (eng, E.DeviceBuffer(eng, self.vals.nbytes).upload(self.vals),
+                         E.DeviceBuffer(eng, 8 * self.m))
+        _, v, out = self._dev
+        plan.score_points_device(v.ptr, self.m, self.m, out.ptr)
+        return out.download(np.empty(self.m))
+
+
+def _pool_for(st, cs, pool):
+    if not isinstance(pool, np.ndarray):
+        return _Pool(cs, pool)
+    p = getattr(st, 'pool', None)
+    if p is None or p.source is not pool:
+        p = st.pool = _Pool(cs, pool)
+    return p
+
+
+def _row_keys(vals, active):
+    """One opaque key per configuration: its activity and active values
+    (inactive slots and the sign of zero do not count)."""
+    canon = np.where(active, vals, 0.0) + 0.0
+    rows = np.ascontiguousarray(np.concatenate([canon.T, active.T.astype(np.float64)], axis=1))
+    return rows.view(np.dtype((np.void, rows.dtype.itemsize * rows.shape[1]))).ravel()
+
+
+def seen_in_history(pool_vals, pool_active, hist_vals, hist_active):
+    """seen[M]: pool configurations whose active values equal those of some
+    history row (vectorised over the columns)."""
+    if hist_vals.shape[1] == 0 or pool_vals.shape[1] == 0:
+        return np.zeros(pool_vals.shape[1], dtype=bool)
+    return np.isin(_row_keys(pool_vals, pool_active),
+                   _row_keys(hist_vals, np.asarray(hist_active).astype(bool)))
+
+
+def rank_pool(total, eligible, k):
+    """The k eligible pool indices of highest EI: ties to the lower index,
+    NaN totals last."""
+    idx = np.flatnonzero(eligible)
+    t = total[idx]
+    nan = np.isnan(t)
+    order = np.lexsort((idx, -np.where(nan, 0.0, t), nan))
+    return idx[order[:k]]
+
+
+def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
+                      prior_weight=_default_prior_weight,
+                      n_startup_jobs=_default_n_startup_jobs,
+                      gamma=_default_gamma, skip_seen=True, engine=None):
+    """``algo=`` for a constrained or discrete search: the next trials are the
+    ``len(new_ids)`` configurations of ``pool`` the fitted model scores
+    highest (``score_configs``' EI), distinct, ties to the lower pool index,
+    NaN scores last.  Use as ``functools.partial(tpe.suggest_from_pool,
+    pool=...)``.  ``pool`` takes ``score_configs``' two formats; an array is
+    converted and uploaded once per domain (cached on the array's identity).
+    ``skip_seen`` drops pool configurations whose active values equal those of
+    a trial already in the history.  While the history has fewer than
+    ``n_startup_jobs`` trials the picks are ``np.random.RandomState(seed)
+    .choice(M, k, replace=False)`` over the whole pool.  ValueError when fewer
+    than ``len(new_ids)`` eligible configurations remain."""
+    new_ids = list(new_ids)
+    if not new_ids:
+        return []
+    if pool is None:
+        raise TypeError('suggest_from_pool needs pool=')
+    cs = domain.space
+    st = _state(domain)
+    k = len(new_ids)
+    with st.lock:
+        pl = _pool_for(st, cs, pool)
+        hist = st.history(domain, trials).sync(trials)
+        if hist.n < n_startup_jobs:
+            if pl.m < k:
+                raise ValueError('the pool holds %d configurations, %d asked for' % (pl.m, k))
+            picks = np.random.RandomState(seed).choice(pl.m, k, replace=False)
+        else:
+            eligible = np.ones(pl.m, dtype=bool)
+            if skip_seen:
+                eligible &= ~seen_in_history(pl.vals, pl.active, hist.vals[:, :hist.n],
+                                             hist.active[:, :hist.n])
+            if int(eligible.sum()) < k:
+                raise ValueError('%d eligible pool configurations remain, %d asked for'
+                                 % (int(eligible.sum()), k))
+            plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
+            picks = rank_pool(pl.totals(plan), eligible, k)
+    chosen = columns_to_configs(cs, pl.vals[:, picks], pl.active[:, picks])
+    return [_new_doc(domain, trials, cs, i, c) for i, c in zip(new_ids, chosen)]
+
+
+# --------------------------------------------------------------------------
 # operator-level drop-ins for the reference's scope functions (GPU-backed)
 # --------------------------------------------------------------------------
 def _eng():

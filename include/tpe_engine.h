@@ -271,6 +271,25 @@ int tpe_plan_score_candidates_sorted(tpe_plan_t p, int32_t hp, int32_t mode,
                                      double *llik_a, int64_t *best_index,
                                      double *best_score);
 
+/* EI of M whole configurations under the last tpe_plan_fit: vals[n_hp][ld]
+ * (the history's layout).  total[M]; terms[n_hp][ld] and active[n_hp][ld]
+ * may be NULL.  on_device != 0: all pointers are device memory and the call
+ * is stream-ordered like every plan call; else host buffers, synchronous.
+ * A configuration's active set follows the space's condition tables from its
+ * own values (an hp is active iff it has no condition, or some condition's
+ * parent is active with value == branch); values of inactive hps are ignored.
+ * terms[i][c] = below_llik - above_llik of hp i at its value (the score
+ * broadcast_best ranks, tpe.py:749-759), +0.0 where inactive; total[c] = the
+ * terms of c added in ascending hp index.  Non-finite lpdfs propagate as IEEE
+ * arithmetic does; an active categorical value that is not an integer in
+ * [0, upper) gives a NaN term and total and activates no child.
+ * TPE_E_INVALID: m < 0, ld < m, null vals / total with m > 0, or a plan that
+ * has not been fitted; m == 0 touches nothing.  The results of the last
+ * suggest and the history are not disturbed.                               */
+int tpe_plan_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                          double *total, double *terms, uint8_t *active,
+                          int32_t on_device, void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
