@@ -15,5 +15,6 @@ from .workers import ThreadTrials  # noqa: F401
 from .expr import scope  # noqa: F401
 from . import hp, rand, tpe, anneal, mix  # noqa: F401
 from .tpe import score_configs, suggest_from_pool  # noqa: F401
+from .tpe import sample_configs, suggest_joint  # noqa: F401
 
 __version__ = '0.1.0'

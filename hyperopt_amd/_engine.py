@@ -45,6 +45,7 @@ EXPORTS = (
     'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
     'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
     'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats', 'tpe_plan_score_points',
+    'tpe_plan_sample_points', 'tpe_plan_topk_points', 'tpe_plan_gather_points',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -154,6 +155,9 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_score_candidates_sorted': (C.c_int, [vp, i32, i32, _D, i64, _D, _D,
                                                            C.POINTER(i64), _D]),
             'tpe_plan_score_points': (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp]),
+            'tpe_plan_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, i32, vp]),
+            'tpe_plan_topk_points': (C.c_int, [vp, vp, vp, i64, i32, vp, i32, vp]),
+            'tpe_plan_gather_points': (C.c_int, [vp, vp, i64, vp, i32, vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -682,6 +686,84 @@ class Plan(object):
             e.check(e.lib.tpe_plan_score_points(
                 self.p, vals_ptr, int(m), int(ld), total_ptr, terms_ptr or None,
                 active_ptr or None, 1, stream))
+
+    def sample_points(self, seed, m, begin=0, want_terms=False, want_active=False, stream=None):
+        """``m`` whole configurations drawn from the below mixtures of the
+        last fit, with their EI (tpe_plan_sample_points): configuration j is
+        draw ``begin + j`` under Philox key ``seed``.  Returns (vals[n_hp, m]
+        with NaN where inactive, total[m][, terms[n_hp, m]][, active[n_hp, m]
+        uint8]) -- vals is a pool array, the rest what ``score_points``
+        returns for it."""
+        e = self.engine
+        m = int(m)
+        if m < 0:
+            raise ValueError('the number of configurations must not be negative')
+        vals = np.empty((self.n_hp, m))
+        total = np.empty(m)
+        terms = np.empty((self.n_hp, m)) if want_terms else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), m, m, vals.ctypes.data,
+                total.ctypes.data, terms.ctypes.data if want_terms else None,
+                active.ctypes.data if want_active else None, 0, stream))
+        return (vals, total) + ((terms,) if want_terms else ()) + ((active,) if want_active else ())
+
+    def sample_points_device(self, seed, begin, m, ld, vals_ptr, total_ptr, terms_ptr=0,
+                             active_ptr=0, stream=None):
+        """The same into device memory: vals[n_hp][ld] float64, total[m],
+        optional terms[n_hp][ld] float64 and active[n_hp][ld] uint8.
+        Stream-ordered, no host synchronisation."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
+                total_ptr, terms_ptr or None, active_ptr or None, 1, stream))
+
+    def topk_points(self, total, k, eligible=None, m=None, out=None, stream=None):
+        """The ``k`` eligible entries that rank first, as ``tpe.rank_pool``
+        ranks them (tpe_plan_topk_points).  Host arrays ``total[m]`` /
+        ``eligible[m]`` return an int32 array [k]; with ``m`` given, ``total``,
+        ``eligible`` (0: none) and ``out`` are device pointers and the picks
+        stay on the device."""
+        e = self.engine
+        if m is not None:
+            with e.lock:
+                e.check(e.lib.tpe_plan_topk_points(self.p, total, eligible or None, int(m), int(k),
+                                                   out, 1, stream))
+            return None
+        total = _f64(total).ravel()
+        el = None if eligible is None else np.ascontiguousarray(
+            np.asarray(eligible).ravel() != 0, dtype=np.uint8)
+        if el is not None and el.size != total.size:
+            raise ValueError('eligible must have one entry per total')
+        idx = np.empty(max(int(k), 0), dtype=np.int32)
+        with e.lock:
+            e.check(e.lib.tpe_plan_topk_points(
+                self.p, total.ctypes.data, None if el is None else el.ctypes.data, total.size,
+                int(k), idx.ctypes.data, 0, stream))
+        return idx
+
+    def gather_points(self, vals, idx, k=None, ld=None, out=None, stream=None):
+        """The columns ``idx`` of ``vals`` (tpe_plan_gather_points): host
+        arrays vals[n_hp, ld] / idx[k] return [n_hp, k]; with ``k`` and ``ld``
+        given, ``vals``, ``idx`` and ``out`` are device pointers."""
+        e = self.engine
+        if k is not None:
+            with e.lock:
+                e.check(e.lib.tpe_plan_gather_points(self.p, vals, int(ld), idx, int(k), out, 1,
+                                                     stream))
+            return None
+        vals = _f64(vals)
+        if vals.ndim != 2 or vals.shape[0] != self.n_hp:
+            raise ValueError('configurations must be a [n_hp, M] array')
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        res = np.empty((self.n_hp, idx.size))
+        with e.lock:
+            e.check(e.lib.tpe_plan_gather_points(self.p, vals.ctypes.data, vals.shape[1],
+                                                 idx.ctypes.data, idx.size, res.ctypes.data, 0,
+                                                 stream))
+        return res
 
     def profile(self, capacity):
         e = self.engine

@@ -109,6 +109,11 @@ struct tpe_plan : PlanShape {
   int32_t *d_pt_idx = nullptr;     // [P][m] each hp's active configurations, compacted
   uint32_t *d_pt_count = nullptr;  // [P] their number
   size_t pt_cap = 0;  // configurations the scratch holds
+  // tpe_plan_sample_points: [P] draw tables of the below mixtures;
+  // tpe_plan_topk_points: the select's histograms and staging, [kTopkMax] picks
+  void *d_pt_tab = nullptr;
+  void *d_tk = nullptr;
+  int32_t *d_tk_idx = nullptr;
   double *d_cand = nullptr;
   int32_t *d_cpos = nullptr;
   size_t cand_cap = 0;
@@ -224,7 +229,8 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
                   p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt, p->d_tab_bound,
                   p->d_tab_hot, p->d_draw_zone, p->d_screen_stats, p->d_pt_vals, p->d_pt_terms,
-                  p->d_pt_total, p->d_pt_act, p->d_pt_idx, p->d_pt_count};
+                  p->d_pt_total, p->d_pt_act, p->d_pt_idx, p->d_pt_count, p->d_pt_tab, p->d_tk,
+                  p->d_tk_idx};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -524,6 +530,13 @@ int ensure_points(tpe_engine *h, tpe_plan *p, size_t m) {
     if (!p->d_pt_count) CKH(dalloc(&p->d_pt_count, (size_t)p->P));
     p->pt_cap = m;
   }
+  return TPE_OK;
+}
+
+// scratch of tpe_plan_topk_points (fixed size, allocated by the first call)
+int ensure_topk(tpe_engine *h, tpe_plan *p) {
+  if (!p->d_tk) CKH(hipMalloc(&p->d_tk, topk_scratch_bytes()));
+  if (!p->d_tk_idx) CKH(dalloc(&p->d_tk_idx, (size_t)kTopkMax));
   return TPE_OK;
 }
 
@@ -1879,6 +1892,150 @@ int tpe_plan_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t l
     CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
                          hipMemcpyDeviceToHost, st));
   CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+// Whole configurations drawn from the below mixtures of the last fit and
+// scored (tpe_sample_points.hip, then tpe_points.hip's scoring launches).
+// Reads d_info, d_coef and the mixtures only, as tpe_plan_score_points does.
+int tpe_plan_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m, int64_t ld,
+                           double *vals, double *total, double *terms, uint8_t *active,
+                           int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, "sample_points: need 0 <= m <= ld");
+  if (begin < 0) return fail(h, TPE_E_INVALID, "sample_points: begin must not be negative");
+  if (m > 0 && (!vals || !total))
+    return fail(h, TPE_E_INVALID, "sample_points: vals and total must not be null");
+  if (m > (int64_t)INT32_MAX) return fail(h, TPE_E_INVALID, "sample_points: too many configurations");
+  if (m == 0) return TPE_OK;
+  if (p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, "sample_points: the plan has not been fitted (tpe_plan_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    const int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  if (!p->d_pt_tab) CKH(hipMalloc(&p->d_pt_tab, sample_tables_bytes(p->P)));
+  CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+  SampleArgs s{};
+  PointsArgs &a = s.P;
+  a.idx = p->d_pt_idx;
+  a.count = p->d_pt_count;
+  a.hps = p->d_hps;
+  a.level_hps = p->d_level_hps;
+  a.cond_parent = p->d_cp;
+  a.cond_branch = p->d_cb;
+  a.info = p->d_info;
+  a.coef = p->d_coef;
+  a.kcap = p->kcap;
+  a.m = m;
+  a.n_hp = p->P;
+  s.mw = p->d_mw;
+  s.mmu = p->d_mmu;
+  s.msig = p->d_msig;
+  s.tab = static_cast<DrawTableT<kTabCap> *>(p->d_pt_tab);
+  s.seed = seed;
+  s.begin = begin;
+  if (dev) {
+    s.out = vals;
+    a.vals = vals;
+    a.ld = ld;
+    a.total = total;
+    a.terms = terms ? terms : p->d_pt_terms;
+    a.term_ld = terms ? ld : m;
+    a.active = active ? active : p->d_pt_act;
+    a.act_ld = active ? ld : m;
+    CKH(launch_sample_points(s, st));
+    return TPE_OK;
+  }
+  s.out = p->d_pt_vals;
+  a.vals = p->d_pt_vals;
+  a.ld = m;
+  a.total = p->d_pt_total;
+  a.terms = p->d_pt_terms;
+  a.active = p->d_pt_act;
+  a.term_ld = a.act_ld = m;
+  CKH(launch_sample_points(s, st));
+  CKH(hipMemcpy2DAsync(vals, (size_t)ld * 8, p->d_pt_vals, (size_t)m * 8, (size_t)m * 8,
+                       (size_t)p->P, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(total, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (terms)
+    CKH(hipMemcpy2DAsync(terms, (size_t)ld * 8, p->d_pt_terms, (size_t)m * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyDeviceToHost, st));
+  if (active)
+    CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
+                         hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+// The k best eligible totals (tpe_topk.hip).  With a mask the call waits for
+// the first pass to learn how many entries are eligible.
+int tpe_plan_topk_points(tpe_plan_t p, const double *total, const uint8_t *eligible, int64_t m,
+                         int32_t k, int32_t *idx, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (k < 1 || k > kTopkMax) return fail(h, TPE_E_INVALID, "topk_points: need 1 <= k <= 4096");
+  if (m < 0 || m > (int64_t)INT32_MAX)
+    return fail(h, TPE_E_INVALID, "topk_points: need 0 <= m <= 2^31 - 1");
+  if (!idx || (m > 0 && !total))
+    return fail(h, TPE_E_INVALID, "topk_points: total and idx must not be null");
+  if (m < k) return fail(h, TPE_E_INVALID, "topk_points: fewer than k eligible entries");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  int rc = ensure_topk(h, p);
+  if (rc) return rc;
+  const double *d_total = total;
+  const uint8_t *d_elig = eligible;
+  if (!dev) {
+    rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+    CKH(hipMemcpyAsync(p->d_pt_total, total, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    if (eligible)
+      CKH(hipMemcpyAsync(p->d_pt_act, eligible, (size_t)m, hipMemcpyHostToDevice, st));
+    d_total = p->d_pt_total;
+    d_elig = eligible ? p->d_pt_act : nullptr;
+  }
+  CKH(launch_topk_first(d_total, d_elig, m, k, p->d_tk, st));
+  if (d_elig) {
+    // (the first pass's histogram is the first member of the scratch)
+    uint32_t hist[256];
+    CKH(hipMemcpyAsync(hist, p->d_tk, sizeof(hist), hipMemcpyDeviceToHost, st));
+    CKH(hipStreamSynchronize(st));
+    int64_t n = 0;
+    for (uint32_t c : hist) n += c;
+    if (n < k) return fail(h, TPE_E_INVALID, "topk_points: fewer than k eligible entries");
+  }
+  CKH(launch_topk_rest(d_total, d_elig, m, k, p->d_tk, dev ? idx : p->d_tk_idx, st));
+  if (!dev) {
+    CKH(hipMemcpyAsync(idx, p->d_tk_idx, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    CKH(hipStreamSynchronize(st));
+  }
+  return TPE_OK;
+}
+
+// out[n_hp][k] = the columns idx[0..k) of vals[n_hp][ld]
+int tpe_plan_gather_points(tpe_plan_t p, const double *vals, int64_t ld, const int32_t *idx,
+                           int32_t k, double *out, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (k < 0 || ld < 0) return fail(h, TPE_E_INVALID, "gather_points: need k >= 0 and ld >= 0");
+  if (k == 0) return TPE_OK;
+  if (!vals || !idx || !out)
+    return fail(h, TPE_E_INVALID, "gather_points: vals, idx and out must not be null");
+  if (on_device) {
+    CKH(hipSetDevice(h->device));
+    CKH(launch_gather_points(vals, ld, p->P, idx, k, out, pick_stream(h, stream)));
+    return TPE_OK;
+  }
+  for (int32_t j = 0; j < k; ++j)
+    if (idx[j] < 0 || idx[j] >= ld) return fail(h, TPE_E_INDEX, "gather_points: index out of range");
+  for (int32_t i = 0; i < p->P; ++i)
+    for (int32_t j = 0; j < k; ++j) out[(int64_t)i * k + j] = vals[(int64_t)i * ld + idx[j]];
   return TPE_OK;
 }
 

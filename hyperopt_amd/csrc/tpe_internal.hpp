@@ -681,5 +681,35 @@ struct PointsArgs {
 };
 // k_points_active, k_score_points, k_points_sum in stream order
 hipError_t launch_points(const PointsArgs &a, hipStream_t st);
+// k_score_points, k_points_sum alone (the caller's launch wrote the lists)
+hipError_t launch_points_score(const PointsArgs &a, hipStream_t st);
+
+// Whole configurations drawn from the fitted below mixtures and scored
+// (tpe_sample_points.hip, tpe_plan_sample_points): P.vals == out
+template <int CAP> struct DrawTableT;
+struct SampleArgs {
+  PointsArgs P;
+  double *out;                 // [P][ld] the drawn values (NaN where inactive)
+  const double *mw, *mmu, *msig;  // [2*P][kcap] the fitted mixtures
+  DrawTableT<kTabCap> *tab;    // [P] draw tables of the below mixtures (scratch)
+  uint64_t seed;               // Philox key; the stream is the hp, the offset begin + j
+  int64_t begin;
+};
+size_t sample_tables_bytes(int32_t n_hp);
+// k_sample_tables, k_sample_points, then launch_points_score
+hipError_t launch_sample_points(const SampleArgs &s, hipStream_t st);
+
+// Device top-k of totals and the gather of the picked columns (tpe_topk.hip;
+// tpe_plan_topk_points, tpe_plan_gather_points)
+constexpr int kTopkMax = 4096;
+constexpr int kTopkPasses = 12;  // 8-bit digits of the 96-bit (key, ~index)
+size_t topk_scratch_bytes();
+// pass 0 alone (its histogram holds the eligible count), then the rest
+hipError_t launch_topk_first(const double *total, const uint8_t *eligible, int64_t m, int32_t k,
+                             void *scratch, hipStream_t st);
+hipError_t launch_topk_rest(const double *total, const uint8_t *eligible, int64_t m, int32_t k,
+                            void *scratch, int32_t *idx, hipStream_t st);
+hipError_t launch_gather_points(const double *vals, int64_t ld, int32_t n_hp, const int32_t *idx,
+                                int32_t k, double *out, hipStream_t st);
 
 }  // namespace tpe

@@ -206,4 +206,13 @@ hipError_t launch_points(const PointsArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// the two scoring launches alone, behind a launch that has written the
+// activity, the inactive terms and the lists itself (tpe_sample_points.hip)
+hipError_t launch_points_score(const PointsArgs &a, hipStream_t st) {
+  const unsigned gx = (unsigned)((a.m + kPtThreads - 1) / kPtThreads);
+  k_score_points<<<dim3(gx, (unsigned)a.n_hp), dim3(kPtThreads), 0, st>>>(a);
+  k_points_sum<<<dim3(gx), dim3(kPtThreads), 0, st>>>(a);
+  return hipGetLastError();
+}
+
 }  // namespace tpe

@@ -436,6 +436,206 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
 
 
 # --------------------------------------------------------------------------
+# whole configurations drawn from the fitted model: sample_configs / suggest_joint
+# --------------------------------------------------------------------------
+_default_n_configs = 4096
+TOPK_MAX = 4096             # tpe_plan_topk_points' largest k
+STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
+
+
+def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
+                   gamma=_default_gamma, engine=None, begin=0, as_dicts=False):
+    """``n`` whole configurations drawn from the fitted model's *below*
+    mixtures, each with its joint EI (``score_configs``' total of it).
+
+    The history is synced, pushed and fitted as ``suggest`` does; the device
+    then draws every configuration parents first -- a conditional hp only
+    under the branch drawn for its parent -- and scores it
+    (tpe_plan_sample_points).  Configuration j is draw ``begin + j`` of the
+    Philox key ``batch_seeds(seed, 1)[0]``, so calls that split a range give
+    the numbers of one call.  Returns (vals[P, n] in ``domain.space.labels``
+    order with NaN for inactive -- a pool array -- , ei[n]); with ``as_dicts``
+    the configurations as ``{label: value}`` dicts instead.  ValueError on an
+    empty history."""
+    cs = domain.space
+    st = _state(domain)
+    with st.lock:
+        hist = st.history(domain, trials).sync(trials)
+        if hist.n == 0:
+            raise ValueError('sample_configs needs a history: trials holds no usable trial')
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
+        vals, total = plan.sample_points(batch_seeds(seed, 1)[0], int(n), begin=int(begin))
+    if as_dicts:
+        return columns_to_configs(cs, vals, ~np.isnan(vals)), total
+    return vals, total
+
+
+def _joint_walk(keys, seen, k, complete):
+    """suggest_joint's selection over configurations in rank order: ``keys``
+    their row keys, ``seen`` those equal to a history row.  Accept a
+    configuration unless it is seen or equals an accepted one, until ``k``
+    are accepted; when the walk ends short, fill from the rejected duplicates
+    of accepted ones in rank order.  Returns the picked positions; None when
+    short and the walk was over a prefix only (``complete`` False); ValueError
+    when short over all of them."""
+    picks, dups, taken = [], [], set()
+    for j in range(len(keys)):
+        if seen[j]:
+            continue
+        kb = keys[j].tobytes()
+        if kb in taken:
+            dups.append(j)
+            continue
+        taken.add(kb)
+        picks.append(j)
+        if len(picks) == k:
+            return picks
+    if not complete:
+        return None
+    picks += dups[:k - len(picks)]
+    if len(picks) < k:
+        raise ValueError('the draw holds %d selectable configurations, %d asked for'
+                         % (len(picks), k))
+    return picks
+
+
+def joint_select(total, eligible, vals, hist_vals, hist_active, k, skip_seen=True):
+    """The indices ``suggest_joint`` picks from drawn configurations
+    ``vals[P, n]`` (NaN for inactive) with EI ``total[n]``: the eligible ones
+    walked in ``rank_pool`` order under ``_joint_walk``'s rule, equality
+    being ``_row_keys``' (active values; the sign of zero does not count)."""
+    n = vals.shape[1]
+    eligible = np.ones(n, dtype=bool) if eligible is None else np.asarray(eligible, dtype=bool)
+    order = rank_pool(np.asarray(total), eligible, n)
+    v = vals[:, order]
+    act = ~np.isnan(v)
+    seen = (seen_in_history(v, act, hist_vals, hist_active) if skip_seen
+            else np.zeros(order.size, dtype=bool))
+    return order[_joint_walk(_row_keys(v, act), seen, k, True)]
+
+
+def _feasible_mask(feasible, cs, vals):
+    """``feasible({label: column[n]})`` checked: a bool array [n]."""
+    n = vals.shape[1]
+    r = feasible({lab: vals[i] for i, lab in enumerate(cs.labels)})
+    r = np.asarray(r)
+    if r.dtype != np.bool_ or r.shape != (n,):
+        raise ValueError('feasible must return a bool array of shape (%d,), got %s %s'
+                         % (n, r.dtype, r.shape))
+    return r
+
+
+def _joint_startup(new_ids, domain, trials, seed, feasible, startup_stream):
+    """Prior rounds of len(new_ids) draws until enough satisfy ``feasible``."""
+    cs = domain.space
+    k = len(new_ids)
+    kept = []
+    for r in range(STARTUP_ROUNDS):
+        sd = batch_seeds(seed, r + 1)[r]
+        if startup_stream == 'numpy' and r > 0:
+            sd %= 2 ** 32       # (RandomState takes 32 bits; round 0 is ``seed`` as given)
+        docs = rand.suggest(new_ids, domain, trials, sd, rng_stream=startup_stream)
+        cfgs = [{lab: v[0] for lab, v in d['misc']['vals'].items() if v} for d in docs]
+        ok = _feasible_mask(feasible, cs, config_columns(cs, cfgs)[0])
+        kept += [c for c, good in zip(cfgs, ok) if good]
+        if len(kept) >= k:
+            return [_new_doc(domain, trials, cs, i, c) for i, c in zip(new_ids, kept)]
+    raise ValueError('%d prior rounds gave %d feasible configurations, %d asked for'
+                     % (STARTUP_ROUNDS, len(kept), k))
+
+
+def _joint_buffers(st, engine, P, n):
+    """The device arrays of a joint draw, kept per domain: values [P, n],
+    totals [n], mask [n], picks [TOPK_MAX] and their columns [P, TOPK_MAX]."""
+    b = getattr(st, 'joint', None)
+    if b is None or b[0] is not engine or b[1] != (P, n):
+        mk = lambda nbytes: E.DeviceBuffer(engine, nbytes)   # noqa: E731
+        b = st.joint = (engine, (P, n), mk(8 * P * n), mk(8 * n), mk(n), mk(4 * TOPK_MAX),
+                        mk(8 * P * TOPK_MAX))
+    return b[2:]
+
+
+def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, feasible=None,
+                  skip_seen=True, prior_weight=_default_prior_weight,
+                  n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
+                  startup_stream='numpy', engine=None):
+    """``algo=`` that ranks whole configurations: one fit, one draw of
+    ``n_configs`` configurations from the fitted model (``sample_configs``)
+    and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
+    ranked together with the children it activates, a batch is the k best of
+    one draw.  Use as ``functools.partial(tpe.suggest_joint, ...)``.
+
+    ``feasible``: a predicate over the whole draw, called once as
+    ``feasible({label: column[n_configs]})`` (NaN where inactive); it must
+    return a bool array [n_configs], and only configurations it accepts are
+    picked.  Selection: the eligible configurations in ``rank_pool`` order
+    (highest EI first, ties to the lower draw index, NaN last); one is taken
+    unless its active values equal those of one already taken or, with
+    ``skip_seen``, of a history row; when fewer than k remain, duplicates of
+    taken ones fill the rest in rank order; ValueError when that is short
+    too.  The ranking and the gather run on the device (tpe_plan_topk_points,
+    tpe_plan_gather_points) over a few multiples of k, with the full host
+    ranking behind them when duplicates exhaust those.
+
+    While the history has fewer than ``n_startup_jobs`` trials the documents
+    come from ``rand.suggest`` as in ``suggest``; under ``feasible``, from
+    rounds of it with seeds ``batch_seeds(seed, r + 1)[r]`` (the 'numpy'
+    stream takes their low 32 bits from round 1 on: RandomState holds no
+    more), the feasible draws kept in order (at most 100 rounds, else
+    ValueError)."""
+    new_ids = list(new_ids)
+    if not new_ids:
+        return []
+    cs = domain.space
+    st = _state(domain)
+    k = len(new_ids)
+    n = int(n_configs)
+    with st.lock:
+        hist = st.history(domain, trials).sync(trials)
+        startup = hist.n < n_startup_jobs
+    if startup:
+        if feasible is None:
+            return rand.suggest(new_ids, domain, trials, seed, rng_stream=startup_stream)
+        return _joint_startup(new_ids, domain, trials, seed, feasible, startup_stream)
+    if n < k:
+        raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
+    P = len(cs.labels)
+    with st.lock:
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
+        d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
+        plan.sample_points_device(batch_seeds(seed, 1)[0], 0, n, n, d_vals.ptr, d_total.ptr)
+        vals = eligible = None
+        n_el = n
+        if feasible is not None:
+            vals = d_vals.download(np.empty((P, n)))
+            eligible = _feasible_mask(feasible, cs, vals)
+            d_mask.upload(eligible.astype(np.uint8))
+            n_el = int(eligible.sum())
+        hv, ha = hist.vals[:, :hist.n], hist.active[:, :hist.n]
+        chosen = None
+        kk = min(n_el, TOPK_MAX, max(4 * k, 64))
+        if k <= kk:
+            plan.topk_points(d_total.ptr, kk, eligible=None if eligible is None else d_mask.ptr,
+                             m=n, out=d_idx.ptr)
+            plan.gather_points(d_vals.ptr, d_idx.ptr, k=kk, ld=n, out=d_cols.ptr)
+            cols = d_cols.download(np.empty((P, kk)))
+            act = ~np.isnan(cols)
+            seen = (seen_in_history(cols, act, hv, ha) if skip_seen
+                    else np.zeros(kk, dtype=bool))
+            pos = _joint_walk(_row_keys(cols, act), seen, k, kk == n_el)
+            if pos is not None:
+                chosen = cols[:, pos]
+        if chosen is None:
+            # duplicates exhausted the device's picks: the rule over the whole draw
+            if vals is None:
+                vals = d_vals.download(np.empty((P, n)))
+            total = d_total.download(np.empty(n))
+            chosen = vals[:, joint_select(total, eligible, vals, hv, ha, k, skip_seen)]
+    cfgs = columns_to_configs(cs, chosen, ~np.isnan(chosen))
+    return [_new_doc(domain, trials, cs, i, c) for i, c in zip(new_ids, cfgs)]
+
+
+# --------------------------------------------------------------------------
 # operator-level drop-ins for the reference's scope functions (GPU-backed)
 # --------------------------------------------------------------------------
 def _eng():

@@ -290,6 +290,47 @@ int tpe_plan_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t l
                           double *total, double *terms, uint8_t *active,
                           int32_t on_device, void *stream);
 
+/* Draw m whole configurations from the below mixtures of the last
+ * tpe_plan_fit and score them: vals[n_hp][ld], total[m], and optional
+ * terms[n_hp][ld] / active[n_hp][ld], laid out as tpe_plan_score_points lays
+ * them out (entries m..ld of a row are not touched).  Configuration j has
+ * index c = begin + j.  The hps are visited parents first; an hp is active iff
+ * it has no condition, or some condition's parent is active with a drawn value
+ * equal to the branch.  An active hp takes, bit for bit, the value tpe_sample
+ * returns for its below mixture with Philox key `seed`, stream = the hp's
+ * index and offset c; an inactive one is NaN, so vals is a pool array for
+ * tpe_plan_score_points.  total, terms and active are what
+ * tpe_plan_score_points returns for the drawn vals, bit for bit.  The draws
+ * depend on (seed, hp, c) only: any split of [begin, begin + m) into calls
+ * gives the same numbers.  on_device != 0: device pointers, stream-ordered, no
+ * host synchronisation; else host buffers, synchronous.  TPE_E_INVALID: m < 0,
+ * ld < m, begin < 0, null vals / total with m > 0, or a plan that has not
+ * been fitted; m == 0 touches nothing.  The history, a pending history update
+ * and the results of the last suggest are not disturbed.                    */
+int tpe_plan_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m,
+                           int64_t ld, double *vals, double *total, double *terms,
+                           uint8_t *active, int32_t on_device, void *stream);
+
+/* idx[0..k): the k eligible entries of total[m] that rank first -- highest
+ * total first, ties to the lower index (-0.0 == +0.0), +inf above and -inf
+ * below every finite total, NaN last (NaN entries by index).  eligible[m]
+ * (bytes, non-zero = eligible) may be NULL: every entry.  1 <= k <= 4096,
+ * m <= 2^31 - 1.  The selection is a radix select on integer keys: the same
+ * result for every launch shape, no floating-point atomics.  TPE_E_INVALID:
+ * k or m out of range, null total / idx, or fewer than k eligible entries
+ * (with a mask the call waits for the device's count of them, in device mode
+ * too).  on_device as above.                                                */
+int tpe_plan_topk_points(tpe_plan_t p, const double *total, const uint8_t *eligible,
+                         int64_t m, int32_t k, int32_t *idx, int32_t on_device,
+                         void *stream);
+
+/* out[n_hp][k] = the columns idx[0..k) of vals[n_hp][ld].  on_device as above;
+ * host mode fails with TPE_E_INDEX on an index outside [0, ld), device mode
+ * writes NaN for it.  k == 0 touches nothing.                               */
+int tpe_plan_gather_points(tpe_plan_t p, const double *vals, int64_t ld,
+                           const int32_t *idx, int32_t k, double *out,
+                           int32_t on_device, void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
