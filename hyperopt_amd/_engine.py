@@ -46,6 +46,8 @@ EXPORTS = (
     'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
     'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats', 'tpe_plan_score_points',
     'tpe_plan_sample_points', 'tpe_plan_topk_points', 'tpe_plan_gather_points',
+    'tpe_plan_joint_fit', 'tpe_plan_joint_get_mixture', 'tpe_plan_joint_score_points',
+    'tpe_plan_joint_sides', 'tpe_plan_joint_sample_points',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -157,6 +159,13 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_score_points': (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp]),
             'tpe_plan_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, i32, vp]),
             'tpe_plan_topk_points': (C.c_int, [vp, vp, vp, i64, i32, vp, i32, vp]),
+            'tpe_plan_joint_fit': (C.c_int, [vp, vp]),
+            'tpe_plan_joint_get_mixture': (C.c_int, [vp, i32, i32, _D, _D, _D, vp, i64,
+                                                     C.POINTER(i64)]),
+            'tpe_plan_joint_score_points': (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, i32, vp]),
+            'tpe_plan_joint_sides': (C.c_int, [vp, vp, vp, i64]),
+            'tpe_plan_joint_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, vp,
+                                                       vp, i32, vp]),
             'tpe_plan_gather_points': (C.c_int, [vp, vp, i64, vp, i32, vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
@@ -719,6 +728,115 @@ class Plan(object):
             e.check(e.lib.tpe_plan_sample_points(
                 self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
                 total_ptr, terms_ptr or None, active_ptr or None, 1, stream))
+
+    # ---- multivariate TPE: the joint model over the root hps (tpe_plan_joint_*)
+    def joint_fit(self, stream=None):
+        """Build the joint Parzen model over the unconditional hps from the
+        last ``fit`` (tpe_plan_joint_fit); a later ``fit`` invalidates it."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_fit(self.p, stream))
+
+    def joint_mixture(self, hp, side=0):
+        """(w, mu, sigma, rows) of root hp ``hp`` in component order
+        (tpe_plan_joint_get_mixture): component 0 is the prior (rows[0] = -1),
+        component k the side's k-th row; the entries are those of
+        ``mixture(hp, side)`` that the row owns.  A categorical hp: mu = the
+        observed option, sigma = the smoothing a.  ``hp = -1``: the component
+        weights (mu and sigma empty)."""
+        e = self.engine
+        cap = max(self.max_trials + 1, 1)
+        w, mu, sg = np.empty(cap), np.empty(cap), np.empty(cap)
+        rows = np.empty(cap, dtype=np.int32)
+        k = C.c_int64(0)
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_get_mixture(self.p, int(hp), int(side), _dp(w), _dp(mu),
+                                                     _dp(sg), rows.ctypes.data, cap, C.byref(k)))
+        k = k.value
+        if int(hp) < 0:
+            return w[:k].copy(), np.empty(0), np.empty(0), rows[:k].copy()
+        return w[:k].copy(), mu[:k].copy(), sg[:k].copy(), rows[:k].copy()
+
+    def joint_score_points(self, vals, want_terms=False, want_active=False, want_joint=False,
+                           stream=None):
+        """``score_points`` under the joint model (tpe_plan_joint_score_points):
+        total = joint + the conditional hps' terms in hp order; the root hps'
+        terms are +0.0.  Returns total[M], or (total[, terms][, active]
+        [, joint[M]]) with the ``want_`` flags."""
+        e = self.engine
+        vals = _f64(vals)
+        if vals.ndim != 2 or vals.shape[0] != self.n_hp:
+            raise ValueError('configurations must be a [n_hp, M] array')
+        m = vals.shape[1]
+        total = np.empty(m)
+        joint = np.empty(m) if want_joint else None
+        terms = np.empty((self.n_hp, m)) if want_terms else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_score_points(
+                self.p, vals.ctypes.data, m, m, total.ctypes.data,
+                joint.ctypes.data if want_joint else None,
+                terms.ctypes.data if want_terms else None,
+                active.ctypes.data if want_active else None, 0, stream))
+        out = (total,) + ((terms,) if want_terms else ()) + ((active,) if want_active else ()) \
+            + ((joint,) if want_joint else ())
+        return out[0] if len(out) == 1 else out
+
+    def joint_score_points_device(self, vals_ptr, m, ld, total_ptr, joint_ptr=0, terms_ptr=0,
+                                  active_ptr=0, stream=None):
+        """The same on device memory, as ``score_points_device``; joint[m]
+        optional.  Stream-ordered, no host synchronisation."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_score_points(
+                self.p, vals_ptr, int(m), int(ld), total_ptr, joint_ptr or None,
+                terms_ptr or None, active_ptr or None, 1, stream))
+
+    def joint_sides(self, m):
+        """(J_below[m], J_above[m]) of the last joint score or draw
+        (tpe_plan_joint_sides; diagnostics)."""
+        e = self.engine
+        jb, ja = np.empty(int(m)), np.empty(int(m))
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_sides(self.p, jb.ctypes.data, ja.ctypes.data, int(m)))
+        return jb, ja
+
+    def joint_sample_points(self, seed, m, begin=0, want_terms=False, want_active=False,
+                            want_joint=False, want_comp=False, stream=None):
+        """``sample_points`` under the joint model
+        (tpe_plan_joint_sample_points): every configuration picks one below
+        component and draws all its root values from it.  Returns (vals,
+        total[, terms][, active][, joint][, comp int32[m]])."""
+        e = self.engine
+        m = int(m)
+        if m < 0:
+            raise ValueError('the number of configurations must not be negative')
+        vals = np.empty((self.n_hp, m))
+        total = np.empty(m)
+        joint = np.empty(m) if want_joint else None
+        comp = np.empty(m, dtype=np.int32) if want_comp else None
+        terms = np.empty((self.n_hp, m)) if want_terms else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), m, m, vals.ctypes.data,
+                comp.ctypes.data if want_comp else None, total.ctypes.data,
+                joint.ctypes.data if want_joint else None,
+                terms.ctypes.data if want_terms else None,
+                active.ctypes.data if want_active else None, 0, stream))
+        return (vals, total) + ((terms,) if want_terms else ()) + \
+            ((active,) if want_active else ()) + ((joint,) if want_joint else ()) + \
+            ((comp,) if want_comp else ())
+
+    def joint_sample_points_device(self, seed, begin, m, ld, vals_ptr, total_ptr, comp_ptr=0,
+                                   joint_ptr=0, terms_ptr=0, active_ptr=0, stream=None):
+        """The same into device memory, as ``sample_points_device``."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_joint_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
+                comp_ptr or None, total_ptr, joint_ptr or None, terms_ptr or None,
+                active_ptr or None, 1, stream))
 
     def topk_points(self, total, k, eligible=None, m=None, out=None, stream=None):
         """The ``k`` eligible entries that rank first, as ``tpe.rank_pool``

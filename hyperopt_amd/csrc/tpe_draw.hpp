@@ -241,15 +241,16 @@ __device__ __forceinline__ U4 draw_block0(uint64_t seed, uint64_t gi, uint32_t s
                 (uint32_t)(seed >> 32));
 }
 
-// (r0: the words of draw4's first Philox block, draw_block0: u0 picks, u1
-// inverts; the second block -- u2 -- only for the unbounded Box-Muller)
+// The value component k of a continuous mixture takes under the uniform u1
+// (the second block -- u2 -- only for the unbounded Box-Muller): the part of
+// draw_table_from behind its pick, shared with the joint sampler
+// (tpe_joint.hip), whose component is picked once per configuration
 template <int CAP>
-__device__ double draw_table_from(const tpe_hp &H, int K, const double *__restrict__ mu,
-                                  const double *__restrict__ sg, const DrawTableT<CAP> &T,
-                                  U4 r0, uint64_t seed, uint64_t gi, uint32_t stream) {
-  const double u0 = u53(r0.x, r0.y), u1 = u53(r0.z, r0.w);
-  const int k = pick_cdf(T.cdf, K, u0);
-  if (H.family == TPE_CAT) return (double)k;
+__device__ __forceinline__ double draw_table_value(const tpe_hp &H, int k,
+                                                   const double *__restrict__ mu,
+                                                   const double *__restrict__ sg,
+                                                   const DrawTableT<CAP> &T, double u1,
+                                                   uint64_t seed, uint64_t gi, uint32_t stream) {
   double x;
   if (H.flags & (TPE_HAS_LOW | TPE_HAS_HIGH)) {
     // one tail probability q and side: x = mu + side * sqrt2 sigma erfcinv(2q)
@@ -274,6 +275,18 @@ __device__ double draw_table_from(const tpe_hp &H, int K, const double *__restri
   if (H.family == TPE_LGMM) x = exp(x);
   if (H.flags & TPE_HAS_Q) x = rint(x / H.q) * H.q;
   return x;
+}
+
+// (r0: the words of draw4's first Philox block, draw_block0: u0 picks, u1
+// inverts)
+template <int CAP>
+__device__ double draw_table_from(const tpe_hp &H, int K, const double *__restrict__ mu,
+                                  const double *__restrict__ sg, const DrawTableT<CAP> &T,
+                                  U4 r0, uint64_t seed, uint64_t gi, uint32_t stream) {
+  const double u0 = u53(r0.x, r0.y), u1 = u53(r0.z, r0.w);
+  const int k = pick_cdf(T.cdf, K, u0);
+  if (H.family == TPE_CAT) return (double)k;
+  return draw_table_value(H, k, mu, sg, T, u1, seed, gi, stream);
 }
 template <int CAP>
 __device__ double draw_table(const tpe_hp &H, int K, const double *__restrict__ mu,

@@ -117,6 +117,28 @@ struct tpe_plan : PlanShape {
   double *d_cand = nullptr;
   int32_t *d_cpos = nullptr;
   size_t cand_cap = 0;
+  // the joint model over the root hps (tpe_plan_joint_*, tpe_joint.hip): the
+  // dims and buffers are set up by the first tpe_plan_joint_fit; joint_ok: the
+  // tables are those of the current fit epoch (fit_args clears it)
+  std::vector<JointDim> jdims;
+  std::vector<int32_t> jdim_of_hp;
+  int32_t j_slots = 0;
+  int64_t j_nopt = 0;
+  bool joint_ok = false;
+  int32_t jK[2] = {0, 0};    // components per side of the last joint fit
+  double fit_pw = 1.0;       // prior_weight / lf of the last fit (fit_args)
+  int32_t fit_lf = 0;
+  JointDim *d_jdims = nullptr;
+  int32_t *d_jdim_of_hp = nullptr, *d_jrows = nullptr, *d_jcount = nullptr, *d_jcomp = nullptr;
+  JointSide *d_jside = nullptr;
+  uint64_t *d_jkeys = nullptr;
+  double *d_jw = nullptr, *d_jcw = nullptr, *d_jcmu = nullptr, *d_jcsig = nullptr;
+  double *d_jtab = nullptr, *d_joptlog = nullptr, *d_jpick = nullptr, *d_joptcdf = nullptr;
+  size_t joptcdf_cap = 0;
+  void *d_jdraw = nullptr;   // [P] draw tables of a joint draw
+  double *d_jsides = nullptr, *d_jjoint = nullptr;  // [2][m], [m] of the last joint score
+  size_t jpt_cap = 0;
+  int64_t jpt_m = 0;         // configurations of the last joint score (tpe_plan_joint_sides)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // per-kind event ring around every scoring launch (tpe_plan_profile)
   struct Prof {
@@ -230,7 +252,9 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt, p->d_tab_bound,
                   p->d_tab_hot, p->d_draw_zone, p->d_screen_stats, p->d_pt_vals, p->d_pt_terms,
                   p->d_pt_total, p->d_pt_act, p->d_pt_idx, p->d_pt_count, p->d_pt_tab, p->d_tk,
-                  p->d_tk_idx};
+                  p->d_tk_idx, p->d_jdims, p->d_jdim_of_hp, p->d_jrows, p->d_jcount, p->d_jcomp,
+                  p->d_jside, p->d_jkeys, p->d_jw, p->d_jcw, p->d_jcmu, p->d_jcsig, p->d_jtab,
+                  p->d_joptlog, p->d_jpick, p->d_joptcdf, p->d_jdraw, p->d_jsides, p->d_jjoint};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -627,6 +651,9 @@ FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf,
   p->mom_w = f.mom_w;
   p->mom_h = f.mom_h;
   p->tab_built = false;  // a new fit epoch
+  p->joint_ok = false;
+  p->fit_pw = prior_weight;
+  p->fit_lf = lf;
   FitArgs a{};
   a.hps = p->d_hps;
   a.vals = p->d_vals;
@@ -1667,6 +1694,9 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
   p->mom_w = p->graph_mom_w;  // (no fit_args on replay: the captured fit's table)
   p->mom_h = p->graph_mom_h;
   p->tab_built = p->graph_tab;
+  p->joint_ok = false;  // (a new fit epoch, fitted with the captured node's arguments)
+  p->fit_pw = p->fit_args0[0].prior_weight;
+  p->fit_lf = p->fit_args0[0].lf;
   return TPE_OK;
 }
 
@@ -1962,6 +1992,382 @@ int tpe_plan_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m
   CKH(hipMemcpy2DAsync(vals, (size_t)ld * 8, p->d_pt_vals, (size_t)m * 8, (size_t)m * 8,
                        (size_t)p->P, hipMemcpyDeviceToHost, st));
   CKH(hipMemcpyAsync(total, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (terms)
+    CKH(hipMemcpy2DAsync(terms, (size_t)ld * 8, p->d_pt_terms, (size_t)m * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyDeviceToHost, st));
+  if (active)
+    CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
+                         hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+// ---- the joint model over the root hps (tpe_joint.hip) ----
+namespace {
+
+constexpr int64_t kJointLdsMax = 160 * 1024;  // k_joint_score's staged values (64 x 8 B a slot)
+
+// the root dims of the plan's space and the buffers of its joint fit, once
+int ensure_joint(tpe_engine *h, tpe_plan *p) {
+  if (p->d_jtab) return TPE_OK;
+  p->jdims.clear();
+  p->jdim_of_hp.assign((size_t)p->P, -1);
+  int32_t slot = 0;
+  int64_t nopt = 0;
+  for (int32_t i = 0; i < p->P; ++i) {
+    const tpe_hp &x = p->hps[i];
+    if (x.cond_count != 0) continue;
+    JointDim d{};
+    d.hp = i;
+    d.kind = score_kind(x);
+    d.slot = slot;
+    d.upper = x.family == TPE_CAT ? x.upper : 0;
+    d.opt_off = nopt;
+    slot += joint_slots(d.kind);
+    nopt += d.upper;
+    p->jdim_of_hp[(size_t)i] = (int32_t)p->jdims.size();
+    p->jdims.push_back(d);
+  }
+  p->j_slots = slot;
+  p->j_nopt = nopt;
+  const size_t D = p->jdims.size(), kc = (size_t)p->kcap;
+  if ((int64_t)slot * 64 * 8 > kJointLdsMax)
+    return fail(h, TPE_E_INVALID, "joint_fit: too many root hps for the scoring kernel's LDS");
+  CKH(dalloc(&p->d_jdims, D));
+  CKH(dalloc(&p->d_jdim_of_hp, (size_t)p->P));
+  CKH(hipMemcpy(p->d_jdims, p->jdims.data(), D * sizeof(JointDim), hipMemcpyHostToDevice));
+  CKH(hipMemcpy(p->d_jdim_of_hp, p->jdim_of_hp.data(), (size_t)p->P * 4, hipMemcpyHostToDevice));
+  CKH(dalloc(&p->d_jrows, 2 * kc));
+  CKH(dalloc(&p->d_jcount, (size_t)2));
+  CKH(dalloc(&p->d_jside, (size_t)2));
+  CKH(dalloc(&p->d_jkeys, 2 * D * kc));
+  CKH(dalloc(&p->d_jw, 2 * kc));
+  CKH(dalloc(&p->d_jcw, 2 * D * kc));
+  CKH(dalloc(&p->d_jcmu, 2 * D * kc));
+  CKH(dalloc(&p->d_jcsig, 2 * D * kc));
+  CKH(dalloc(&p->d_joptlog, 2 * (size_t)nopt * 3));
+  CKH(dalloc(&p->d_jpick, kc));
+  CKH(dalloc(&p->d_jtab, 2 * (kc / kCoefBlock) * (size_t)joint_stride((int32_t)D)));
+  return TPE_OK;
+}
+
+// per-call scratch of m joint scores
+int ensure_joint_points(tpe_engine *h, tpe_plan *p, size_t m) {
+  if (m > p->jpt_cap) {
+    dfree(p->d_jsides); dfree(p->d_jjoint); dfree(p->d_jcomp);
+    p->d_jsides = p->d_jjoint = nullptr;
+    p->d_jcomp = nullptr;
+    p->jpt_cap = 0;
+    CKH(dalloc(&p->d_jsides, 2 * m));
+    CKH(dalloc(&p->d_jjoint, m));
+    CKH(dalloc(&p->d_jcomp, m));
+    p->jpt_cap = m;
+  }
+  return TPE_OK;
+}
+
+PointsArgs points_args(tpe_plan *p, int64_t m) {
+  PointsArgs a{};
+  a.idx = p->d_pt_idx;
+  a.count = p->d_pt_count;
+  a.hps = p->d_hps;
+  a.level_hps = p->d_level_hps;
+  a.cond_parent = p->d_cp;
+  a.cond_branch = p->d_cb;
+  a.info = p->d_info;
+  a.coef = p->d_coef;
+  a.kcap = p->kcap;
+  a.m = m;
+  a.n_hp = p->P;
+  return a;
+}
+
+// the joint launch arguments over a filled PointsArgs; joint: the caller's
+// output or null (the plan's scratch)
+JointScoreArgs joint_score_args(tpe_plan *p, const PointsArgs &a, double *joint) {
+  JointScoreArgs j{};
+  j.hps = p->d_hps;
+  j.dims = p->d_jdims;
+  j.n_dim = (int32_t)p->jdims.size();
+  j.n_slots = p->j_slots;
+  j.K[0] = p->jK[0];
+  j.K[1] = p->jK[1];
+  j.tab = p->d_jtab;
+  j.tab_side = (p->kcap / kCoefBlock) * joint_stride(j.n_dim);
+  j.optlog = p->d_joptlog;
+  j.n_opt = p->j_nopt;
+  j.vals = a.vals;
+  j.m = a.m;
+  j.ld = a.ld;
+  j.sides = p->d_jsides;
+  j.joint = joint ? joint : p->d_jjoint;
+  j.terms = a.terms;
+  j.term_ld = a.term_ld;
+  j.n_hp = p->P;
+  j.total = a.total;
+  p->jpt_m = a.m;
+  return j;
+}
+
+}  // namespace
+
+int tpe_plan_joint_fit(tpe_plan_t p, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, "joint_fit: the plan has not been fitted (tpe_plan_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  {
+    int rc = ensure_joint(h, p);
+    if (rc) return rc;
+    rc = flush_patch(h, p, st);
+    if (rc) return rc;
+  }
+  // the split of the last fit, as a mask (k_split computes k_fit's threshold)
+  FitArgs f{};
+  f.losses = p->d_losses;
+  f.n = p->n;
+  f.n_below = p->last_nb;
+  f.sortbuf = p->d_sortbuf;
+  f.scap = p->scap;
+  f.kcap = p->kcap;
+  CKH(launch_split(f, p->d_below, st));
+  JointFitArgs a{};
+  a.hps = p->d_hps;
+  a.dims = p->d_jdims;
+  a.n_dim = (int32_t)p->jdims.size();
+  a.n_hp = p->P;
+  a.vals = p->d_vals;
+  a.ld = p->ncap;
+  a.n = p->n;
+  a.below = p->d_below;
+  a.lf = p->fit_lf;
+  a.prior_weight = p->fit_pw;
+  a.pprior = p->d_pprior;
+  a.info = p->d_info;
+  a.mw = p->d_mw;
+  a.mmu = p->d_mmu;
+  a.msig = p->d_msig;
+  a.kcap = p->kcap;
+  a.keys = p->d_jkeys;
+  a.rows = p->d_jrows;
+  a.count = p->d_jcount;
+  a.side = p->d_jside;
+  a.jw = p->d_jw;
+  a.cw = p->d_jcw;
+  a.cmu = p->d_jcmu;
+  a.csig = p->d_jcsig;
+  a.tab = p->d_jtab;
+  a.optlog = p->d_joptlog;
+  a.n_opt = p->j_nopt;
+  CKH(launch_joint_fit(a, st));
+  const int64_t nb = std::min<int64_t>(std::max<int64_t>(p->last_nb, 0), p->n);
+  p->jK[0] = (int32_t)nb + 1;
+  p->jK[1] = (int32_t)(p->n - nb) + 1;
+  p->joint_ok = true;
+  return TPE_OK;
+}
+
+int tpe_plan_joint_get_mixture(tpe_plan_t p, int32_t hp, int32_t side, double *w, double *mu,
+                               double *sigma, int32_t *rows, int64_t cap, int64_t *k) {
+  if (!p || !k) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!p->joint_ok)
+    return fail(h, TPE_E_INVALID, "joint_get_mixture: no joint fit (tpe_plan_joint_fit first)");
+  if (hp < -1 || hp >= p->P || side < 0 || side > 1) return fail(h, TPE_E_INVALID, "bad hp/side");
+  const int32_t d = hp < 0 ? -1 : p->jdim_of_hp[(size_t)hp];
+  if (hp >= 0 && d < 0)
+    return fail(h, TPE_E_INVALID, "joint_get_mixture: a conditional hp is not in the joint model");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const int64_t K = p->jK[side];
+  *k = K;
+  if (K > cap) return fail(h, TPE_E_INVALID, "capacity too small");
+  const size_t bytes = (size_t)K * 8;
+  if (rows)
+    CKH(hipMemcpy(rows, p->d_jrows + side * p->kcap, (size_t)K * 4, hipMemcpyDeviceToHost));
+  if (hp < 0) {  // the component weights themselves
+    if (w) CKH(hipMemcpy(w, p->d_jw + side * p->kcap, bytes, hipMemcpyDeviceToHost));
+    return TPE_OK;
+  }
+  const int64_t ds = ((int64_t)d * 2 + side) * p->kcap;
+  if (w) CKH(hipMemcpy(w, p->d_jcw + ds, bytes, hipMemcpyDeviceToHost));
+  if (mu) CKH(hipMemcpy(mu, p->d_jcmu + ds, bytes, hipMemcpyDeviceToHost));
+  if (sigma) CKH(hipMemcpy(sigma, p->d_jcsig + ds, bytes, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+// Whole configurations under the joint model: tpe_plan_score_points' staging
+// and conventions; the roots are scored together (k_joint_score), the
+// conditional hps by k_score_points.
+int tpe_plan_joint_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                                double *total, double *joint, double *terms, uint8_t *active,
+                                int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, "joint_score_points: need 0 <= m <= ld");
+  if (m > 0 && (!vals || !total))
+    return fail(h, TPE_E_INVALID, "joint_score_points: vals and total must not be null");
+  if (m > (int64_t)INT32_MAX)
+    return fail(h, TPE_E_INVALID, "joint_score_points: too many configurations");
+  if (m == 0) return TPE_OK;
+  if (!p->joint_ok)
+    return fail(h, TPE_E_INVALID, "joint_score_points: no joint fit (tpe_plan_joint_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+    rc = ensure_joint_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+  PointsArgs a = points_args(p, m);
+  if (dev) {
+    a.vals = vals;
+    a.ld = ld;
+    a.total = total;
+    a.terms = terms ? terms : p->d_pt_terms;
+    a.term_ld = terms ? ld : m;
+    a.active = active ? active : p->d_pt_act;
+    a.act_ld = active ? ld : m;
+    CKH(launch_joint_points(joint_score_args(p, a, joint), a, true, st));
+    return TPE_OK;
+  }
+  if (ld == m)  // (contiguous: one plain copy)
+    CKH(hipMemcpyAsync(p->d_pt_vals, vals, (size_t)m * p->P * 8, hipMemcpyHostToDevice, st));
+  else
+    CKH(hipMemcpy2DAsync(p->d_pt_vals, (size_t)m * 8, vals, (size_t)ld * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyHostToDevice, st));
+  a.vals = p->d_pt_vals;
+  a.ld = m;
+  a.total = p->d_pt_total;
+  a.terms = p->d_pt_terms;
+  a.active = p->d_pt_act;
+  a.term_ld = a.act_ld = m;
+  CKH(launch_joint_points(joint_score_args(p, a, nullptr), a, true, st));
+  CKH(hipMemcpyAsync(total, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (joint) CKH(hipMemcpyAsync(joint, p->d_jjoint, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (terms)
+    CKH(hipMemcpy2DAsync(terms, (size_t)ld * 8, p->d_pt_terms, (size_t)m * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyDeviceToHost, st));
+  if (active)
+    CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
+                         hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+int tpe_plan_joint_sides(tpe_plan_t p, double *below, double *above, int64_t m) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || m > p->jpt_m)
+    return fail(h, TPE_E_INVALID, "joint_sides: more entries than the last joint score holds");
+  if (m == 0) return TPE_OK;
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  if (below) CKH(hipMemcpy(below, p->d_jsides, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (above)
+    CKH(hipMemcpy(above, p->d_jsides + p->jpt_m, (size_t)m * 8, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+// Whole configurations drawn from the joint below model and scored: one
+// component per configuration, every root value from it, the conditional hps
+// by tpe_plan_sample_points' walk; then tpe_plan_joint_score_points' launches
+// behind the draw's own lists.
+int tpe_plan_joint_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m, int64_t ld,
+                                 double *vals, int32_t *comp, double *total, double *joint,
+                                 double *terms, uint8_t *active, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, "joint_sample_points: need 0 <= m <= ld");
+  if (begin < 0) return fail(h, TPE_E_INVALID, "joint_sample_points: begin must not be negative");
+  if (m > 0 && (!vals || !total))
+    return fail(h, TPE_E_INVALID, "joint_sample_points: vals and total must not be null");
+  if (m > (int64_t)INT32_MAX)
+    return fail(h, TPE_E_INVALID, "joint_sample_points: too many configurations");
+  if (m == 0) return TPE_OK;
+  if (!p->joint_ok)
+    return fail(h, TPE_E_INVALID, "joint_sample_points: no joint fit (tpe_plan_joint_fit first)");
+  const int64_t Kb = p->jK[0];
+  if (Kb > kTabCap)
+    return fail(h, TPE_E_INVALID, "joint_sample_points: more below components than a draw table holds");
+  for (const JointDim &d : p->jdims)
+    if (d.upper > kTabCap)
+      return fail(h, TPE_E_INVALID, "joint_sample_points: a root choice has more options than a draw table holds");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+    rc = ensure_joint_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  if (!p->d_jdraw) CKH(hipMalloc(&p->d_jdraw, joint_sample_tables_bytes(p->P)));
+  const size_t need = (size_t)p->j_nopt * (size_t)Kb;
+  if (need > p->joptcdf_cap) {
+    dfree(p->d_joptcdf);
+    p->d_joptcdf = nullptr;
+    p->joptcdf_cap = 0;
+    CKH(dalloc(&p->d_joptcdf, need));
+    p->joptcdf_cap = need;
+  }
+  CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+  JointSampleArgs js{};
+  SampleArgs &s = js.S;
+  s.P = points_args(p, m);
+  PointsArgs &a = s.P;
+  s.mw = p->d_mw;
+  s.mmu = p->d_mmu;
+  s.msig = p->d_msig;
+  s.tab = static_cast<DrawTableT<kTabCap> *>(p->d_jdraw);
+  s.seed = seed;
+  s.begin = begin;
+  js.dims = p->d_jdims;
+  js.n_dim = (int32_t)p->jdims.size();
+  js.Kb = (int32_t)Kb;
+  js.dim_of_hp = p->d_jdim_of_hp;
+  js.jw = p->d_jw;
+  js.cmu = p->d_jcmu;
+  js.csig = p->d_jcsig;
+  js.side = p->d_jside;
+  js.pprior = p->d_pprior;
+  js.prior_weight = p->fit_pw;
+  js.pick_cdf = p->d_jpick;
+  js.opt_cdf = p->d_joptcdf;
+  if (dev) {
+    s.out = vals;
+    a.vals = vals;
+    a.ld = ld;
+    a.total = total;
+    a.terms = terms ? terms : p->d_pt_terms;
+    a.term_ld = terms ? ld : m;
+    a.active = active ? active : p->d_pt_act;
+    a.act_ld = active ? ld : m;
+    js.comp = comp;
+    CKH(launch_joint_sample(js, st));
+    CKH(launch_joint_points(joint_score_args(p, a, joint), a, false, st));
+    return TPE_OK;
+  }
+  s.out = p->d_pt_vals;
+  a.vals = p->d_pt_vals;
+  a.ld = m;
+  a.total = p->d_pt_total;
+  a.terms = p->d_pt_terms;
+  a.active = p->d_pt_act;
+  a.term_ld = a.act_ld = m;
+  js.comp = comp ? p->d_jcomp : nullptr;
+  CKH(launch_joint_sample(js, st));
+  CKH(launch_joint_points(joint_score_args(p, a, nullptr), a, false, st));
+  CKH(hipMemcpy2DAsync(vals, (size_t)ld * 8, p->d_pt_vals, (size_t)m * 8, (size_t)m * 8,
+                       (size_t)p->P, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(total, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (comp) CKH(hipMemcpyAsync(comp, p->d_jcomp, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+  if (joint) CKH(hipMemcpyAsync(joint, p->d_jjoint, (size_t)m * 8, hipMemcpyDeviceToHost, st));
   if (terms)
     CKH(hipMemcpy2DAsync(terms, (size_t)ld * 8, p->d_pt_terms, (size_t)m * 8, (size_t)m * 8,
                          (size_t)p->P, hipMemcpyDeviceToHost, st));

@@ -590,39 +590,7 @@ __device__ double block_np_sum(const double *a, int64_t n, FitShared &sm) {
 // ------------------------------------------------------------------------
 // scalar helpers of the reference
 // ------------------------------------------------------------------------
-// linear_forgetting_weights(n, lf)[i] (tpe.py:381-394) with numpy linspace
-// rounding (i*step + start, last ramp element == stop).  The two divisions
-// are hoisted: LfRamp is built once per slot.
-struct LfRamp {
-  int64_t ramp;  // ramp length n - lf (<= 0: all ones)
-  double start, step;
-};
-__device__ __forceinline__ LfRamp lf_ramp(int64_t n, int32_t lf) {
-  LfRamp r;
-  r.ramp = n < lf ? 0 : n - lf;
-  r.start = 1.0 / (double)(n > 0 ? n : 1);
-  r.step = r.ramp > 1 ? (1.0 - r.start) / (double)(r.ramp - 1) : 0.0;
-  return r;
-}
-__device__ __forceinline__ double lf_weight(const LfRamp &r, int64_t i) {
-  if (i >= r.ramp) return 1.0;
-  if (r.ramp == 1) return r.start;
-  if (i == r.ramp - 1) return 1.0;
-  return (double)i * r.step + r.start;
-}
-
-// the observation transform of an hp (tpe.py:510-560 posteriors): one log
-// at most per value; `floor` = the clip's lower bound (max(EPS, exp(low)) or
-// EPS), computed once per slot by ObsFloor
-__device__ __forceinline__ double obs_floor(int32_t tf, double low) {
-  if (tf == TPE_OBS_LOG_CLIP_EXPLOW) return np_maximum(kEPS, exp(low));
-  return kEPS;
-}
-__device__ __forceinline__ double obs_transform(double v, int32_t tf, double floor) {
-  if (tf == TPE_OBS_IDENT) return v;
-  const bool clip = tf == TPE_OBS_LOG_CLIP_EXPLOW || tf == TPE_OBS_LOG_CLIP_EPS;
-  return log(clip ? np_maximum(v, floor) : v);
-}
+// (linear forgetting weights and the observation transform: tpe_device.hpp)
 
 // ------------------------------------------------------------------------
 // (a2) split: the n_below-th smallest (loss key, position).  below(j) <=>

@@ -699,6 +699,112 @@ size_t sample_tables_bytes(int32_t n_hp);
 // k_sample_tables, k_sample_points, then launch_points_score
 hipError_t launch_sample_points(const SampleArgs &s, hipStream_t st);
 
+// The joint Parzen model over the root (unconditional) hps (tpe_joint.hip;
+// tpe_plan_joint_*).  Side s has K_s = n_s + 1 components --
+// component 0 the prior, component k the side's k-th row in row order -- each
+// the product over the root hps of that hp's marginal kernel for the row.
+//
+// Scoring tables, per side, in blocks of kCoefBlock components:
+//   [block][ 8 log2 w | dim 0: 3 fields x 8 | dim 1: 3 fields x 8 | ... ]
+// so a scoring wave streams a block front to back through scalar loads.  The
+// fields of a dim are, by its kind,
+//   LSE  alpha, beta, gamma of make_coef with w = 1, p_accept = 1
+//   ERF  mu, 1 / max(sqrt2 sigma, EPS), 0
+//   CAT  the row's observed option (-1: the prior component), 0, 0
+// Padding components of the last block have log2 w = -inf and zero fields.
+struct JointDim {
+  int32_t hp;        // the root hp
+  int32_t kind;      // score_kind(hp)
+  int32_t slot;      // first of the lane's staged values of this dim (k_joint_score)
+  int32_t upper;     // CAT: options
+  int64_t opt_off;   // CAT: the dim's first entry in the per-option tables
+};
+__host__ __device__ constexpr int joint_slots(int kind) {
+  return kind == KIND_CAT ? 4 : (kind == KIND_ERF_G || kind == KIND_ERF_L) ? 2 : 1;
+}
+constexpr int kJointFields = 3;
+// doubles of one component block of a side's table
+__host__ __device__ constexpr int64_t joint_stride(int32_t n_dim) {
+  return (int64_t)kCoefBlock * (1 + kJointFields * (int64_t)n_dim);
+}
+struct JointSide {
+  double tot;  // S + prior_weight
+  double a1;   // prior_weight / tot: the categorical smoothing a = a1 * (upper - 1)
+};
+struct JointFitArgs {
+  const tpe_hp *hps;
+  const JointDim *dims;
+  int32_t n_dim;
+  int32_t n_hp;
+  const double *vals;        // [P][ld] history
+  int64_t ld;
+  int64_t n;                 // history rows
+  const uint8_t *below;      // [n] the split of the last fit (k_split)
+  int32_t lf;
+  int32_t pad;
+  double prior_weight;
+  const double *pprior;
+  const MixInfo *info;       // the marginal fit: [2P]
+  const double *mw, *mmu, *msig;  // [2P][kcap]
+  int64_t kcap;
+  uint64_t *keys;            // [2][n_dim][kcap] scratch: the rows' sort keys
+  // out
+  int32_t *rows;             // [2][kcap] rows[0] = -1
+  int32_t *count;            // [2] K_s
+  JointSide *side;           // [2]
+  double *jw;                // [2][kcap] component weights
+  double *cw, *cmu, *csig;   // [n_dim][2][kcap] per dim, component order: the marginal's
+                             // (w, mu, sigma) of the row (CAT: w = jw, mu = option, sigma = a)
+  double *tab;               // [2][kcap / 8][joint_stride]
+  double *optlog;            // [2][n_opt][3] log2 of kappa hit / miss / prior per option
+  int64_t n_opt;
+};
+hipError_t launch_joint_fit(const JointFitArgs &a, hipStream_t st);
+
+struct JointScoreArgs {
+  const tpe_hp *hps;
+  const JointDim *dims;
+  int32_t n_dim;
+  int32_t n_slots;           // staged values per configuration
+  int32_t K[2];
+  const double *tab;         // [2][kcap / 8][joint_stride]
+  int64_t tab_side;          // doubles per side
+  const double *optlog;
+  int64_t n_opt;
+  const double *vals;        // [P][ld]
+  int64_t m, ld;
+  double *sides;             // [2][m] J_below, J_above
+  double *joint;             // [m]
+  const double *terms;       // [P][term_ld]
+  int64_t term_ld;
+  int32_t n_hp;
+  int32_t pad;
+  double *total;             // [m] joint + terms in ascending hp index
+};
+// the roots' share of k_points_active (roots active, +0.0 terms, not listed),
+// k_joint_score, the conditional hps' k_score_points, k_joint_sum
+hipError_t launch_joint_points(const JointScoreArgs &j, const PointsArgs &a, bool walk,
+                               hipStream_t st);
+
+struct JointSampleArgs {
+  SampleArgs S;              // the conditional walk's arguments (S.tab: [P] draw tables)
+  const JointDim *dims;
+  int32_t n_dim;
+  int32_t Kb;                // below components
+  const int32_t *dim_of_hp;  // [P] root dim of an hp, -1: conditional
+  const double *jw;          // [kcap] below component weights
+  const double *cmu, *csig;  // [n_dim][2][kcap]
+  const JointSide *side;     // [2]
+  const double *pprior;
+  double prior_weight;
+  double *pick_cdf;         // [kcap] scratch: inclusive CDF of jw
+  double *opt_cdf;           // [n_opt][Kb] scratch: per CAT dim [Kb][upper] CDFs of kappa
+  int32_t *comp;             // [m] out (nullable)
+};
+size_t joint_sample_tables_bytes(int32_t n_hp);
+// k_joint_tables, k_joint_sample (values, activity, lists); the caller scores
+hipError_t launch_joint_sample(const JointSampleArgs &s, hipStream_t st);
+
 // Device top-k of totals and the gather of the picked columns (tpe_topk.hip;
 // tpe_plan_topk_points, tpe_plan_gather_points)
 constexpr int kTopkMax = 4096;

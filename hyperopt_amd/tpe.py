@@ -287,17 +287,33 @@ def _check_consistent(cs, present, active):
                             'inactive' if present[i, j] else 'active'))
 
 
-def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma):
-    """Push the history and fit, exactly as ``suggest`` does (st.lock held)."""
+def root_indices(cs):
+    """The unconditional hps of a space -- the dimensions of the multivariate
+    model -- as indices into ``cs.labels``."""
+    return [i for i, h in enumerate(cs.hps) if len(h.conds()) == 0]
+
+
+def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate=False):
+    """Push the history and fit, exactly as ``suggest`` does (st.lock held).
+    ``multivariate``: also the joint model over the unconditional hps, which
+    every history row must hold (ValueError otherwise)."""
     engine = engine or E.default_engine()
     plan = st.plan_for(domain, hist.n, engine)
     hist.push(plan)
     plan.fit(gamma=gamma, prior_weight=prior_weight, lf=DEFAULT_LF)
+    if multivariate:
+        roots = root_indices(domain.space)
+        act = np.asarray(hist.active)[roots, :hist.n]
+        if not act.all():
+            i, j = (int(x) for x in np.argwhere(act == 0)[0])
+            raise ValueError('multivariate TPE: history row %d has no value for the '
+                             'unconditional hp %r' % (j, domain.space.labels[roots[i]]))
+        plan.joint_fit()
     return plan
 
 
 def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
-                  gamma=_default_gamma, engine=None, return_terms=False):
+                  gamma=_default_gamma, engine=None, return_terms=False, multivariate=False):
     """What the fitted TPE model thinks of configurations the caller holds.
 
     The history of ``trials`` is synced, pushed and fitted as ``suggest``
@@ -310,7 +326,14 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     ``{label: term[M]}`` and ``{label: active[M]}``.  Non-finite lpdfs
     propagate (nothing is clamped); an active categorical value that is not
     an option index scores NaN.  ValueError: an empty history, or a dict whose
-    labels contradict the activity its own choices imply."""
+    labels contradict the activity its own choices imply.
+
+    ``multivariate``: the unconditional hps are scored together under the
+    joint Parzen model (one mixture over whole history rows per side, as
+    Optuna's ``multivariate=True``), which sees interactions
+    between them: ``EI(c) = joint(c) + the conditional hps' terms``.  With
+    ``return_terms`` the result is (EI, terms, active, joint[M]); the terms of
+    unconditional labels are 0.0."""
     cs = domain.space
     as_dicts = not isinstance(configs, np.ndarray)
     vals, present = config_columns(cs, configs)
@@ -319,14 +342,20 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
         hist = st.history(domain, trials).sync(trials)
         if hist.n == 0:
             raise ValueError('score_configs needs a history: trials holds no usable trial')
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
-        total, terms, active = plan.score_points(vals, want_terms=True, want_active=True)
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
+        joint = None
+        if multivariate:
+            total, terms, active, joint = plan.joint_score_points(
+                vals, want_terms=True, want_active=True, want_joint=True)
+        else:
+            total, terms, active = plan.score_points(vals, want_terms=True, want_active=True)
     if as_dicts:
         _check_consistent(cs, present, active)
     if not return_terms:
         return total
-    return (total, {lab: terms[i] for i, lab in enumerate(cs.labels)},
-            {lab: active[i].astype(bool) for i, lab in enumerate(cs.labels)})
+    out = (total, {lab: terms[i] for i, lab in enumerate(cs.labels)},
+           {lab: active[i].astype(bool) for i, lab in enumerate(cs.labels)})
+    return out + (joint,) if multivariate else out
 
 
 class _Pool(object):
@@ -341,17 +370,18 @@ class _Pool(object):
         self.m = self.vals.shape[1]
         self._dev = None            # (engine, values, totals) device buffers of an array pool
 
-    def totals(self, plan):
+    def totals(self, plan, multivariate=False):
         """EI of every pool configuration under ``plan``'s fit."""
         if not isinstance(self.source, np.ndarray) or self.m == 0:
-            return plan.score_points(self.vals)
+            return (plan.joint_score_points if multivariate else plan.score_points)(self.vals)
         # an array pool lives on the device: uploaded once, scored in place
         eng = plan.engine
         if self._dev is None or self._dev[0] is not eng:
             self._dev = (eng, E.DeviceBuffer(eng, self.vals.nbytes).upload(self.vals),
                          E.DeviceBuffer(eng, 8 * self.m))
         _, v, out = self._dev
-        plan.score_points_device(v.ptr, self.m, self.m, out.ptr)
+        score = plan.joint_score_points_device if multivariate else plan.score_points_device
+        score(v.ptr, self.m, self.m, out.ptr)
         return out.download(np.empty(self.m))
 
 
@@ -394,7 +424,7 @@ def rank_pool(total, eligible, k):
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
                       prior_weight=_default_prior_weight,
                       n_startup_jobs=_default_n_startup_jobs,
-                      gamma=_default_gamma, skip_seen=True, engine=None):
+                      gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False):
     """``algo=`` for a constrained or discrete search: the next trials are the
     ``len(new_ids)`` configurations of ``pool`` the fitted model scores
     highest (``score_configs``' EI), distinct, ties to the lower pool index,
@@ -405,7 +435,8 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     a trial already in the history.  While the history has fewer than
     ``n_startup_jobs`` trials the picks are ``np.random.RandomState(seed)
     .choice(M, k, replace=False)`` over the whole pool.  ValueError when fewer
-    than ``len(new_ids)`` eligible configurations remain."""
+    than ``len(new_ids)`` eligible configurations remain.  ``multivariate``:
+    the pool is ranked by ``score_configs(..., multivariate=True)``."""
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -429,8 +460,8 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
             if int(eligible.sum()) < k:
                 raise ValueError('%d eligible pool configurations remain, %d asked for'
                                  % (int(eligible.sum()), k))
-            plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
-            picks = rank_pool(pl.totals(plan), eligible, k)
+            plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
+            picks = rank_pool(pl.totals(plan, multivariate), eligible, k)
     chosen = columns_to_configs(cs, pl.vals[:, picks], pl.active[:, picks])
     return [_new_doc(domain, trials, cs, i, c) for i, c in zip(new_ids, chosen)]
 
@@ -444,7 +475,8 @@ STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
 
 
 def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
-                   gamma=_default_gamma, engine=None, begin=0, as_dicts=False):
+                   gamma=_default_gamma, engine=None, begin=0, as_dicts=False,
+                   multivariate=False):
     """``n`` whole configurations drawn from the fitted model's *below*
     mixtures, each with its joint EI (``score_configs``' total of it).
 
@@ -456,15 +488,22 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     the numbers of one call.  Returns (vals[P, n] in ``domain.space.labels``
     order with NaN for inactive -- a pool array -- , ei[n]); with ``as_dicts``
     the configurations as ``{label: value}`` dicts instead.  ValueError on an
-    empty history."""
+    empty history.
+
+    ``multivariate``: every configuration picks one component of the joint
+    below model -- the prior or one good trial -- and draws all its
+    unconditional hps from that component's kernels, so they keep the good
+    trials' correlations; the EI is ``score_configs(..., multivariate=True)``'s
+    (tpe_plan_joint_sample_points)."""
     cs = domain.space
     st = _state(domain)
     with st.lock:
         hist = st.history(domain, trials).sync(trials)
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
-        vals, total = plan.sample_points(batch_seeds(seed, 1)[0], int(n), begin=int(begin))
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
+        draw = plan.joint_sample_points if multivariate else plan.sample_points
+        vals, total = draw(batch_seeds(seed, 1)[0], int(n), begin=int(begin))
     if as_dicts:
         return columns_to_configs(cs, vals, ~np.isnan(vals)), total
     return vals, total
@@ -558,7 +597,7 @@ def _joint_buffers(st, engine, P, n):
 def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, feasible=None,
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
-                  startup_stream='numpy', engine=None):
+                  startup_stream='numpy', engine=None, multivariate=False):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -582,7 +621,11 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     rounds of it with seeds ``batch_seeds(seed, r + 1)[r]`` (the 'numpy'
     stream takes their low 32 bits from round 1 on: RandomState holds no
     more), the feasible draws kept in order (at most 100 rounds, else
-    ValueError)."""
+    ValueError).
+
+    ``multivariate``: the draw and its ranking are
+    ``sample_configs(..., multivariate=True)``'s; everything else is as
+    above."""
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -601,9 +644,10 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
     P = len(cs.labels)
     with st.lock:
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma)
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
-        plan.sample_points_device(batch_seeds(seed, 1)[0], 0, n, n, d_vals.ptr, d_total.ptr)
+        draw = plan.joint_sample_points_device if multivariate else plan.sample_points_device
+        draw(batch_seeds(seed, 1)[0], 0, n, n, d_vals.ptr, d_total.ptr)
         vals = eligible = None
         n_el = n
         if feasible is not None:

@@ -331,6 +331,70 @@ int tpe_plan_gather_points(tpe_plan_t p, const double *vals, int64_t ld,
                            const int32_t *idx, int32_t k, double *out,
                            int32_t on_device, void *stream);
 
+/* Multivariate TPE: a joint Parzen model over the root hps -- those without a
+ * condition, in ascending index; they must be active in every history row
+ * (not checked).  The sides are the split of the last tpe_plan_fit, each kept
+ * in row order.  Side s with n_s rows has n_s + 1 components: component 0 is
+ * the prior, component k >= 1 the side's k-th row, with weight w_0 =
+ * prior_weight / (S + prior_weight), w_k = lw[k - 1] / (S + prior_weight), lw
+ * the linear-forgetting weights of the side's rows (ones unless lf < n_s) and
+ * S their sum.  A component's density is the product over the root hps of a
+ * kernel: for a continuous hp the (mu, sigma) the marginal fit of that hp
+ * gave the row's observation (the prior's for component 0), as the q = None
+ * log-density or, with q, log(cdf(ub) - cdf(lb)) on the reference's bounds,
+ * without truncation normaliser; for a categorical hp with observation o,
+ * kappa(c) = ((c == o ? 1 : 0) + a pi[c]) / (1 + a), a = prior_weight
+ * (upper - 1) / (S + prior_weight), pi the prior over the options (component
+ * 0: pi itself).  J_s(c) = logsumexp_k [log w_k + sum_d log kappa_dk(c_d)],
+ * joint(c) = J_below(c) - J_above(c).
+ * tpe_plan_joint_fit builds the model's tables from the last tpe_plan_fit
+ * (TPE_E_INVALID before one); a later fit invalidates them.  Stream-ordered. */
+int tpe_plan_joint_fit(tpe_plan_t p, void *stream);
+/* The joint model's components of a root hp in component order, k of them
+ * (cap >= k): w, mu, sigma are the entries of the hp's marginal mixture
+ * (tpe_plan_get_mixture) that row rows[j] owns, bit for bit -- sorted by (mu,
+ * row) they are that mixture -- and rows[0] = -1 (the prior).  A categorical
+ * hp: w = the component weight, mu = the observed option (-1 for component
+ * 0), sigma = a.  hp = -1: the component weights themselves in w (the draw's
+ * pick distribution); mu and sigma are not written.  Any output may be NULL.
+ * TPE_E_INVALID for a conditional hp or without a joint fit.  Synchronizes
+ * the device.                                                               */
+int tpe_plan_joint_get_mixture(tpe_plan_t p, int32_t hp, int32_t side, double *w,
+                               double *mu, double *sigma, int32_t *rows, int64_t cap,
+                               int64_t *k);
+/* tpe_plan_score_points under the joint model: joint[M] (may be NULL) as
+ * above from the root values; terms[i][c] of a conditional hp is what
+ * tpe_plan_score_points returns, of a root hp +0.0; total[c] = joint[c] plus
+ * the terms in ascending hp index, added in float64 in that order.  Activity,
+ * layouts, on_device, the NULL outputs, m == 0 and the errors are
+ * tpe_plan_score_points'; a root value that is NaN, or a root choice that is
+ * not an integer in [0, upper), gives NaN joint and total and activates no
+ * child.  A configuration's numbers depend on its own values and the fit
+ * alone.  TPE_E_INVALID without a joint fit.                                */
+int tpe_plan_joint_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                                double *total, double *joint, double *terms,
+                                uint8_t *active, int32_t on_device, void *stream);
+/* Debug: J_below and J_above (either may be NULL) of the first m
+ * configurations of the plan's last tpe_plan_joint_score_points or
+ * tpe_plan_joint_sample_points call.  Synchronizes the device.              */
+int tpe_plan_joint_sides(tpe_plan_t p, double *below, double *above, int64_t m);
+/* tpe_plan_sample_points under the joint model.  Configuration c = begin + j
+ * picks one below component, comp[j] (may be NULL) = tpe_sample(TPE_CAT, the
+ * below component weights, stream 2^29 | n_hp, offset c).  A continuous root
+ * hp d takes, bit for bit, tpe_sample of the one-component mixture (1.0,
+ * mu_d,comp, sigma_d,comp) with the hp's family, bounds, q and flags, stream
+ * 2^29 | d, offset c; a categorical one tpe_sample(TPE_CAT, kappa_d,comp,
+ * stream 2^29 | d, offset c).  Conditional hps are drawn and routed as
+ * tpe_plan_sample_points draws them.  total, joint, terms and active are what
+ * tpe_plan_joint_score_points returns for the drawn vals, bit for bit.  The
+ * draws depend on (seed, c) only.  TPE_E_INVALID as tpe_plan_sample_points,
+ * without a joint fit, or with more than 2048 below components or options of
+ * a root choice.                                                            */
+int tpe_plan_joint_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m,
+                                 int64_t ld, double *vals, int32_t *comp, double *total,
+                                 double *joint, double *terms, uint8_t *active,
+                                 int32_t on_device, void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
