@@ -47,7 +47,7 @@ EXPORTS = (
     'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats', 'tpe_plan_score_points',
     'tpe_plan_sample_points', 'tpe_plan_topk_points', 'tpe_plan_gather_points',
     'tpe_plan_joint_fit', 'tpe_plan_joint_get_mixture', 'tpe_plan_joint_score_points',
-    'tpe_plan_joint_sides', 'tpe_plan_joint_sample_points',
+    'tpe_plan_joint_sides', 'tpe_plan_joint_sample_points', 'tpe_math_probe',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -171,6 +171,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
             'tpe_microbench': (C.c_int, [vp, i32, _D]),
+            'tpe_math_probe': (C.c_int, [vp, i32, _D, i64, _D]),
             'tpe_plan_get_results': (C.c_int, [vp, vp, i32, vp]),
             'tpe_plan_results_device': (vp, [vp]),
             'tpe_plan_census': (C.c_int, [vp, i32, C.POINTER(i64)]),
@@ -264,6 +265,17 @@ class Engine(object):
         with self.lock:
             self.check(self.lib.tpe_microbench(self.h, int(which), C.byref(r)))
         return r.value
+
+    def math_probe(self, which, x):
+        """A device math helper on the arguments x (tpe_math_probe): 0
+        fast_log, 1 fast_log2, 2 erfcinv_fast, 3 erfc; wave j evaluates
+        x.ravel()[64 j : 64 j + 64]."""
+        xa = _f64(x)
+        xs = xa.ravel()
+        out = np.empty(xs.size)
+        with self.lock:
+            self.check(self.lib.tpe_math_probe(self.h, int(which), _dp(xs), xs.size, _dp(out)))
+        return out.reshape(xa.shape)
 
     # -- operator level ----------------------------------------------------
     def split(self, losses, gamma, gamma_cap=25):

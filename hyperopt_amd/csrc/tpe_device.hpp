@@ -381,11 +381,18 @@ __device__ __forceinline__ void store_lse_moments16h(CoefM8 *tm, int64_t k, EnvT
 // candidate transforms y = log x, the EI ratio, bucketing keys): x = m 2^e
 // with m in [1/sqrt2, sqrt2), log m = 2 atanh s, s = (m - 1) / (m + 1),
 // |s| <= 0.1716, the odd series to s^21 (truncation < 2e-18 relative), the
-// quotient by v_rcp_f64 and two Newton steps, e ln2 in two parts; within a
-// few ulp of log x (tests/test_gpu_ops.py fast_log check).  Zero, negative,
-// infinite and NaN x take the library log (same results as before).
+// quotient by v_rcp_f64 and two Newton steps, e ln2 in two parts; within
+// 3 ulp of log x over every finite positive double, subnormals included
+// (tests/test_gpu_device_math.py, against mpmath).  Zero, negative, infinite
+// and NaN x take the library log (same results as before), except that a
+// negative x gives numpy's NaN on the reference's platform: the default NaN of
+// an invalid x86 operation, sign set (the library's has it clear), so the
+// bits are numpy.log's for every argument.
+__device__ __forceinline__ double invalid_nan() {
+  return __longlong_as_double((long long)0xfff8000000000000ull);
+}
 __device__ __forceinline__ double fast_log(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return log(x);
+  if (!(x > 0.0 && x < INFINITY)) return x < 0.0 ? invalid_nan() : log(x);
   int e = __builtin_amdgcn_frexp_exp(x);
   double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
   const bool lo = m < 0.70710678118654752440;
@@ -414,7 +421,7 @@ __device__ __forceinline__ double fast_log(double x) {
   return fma(fe, 6.93147180369123816490e-01, fma(fe, 1.90821492927058770002e-10, lm));
 }
 __device__ __forceinline__ double fast_log2(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return log2(x);
+  if (!(x > 0.0 && x < INFINITY)) return x < 0.0 ? invalid_nan() : log2(x);
   int e = __builtin_amdgcn_frexp_exp(x);
   double m = __builtin_amdgcn_frexp_mant(x);
   const bool lo = m < 0.70710678118654752440;

@@ -2844,6 +2844,23 @@ int tpe_microbench(tpe_handle_t h, int32_t which, double *per_second) {
   return TPE_OK;
 }
 
+int tpe_math_probe(tpe_handle_t h, int32_t which, const double *x, int64_t n, double *out) {
+  if (!h) return TPE_E_INVALID;
+  if (which < 0 || which > 3) return fail(h, TPE_E_INVALID, "unknown math helper");
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(h, TPE_E_INVALID, "bad args");
+  if (n == 0) return TPE_OK;
+  CKH(hipSetDevice(h->device));
+  double *d = nullptr;
+  CKH(dalloc(&d, 2 * (size_t)n));
+  hipError_t e = hipMemcpyAsync(d, x, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = launch_math_probe(which, d, n, d + n, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d + n, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  dfree(d);
+  CKH(e);
+  return TPE_OK;
+}
+
 int tpe_plan_last_stats(tpe_plan_t p, double *score_ms, double *pairs) {
   if (!p) return TPE_E_INVALID;
   tpe_engine *h = p->eng;

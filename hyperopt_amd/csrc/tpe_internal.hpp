@@ -617,6 +617,8 @@ hipError_t launch_sample(const tpe_hp *hp_dev, const double *mw,
                          hipStream_t st);
 
 hipError_t launch_micro(int which, int blocks, int iters, double *sink, hipStream_t st);
+// out[i] = helper `which` of x[i] (tpe_math_probe), device pointers
+hipError_t launch_math_probe(int which, const double *x, int64_t n, double *out, hipStream_t st);
 // Chebyshev tables of both mixtures of every table_hp of the plan (headers
 // zeroed first); census: optional pair counters ([3] and [5] += node pairs);
 // bound (optional): then the bound lattice of every hp whose two tables are

@@ -9,6 +9,7 @@
 //   k_merge  : cross-device argmax with numpy semantics   tpe.py:749-759
 //   k_sample : operator-level sampler (tpe_sample)
 //   k_micro  : register-only microbenchmarks for the roofline
+//   k_math_probe : the device math helpers on given arguments (tests)
 #include <math.h>
 
 #include <algorithm>
@@ -654,6 +655,36 @@ hipError_t launch_micro(int which, int blocks, int iters, double *sink, hipStrea
     case 8: k_micro<8><<<blocks, 256, 0, st>>>(iters, sink); break;
     case 9: k_micro<9><<<blocks, 256, 0, st>>>(iters, sink); break;
     default: k_micro<2><<<blocks, 256, 0, st>>>(iters, sink); break;
+  }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------
+// the device math helpers on given arguments (tpe_math_probe): one element
+// per thread, so a wave holds 64 consecutive arguments (erfcinv_fast's tail
+// polynomial is evaluated per wave)
+// ------------------------------------------------------------------------
+template <int WHICH>
+__global__ __launch_bounds__(256) void k_math_probe(const double *__restrict__ x, int64_t n,
+                                                    double *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const double v = x[i];
+    if constexpr (WHICH == 0) out[i] = fast_log(v);
+    else if constexpr (WHICH == 1) out[i] = fast_log2(v);
+    else if constexpr (WHICH == 2) out[i] = erfcinv_fast(v);
+    else out[i] = erfc(v);
+  }
+}
+
+hipError_t launch_math_probe(int which, const double *x, int64_t n, double *out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  switch (which) {
+    case 0: k_math_probe<0><<<blocks, 256, 0, st>>>(x, n, out); break;
+    case 1: k_math_probe<1><<<blocks, 256, 0, st>>>(x, n, out); break;
+    case 2: k_math_probe<2><<<blocks, 256, 0, st>>>(x, n, out); break;
+    default: k_math_probe<3><<<blocks, 256, 0, st>>>(x, n, out); break;
   }
   return hipGetLastError();
 }

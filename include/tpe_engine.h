@@ -569,6 +569,13 @@ int tpe_plan_set_prune(tpe_plan_t p, int32_t mode);
  * pairs/s, 8 per block evaluation).                                         */
 int tpe_microbench(tpe_handle_t h, int32_t which, double *per_second);
 
+/* Test probe of the device math helpers: out[i] = f(x[i]), i < n (host
+ * pointers), with f = 0 fast_log, 1 fast_log2, 2 erfcinv_fast, 3 the library
+ * erfc the draw table and the draw screen's zones call.  One element per
+ * thread in 256-thread blocks, so wave j holds x[64 j .. 64 j + 63].  Another
+ * `which` is TPE_E_INVALID.                                                 */
+int tpe_math_probe(tpe_handle_t h, int32_t which, const double *x, int64_t n, double *out);
+
 #ifdef __cplusplus
 }
 #endif
