@@ -48,6 +48,8 @@ EXPORTS = (
     'tpe_plan_sample_points', 'tpe_plan_topk_points', 'tpe_plan_gather_points',
     'tpe_plan_joint_fit', 'tpe_plan_joint_get_mixture', 'tpe_plan_joint_score_points',
     'tpe_plan_joint_sides', 'tpe_plan_joint_sample_points', 'tpe_math_probe',
+    'tpe_plan_group_info', 'tpe_plan_group_fit', 'tpe_plan_group_get_mixture',
+    'tpe_plan_group_score_points', 'tpe_plan_group_sides', 'tpe_plan_group_sample_points',
 )
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
@@ -166,6 +168,14 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_joint_sides': (C.c_int, [vp, vp, vp, i64]),
             'tpe_plan_joint_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, vp,
                                                        vp, i32, vp]),
+            'tpe_plan_group_info': (C.c_int, [vp, vp, C.POINTER(i32)]),
+            'tpe_plan_group_fit': (C.c_int, [vp, vp]),
+            'tpe_plan_group_get_mixture': (C.c_int, [vp, i32, i32, i32, _D, _D, _D, vp, i64,
+                                                     C.POINTER(i64)]),
+            'tpe_plan_group_score_points': (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp]),
+            'tpe_plan_group_sides': (C.c_int, [vp, i32, vp, vp, i64]),
+            'tpe_plan_group_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, vp,
+                                                       i32, vp]),
             'tpe_plan_gather_points': (C.c_int, [vp, vp, i64, vp, i32, vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
@@ -849,6 +859,121 @@ class Plan(object):
                 self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
                 comp_ptr or None, total_ptr, joint_ptr or None, terms_ptr or None,
                 active_ptr or None, 1, stream))
+
+    # ---- multivariate TPE over conditional spaces: one joint model per group
+    # of hps that are active together (tpe_plan_group_*)
+    def group_info(self):
+        """group_of_hp int32[n_hp] and the number of groups G
+        (tpe_plan_group_info): group 0 the unconditional hps, the others in
+        ascending order of their smallest hp index."""
+        e = self.engine
+        g = np.empty(self.n_hp, dtype=np.int32)
+        n = C.c_int32(0)
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_info(self.p, g.ctypes.data, C.byref(n)))
+        return g, n.value
+
+    def group_fit(self, stream=None):
+        """Build every group's joint Parzen model from the last ``fit``
+        (tpe_plan_group_fit); a later ``fit`` invalidates them."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_fit(self.p, stream))
+
+    def group_mixture(self, group, hp, side=0):
+        """``joint_mixture`` of hp ``hp`` of group ``group``
+        (tpe_plan_group_get_mixture): (w, mu, sigma, rows) in component
+        order, rows[0] = -1; ``hp = -1``: the group's component weights."""
+        e = self.engine
+        cap = max(self.max_trials + 1, 1)
+        w, mu, sg = np.empty(cap), np.empty(cap), np.empty(cap)
+        rows = np.empty(cap, dtype=np.int32)
+        k = C.c_int64(0)
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_get_mixture(self.p, int(group), int(hp), int(side),
+                                                     _dp(w), _dp(mu), _dp(sg), rows.ctypes.data,
+                                                     cap, C.byref(k)))
+        k = k.value
+        if int(hp) < 0:
+            return w[:k].copy(), np.empty(0), np.empty(0), rows[:k].copy()
+        return w[:k].copy(), mu[:k].copy(), sg[:k].copy(), rows[:k].copy()
+
+    def group_score_points(self, vals, want_active=False, want_joint=False, stream=None):
+        """``score_points`` under the group models
+        (tpe_plan_group_score_points): total = the active groups' joint in
+        group order.  Returns total[M], or (total[, active][, joint[G, M]])
+        with the ``want_`` flags; there are no per-hp terms."""
+        e = self.engine
+        vals = _f64(vals)
+        if vals.ndim != 2 or vals.shape[0] != self.n_hp:
+            raise ValueError('configurations must be a [n_hp, M] array')
+        m = vals.shape[1]
+        total = np.empty(m)
+        joint = np.empty((self.group_info()[1], m)) if want_joint else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_score_points(
+                self.p, vals.ctypes.data, m, m, total.ctypes.data,
+                joint.ctypes.data if want_joint else None,
+                active.ctypes.data if want_active else None, 0, stream))
+        out = (total,) + ((active,) if want_active else ()) + ((joint,) if want_joint else ())
+        return out[0] if len(out) == 1 else out
+
+    def group_score_points_device(self, vals_ptr, m, ld, total_ptr, joint_ptr=0, active_ptr=0,
+                                  stream=None):
+        """The same on device memory, as ``score_points_device``; joint[G][ld]
+        optional.  Stream-ordered, no host synchronisation."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_score_points(
+                self.p, vals_ptr, int(m), int(ld), total_ptr, joint_ptr or None,
+                active_ptr or None, 1, stream))
+
+    def group_sides(self, group, m):
+        """(J_below[m], J_above[m]) of ``group`` in the last group score or
+        draw, NaN where the group was inactive (tpe_plan_group_sides)."""
+        e = self.engine
+        jb, ja = np.empty(int(m)), np.empty(int(m))
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_sides(self.p, int(group), jb.ctypes.data,
+                                               ja.ctypes.data, int(m)))
+        return jb, ja
+
+    def group_sample_points(self, seed, m, begin=0, want_active=False, want_joint=False,
+                            want_comp=False, stream=None):
+        """``sample_points`` under the group models
+        (tpe_plan_group_sample_points): every active group picks one of its
+        below components and draws all its hps from it.  Returns (vals,
+        total[, active][, joint[G, m]][, comp int32[G, m], -1 where the group
+        is inactive])."""
+        e = self.engine
+        m = int(m)
+        if m < 0:
+            raise ValueError('the number of configurations must not be negative')
+        G = self.group_info()[1]
+        vals = np.empty((self.n_hp, m))
+        total = np.empty(m)
+        joint = np.empty((G, m)) if want_joint else None
+        comp = np.empty((G, m), dtype=np.int32) if want_comp else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), m, m, vals.ctypes.data,
+                comp.ctypes.data if want_comp else None, total.ctypes.data,
+                joint.ctypes.data if want_joint else None,
+                active.ctypes.data if want_active else None, 0, stream))
+        return (vals, total) + ((active,) if want_active else ()) + \
+            ((joint,) if want_joint else ()) + ((comp,) if want_comp else ())
+
+    def group_sample_points_device(self, seed, begin, m, ld, vals_ptr, total_ptr, comp_ptr=0,
+                                   joint_ptr=0, active_ptr=0, stream=None):
+        """The same into device memory, as ``sample_points_device``;
+        comp[G][ld] int32 and joint[G][ld] optional."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
+                comp_ptr or None, total_ptr, joint_ptr or None, active_ptr or None, 1, stream))
 
     def topk_points(self, total, k, eligible=None, m=None, out=None, stream=None):
         """The ``k`` eligible entries that rank first, as ``tpe.rank_pool``

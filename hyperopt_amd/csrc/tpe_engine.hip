@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "tpe_anneal.hpp"
+#include "tpe_group_plan.hpp"
 #include "tpe_internal.hpp"
 #include "tpe_level_plan.hpp"
 #include "tpe_switches.hpp"
@@ -139,6 +140,28 @@ struct tpe_plan : PlanShape {
   double *d_jsides = nullptr, *d_jjoint = nullptr;  // [2][m], [m] of the last joint score
   size_t jpt_cap = 0;
   int64_t jpt_m = 0;         // configurations of the last joint score (tpe_plan_joint_sides)
+  // one joint model per group of hps that are active together (tpe_plan_group_*,
+  // tpe_group.hip): the partition and the layout are set up by the first
+  // tpe_plan_group_info / tpe_plan_group_fit; group_ok: the tables are those of
+  // the current fit epoch
+  GroupPartition gpart;
+  GroupLayout glay;
+  bool group_ready = false, group_ok = false;
+  int32_t gkb_max = 0;       // below components of group 0, which holds every below row:
+                             // a bound on every group's
+  JointDim *d_gdims = nullptr;
+  GroupDesc *d_ggroups = nullptr;
+  int32_t *d_gdim_of_hp = nullptr, *d_ggroup_of_hp = nullptr, *d_grows = nullptr;
+  int32_t *d_gcount = nullptr, *d_gcomp = nullptr;
+  JointSide *d_gside = nullptr;
+  uint64_t *d_gkeys = nullptr;
+  double *d_gw = nullptr, *d_gcw = nullptr, *d_gcmu = nullptr, *d_gcsig = nullptr;
+  double *d_gtab = nullptr, *d_goptlog = nullptr, *d_gpick = nullptr, *d_goptcdf = nullptr;
+  size_t goptcdf_cap = 0;
+  void *d_gdraw = nullptr;   // [P] draw tables of a group draw
+  double *d_gsides = nullptr, *d_gjoint = nullptr;  // [G][2][m], [G][m] of the last group score
+  size_t gpt_cap = 0;
+  int64_t gpt_m = 0;         // configurations of the last group score (tpe_plan_group_sides)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // per-kind event ring around every scoring launch (tpe_plan_profile)
   struct Prof {
@@ -254,7 +277,11 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_pt_total, p->d_pt_act, p->d_pt_idx, p->d_pt_count, p->d_pt_tab, p->d_tk,
                   p->d_tk_idx, p->d_jdims, p->d_jdim_of_hp, p->d_jrows, p->d_jcount, p->d_jcomp,
                   p->d_jside, p->d_jkeys, p->d_jw, p->d_jcw, p->d_jcmu, p->d_jcsig, p->d_jtab,
-                  p->d_joptlog, p->d_jpick, p->d_joptcdf, p->d_jdraw, p->d_jsides, p->d_jjoint};
+                  p->d_joptlog, p->d_jpick, p->d_joptcdf, p->d_jdraw, p->d_jsides, p->d_jjoint,
+                  p->d_gdims, p->d_ggroups, p->d_gdim_of_hp, p->d_ggroup_of_hp, p->d_grows,
+                  p->d_gcount, p->d_gcomp, p->d_gside, p->d_gkeys, p->d_gw, p->d_gcw, p->d_gcmu,
+                  p->d_gcsig, p->d_gtab, p->d_goptlog, p->d_gpick, p->d_goptcdf, p->d_gdraw,
+                  p->d_gsides, p->d_gjoint};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -652,6 +679,7 @@ FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf,
   p->mom_h = f.mom_h;
   p->tab_built = false;  // a new fit epoch
   p->joint_ok = false;
+  p->group_ok = false;
   p->fit_pw = prior_weight;
   p->fit_lf = lf;
   FitArgs a{};
@@ -1695,6 +1723,7 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
   p->mom_h = p->graph_mom_h;
   p->tab_built = p->graph_tab;
   p->joint_ok = false;  // (a new fit epoch, fitted with the captured node's arguments)
+  p->group_ok = false;
   p->fit_pw = p->fit_args0[0].prior_weight;
   p->fit_lf = p->fit_args0[0].lf;
   return TPE_OK;
@@ -2374,6 +2403,400 @@ int tpe_plan_joint_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int
   if (active)
     CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
                          hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+// ---- one joint model per group of hps (tpe_group.hip, tpe_group_plan.hpp) ----
+namespace {
+
+// the partition of the plan's space (host only; no device needed)
+void ensure_group_shape(tpe_plan *p) {
+  if (!p->gpart.group_of_hp.empty()) return;
+  p->gpart = group_partition(p->hps, p->cond_parent, p->cond_branch);
+  std::vector<int32_t> lh;
+  for (auto &l : p->levels) lh.insert(lh.end(), l.begin(), l.end());
+  p->glay = group_layout(p->gpart, p->hps, lh, p->kcap);
+}
+
+// the buffers of the plan's group fit
+int alloc_group(tpe_engine *h, tpe_plan *p) {
+  const GroupLayout &L = p->glay;
+  if (p->gpart.members[0].empty())
+    return fail(h, TPE_E_INVALID, "group_fit: the space has no unconditional hp");
+  if ((int64_t)L.max_slots * 64 * 8 > kJointLdsMax)
+    return fail(h, TPE_E_INVALID, "group_fit: a group has too many hps for the scoring kernel's LDS");
+  const size_t P = (size_t)p->P, G = L.groups.size(), kc = (size_t)p->kcap;
+  CKH(dalloc(&p->d_gdims, P));
+  CKH(dalloc(&p->d_ggroups, G));
+  CKH(dalloc(&p->d_gdim_of_hp, P));
+  CKH(dalloc(&p->d_ggroup_of_hp, P));
+  CKH(hipMemcpy(p->d_gdims, L.dims.data(), P * sizeof(JointDim), hipMemcpyHostToDevice));
+  CKH(hipMemcpy(p->d_ggroups, L.groups.data(), G * sizeof(GroupDesc), hipMemcpyHostToDevice));
+  CKH(hipMemcpy(p->d_gdim_of_hp, L.dim_of_hp.data(), P * 4, hipMemcpyHostToDevice));
+  CKH(hipMemcpy(p->d_ggroup_of_hp, p->gpart.group_of_hp.data(), P * 4, hipMemcpyHostToDevice));
+  CKH(dalloc(&p->d_grows, 2 * G * kc));
+  CKH(dalloc(&p->d_gcount, 2 * G));
+  CKH(dalloc(&p->d_gside, 2 * G));
+  CKH(dalloc(&p->d_gkeys, 2 * P * kc));
+  CKH(dalloc(&p->d_gw, 2 * G * kc));
+  CKH(dalloc(&p->d_gcw, 2 * P * kc));
+  CKH(dalloc(&p->d_gcmu, 2 * P * kc));
+  CKH(dalloc(&p->d_gcsig, 2 * P * kc));
+  CKH(dalloc(&p->d_goptlog, 2 * (size_t)L.n_opt * 3));
+  CKH(dalloc(&p->d_gpick, G * kc));
+  CKH(dalloc(&p->d_gtab, (size_t)L.tab_doubles));
+  return TPE_OK;
+}
+
+// ... once; a failure part-way leaves none of them behind
+int ensure_group(tpe_engine *h, tpe_plan *p) {
+  if (p->group_ready) return TPE_OK;
+  ensure_group_shape(p);
+  const int rc = alloc_group(h, p);
+  if (rc) {
+    void **bufs[] = {(void **)&p->d_gdims, (void **)&p->d_ggroups, (void **)&p->d_gdim_of_hp,
+                     (void **)&p->d_ggroup_of_hp, (void **)&p->d_grows, (void **)&p->d_gcount,
+                     (void **)&p->d_gside, (void **)&p->d_gkeys, (void **)&p->d_gw,
+                     (void **)&p->d_gcw, (void **)&p->d_gcmu, (void **)&p->d_gcsig,
+                     (void **)&p->d_goptlog, (void **)&p->d_gpick, (void **)&p->d_gtab};
+    for (void **b : bufs) { dfree(*b); *b = nullptr; }
+    return rc;
+  }
+  p->group_ready = true;
+  return TPE_OK;
+}
+
+// per-call scratch of m group scores
+int ensure_group_points(tpe_engine *h, tpe_plan *p, size_t m) {
+  if (m > p->gpt_cap) {
+    dfree(p->d_gsides); dfree(p->d_gjoint); dfree(p->d_gcomp);
+    p->d_gsides = p->d_gjoint = nullptr;
+    p->d_gcomp = nullptr;
+    p->gpt_cap = 0;
+    const size_t G = p->glay.groups.size();
+    CKH(dalloc(&p->d_gsides, 2 * G * m));
+    CKH(dalloc(&p->d_gjoint, G * m));
+    CKH(dalloc(&p->d_gcomp, G * m));
+    p->gpt_cap = m;
+  }
+  return TPE_OK;
+}
+
+// the launch arguments of a group score or draw of m configurations, without
+// the caller's arrays (ensure_points' lists serve the groups: G <= P)
+GroupArgs group_args(tpe_plan *p, int64_t m) {
+  GroupArgs a{};
+  a.hps = p->d_hps;
+  a.dims = p->d_gdims;
+  a.groups = p->d_ggroups;
+  a.dim_of_hp = p->d_gdim_of_hp;
+  a.group_of_hp = p->d_ggroup_of_hp;
+  a.level_hps = p->d_level_hps;
+  a.cond_parent = p->d_cp;
+  a.cond_branch = p->d_cb;
+  a.n_hp = p->P;
+  a.n_group = (int32_t)p->glay.groups.size();
+  a.max_slots = p->glay.max_slots;
+  a.kb_max = p->gkb_max;
+  a.kcap = p->kcap;
+  a.K = p->d_gcount;
+  a.side = p->d_gside;
+  a.jw = p->d_gw;
+  a.cmu = p->d_gcmu;
+  a.csig = p->d_gcsig;
+  a.tab = p->d_gtab;
+  a.optlog = p->d_goptlog;
+  a.n_opt = p->glay.n_opt;
+  a.pprior = p->d_pprior;
+  a.prior_weight = p->fit_pw;
+  a.m = m;
+  a.idx = p->d_pt_idx;
+  a.count = p->d_pt_count;
+  a.sides = p->d_gsides;
+  p->gpt_m = m;
+  return a;
+}
+
+// the host-mode copies back of a group score or draw
+int group_copy_back(tpe_engine *h, tpe_plan *p, int64_t m, int64_t ld, double *total,
+                    double *joint, uint8_t *active, hipStream_t st) {
+  const size_t G = p->glay.groups.size();
+  CKH(hipMemcpyAsync(total, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (joint)
+    CKH(hipMemcpy2DAsync(joint, (size_t)ld * 8, p->d_gjoint, (size_t)m * 8, (size_t)m * 8, G,
+                         hipMemcpyDeviceToHost, st));
+  if (active)
+    CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
+                         hipMemcpyDeviceToHost, st));
+  return TPE_OK;
+}
+
+}  // namespace
+
+int tpe_plan_group_info(tpe_plan_t p, int32_t *group_of_hp, int32_t *n_groups) {
+  if (!p) return TPE_E_INVALID;
+  ensure_group_shape(p);
+  if (group_of_hp)
+    std::copy(p->gpart.group_of_hp.begin(), p->gpart.group_of_hp.end(), group_of_hp);
+  if (n_groups) *n_groups = (int32_t)p->gpart.members.size();
+  return TPE_OK;
+}
+
+int tpe_plan_group_fit(tpe_plan_t p, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, "group_fit: the plan has not been fitted (tpe_plan_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  {
+    int rc = ensure_group(h, p);
+    if (rc) return rc;
+    rc = flush_patch(h, p, st);
+    if (rc) return rc;
+  }
+  // the split of the last fit, as a mask (k_split computes k_fit's threshold)
+  FitArgs f{};
+  f.losses = p->d_losses;
+  f.n = p->n;
+  f.n_below = p->last_nb;
+  f.sortbuf = p->d_sortbuf;
+  f.scap = p->scap;
+  f.kcap = p->kcap;
+  CKH(launch_split(f, p->d_below, st));
+  GroupFitArgs a{};
+  a.hps = p->d_hps;
+  a.dims = p->d_gdims;
+  a.groups = p->d_ggroups;
+  a.dim_of_hp = p->d_gdim_of_hp;
+  a.group_of_hp = p->d_ggroup_of_hp;
+  a.n_group = (int32_t)p->glay.groups.size();
+  a.n_hp = p->P;
+  a.vals = p->d_vals;
+  a.active = p->d_active;
+  a.ld = p->ncap;
+  a.n = p->n;
+  a.below = p->d_below;
+  a.lf = p->fit_lf;
+  a.prior_weight = p->fit_pw;
+  a.pprior = p->d_pprior;
+  a.info = p->d_info;
+  a.mw = p->d_mw;
+  a.mmu = p->d_mmu;
+  a.msig = p->d_msig;
+  a.kcap = p->kcap;
+  a.keys = p->d_gkeys;
+  a.rows = p->d_grows;
+  a.count = p->d_gcount;
+  a.side = p->d_gside;
+  a.jw = p->d_gw;
+  a.cw = p->d_gcw;
+  a.cmu = p->d_gcmu;
+  a.csig = p->d_gcsig;
+  a.tab = p->d_gtab;
+  a.optlog = p->d_goptlog;
+  a.n_opt = p->glay.n_opt;
+  CKH(launch_group_fit(a, st));
+  // (group 0 holds every row of a side; a group's below rows are among them)
+  p->gkb_max = (int32_t)std::min<int64_t>(std::max<int64_t>(p->last_nb, 0), p->n) + 1;
+  p->group_ok = true;
+  return TPE_OK;
+}
+
+int tpe_plan_group_get_mixture(tpe_plan_t p, int32_t group, int32_t hp, int32_t side, double *w,
+                               double *mu, double *sigma, int32_t *rows, int64_t cap,
+                               int64_t *k) {
+  if (!p || !k) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!p->group_ok)
+    return fail(h, TPE_E_INVALID, "group_get_mixture: no group fit (tpe_plan_group_fit first)");
+  const int32_t G = (int32_t)p->glay.groups.size();
+  if (group < 0 || group >= G || hp < -1 || hp >= p->P || side < 0 || side > 1)
+    return fail(h, TPE_E_INVALID, "bad group/hp/side");
+  if (hp >= 0 && p->gpart.group_of_hp[(size_t)hp] != group)
+    return fail(h, TPE_E_INVALID, "group_get_mixture: the hp is not in that group");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const int64_t gs = (int64_t)group * 2 + side;
+  int32_t K32 = 0;
+  CKH(hipMemcpy(&K32, p->d_gcount + gs, 4, hipMemcpyDeviceToHost));
+  const int64_t K = K32;
+  *k = K;
+  if (K > cap) return fail(h, TPE_E_INVALID, "capacity too small");
+  const size_t bytes = (size_t)K * 8;
+  if (rows)
+    CKH(hipMemcpy(rows, p->d_grows + gs * p->kcap, (size_t)K * 4, hipMemcpyDeviceToHost));
+  if (hp < 0) {  // the component weights themselves
+    if (w) CKH(hipMemcpy(w, p->d_gw + gs * p->kcap, bytes, hipMemcpyDeviceToHost));
+    return TPE_OK;
+  }
+  const int64_t ds = ((int64_t)hp * 2 + side) * p->kcap;
+  if (w) CKH(hipMemcpy(w, p->d_gcw + ds, bytes, hipMemcpyDeviceToHost));
+  if (mu) CKH(hipMemcpy(mu, p->d_gcmu + ds, bytes, hipMemcpyDeviceToHost));
+  if (sigma) CKH(hipMemcpy(sigma, p->d_gcsig + ds, bytes, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+// Whole configurations under the group models: tpe_plan_score_points' staging
+// and conventions; one walk, one scoring launch over all groups, one sum.
+int tpe_plan_group_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                                double *total, double *joint, uint8_t *active,
+                                int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, "group_score_points: need 0 <= m <= ld");
+  if (m > 0 && (!vals || !total))
+    return fail(h, TPE_E_INVALID, "group_score_points: vals and total must not be null");
+  if (m > (int64_t)INT32_MAX)
+    return fail(h, TPE_E_INVALID, "group_score_points: too many configurations");
+  if (m == 0) return TPE_OK;
+  if (!p->group_ok)
+    return fail(h, TPE_E_INVALID, "group_score_points: no group fit (tpe_plan_group_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+    rc = ensure_group_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+  GroupArgs a = group_args(p, m);
+  if (dev) {
+    a.vals = vals;
+    a.ld = ld;
+    a.total = total;
+    a.active = active ? active : p->d_pt_act;
+    a.act_ld = active ? ld : m;
+    a.joint = joint ? joint : p->d_gjoint;
+    a.joint_ld = joint ? ld : m;
+    CKH(launch_group_points(a, true, st));
+    return TPE_OK;
+  }
+  if (ld == m)  // (contiguous: one plain copy)
+    CKH(hipMemcpyAsync(p->d_pt_vals, vals, (size_t)m * p->P * 8, hipMemcpyHostToDevice, st));
+  else
+    CKH(hipMemcpy2DAsync(p->d_pt_vals, (size_t)m * 8, vals, (size_t)ld * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyHostToDevice, st));
+  a.vals = p->d_pt_vals;
+  a.ld = m;
+  a.total = p->d_pt_total;
+  a.active = p->d_pt_act;
+  a.act_ld = m;
+  a.joint = p->d_gjoint;
+  a.joint_ld = m;
+  CKH(launch_group_points(a, true, st));
+  {
+    const int rc = group_copy_back(h, p, m, ld, total, joint, active, st);
+    if (rc) return rc;
+  }
+  CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+int tpe_plan_group_sides(tpe_plan_t p, int32_t group, double *below, double *above, int64_t m) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (group < 0 || group >= (int32_t)p->glay.groups.size())
+    return fail(h, TPE_E_INVALID, "group_sides: no such group");
+  if (!p->group_ok)
+    return fail(h, TPE_E_INVALID, "group_sides: no group fit (a later tpe_plan_fit drops the sides)");
+  if (m < 0 || m > p->gpt_m)
+    return fail(h, TPE_E_INVALID, "group_sides: more entries than the last group score holds");
+  if (m == 0) return TPE_OK;
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const double *s = p->d_gsides + (int64_t)group * 2 * p->gpt_m;
+  if (below) CKH(hipMemcpy(below, s, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (above) CKH(hipMemcpy(above, s + p->gpt_m, (size_t)m * 8, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+// Whole configurations drawn from the groups' below models and scored: the
+// walk picks one component per active group and draws the group's hps from
+// it; then tpe_plan_group_score_points' launches behind the draw's own lists.
+int tpe_plan_group_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m, int64_t ld,
+                                 double *vals, int32_t *comp, double *total, double *joint,
+                                 uint8_t *active, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, "group_sample_points: need 0 <= m <= ld");
+  if (begin < 0) return fail(h, TPE_E_INVALID, "group_sample_points: begin must not be negative");
+  if (m > 0 && (!vals || !total))
+    return fail(h, TPE_E_INVALID, "group_sample_points: vals and total must not be null");
+  if (m > (int64_t)INT32_MAX)
+    return fail(h, TPE_E_INVALID, "group_sample_points: too many configurations");
+  if (m == 0) return TPE_OK;
+  if (!p->group_ok)
+    return fail(h, TPE_E_INVALID, "group_sample_points: no group fit (tpe_plan_group_fit first)");
+  if (p->gkb_max > kTabCap)
+    return fail(h, TPE_E_INVALID, "group_sample_points: more below components than a draw table holds");
+  for (const JointDim &d : p->glay.dims)
+    if (d.upper > kTabCap)
+      return fail(h, TPE_E_INVALID, "group_sample_points: a choice has more options than a draw table holds");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+    rc = ensure_group_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  if (!p->d_gdraw) CKH(hipMalloc(&p->d_gdraw, joint_sample_tables_bytes(p->P)));
+  const size_t need = (size_t)p->glay.n_opt * (size_t)p->gkb_max;
+  if (need > p->goptcdf_cap) {
+    dfree(p->d_goptcdf);
+    p->d_goptcdf = nullptr;
+    p->goptcdf_cap = 0;
+    CKH(dalloc(&p->d_goptcdf, need));
+    p->goptcdf_cap = need;
+  }
+  CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+  GroupArgs a = group_args(p, m);
+  a.seed = seed;
+  a.begin = begin;
+  a.dtab = static_cast<DrawTableT<kTabCap> *>(p->d_gdraw);
+  a.pick_cdf = p->d_gpick;
+  a.opt_cdf = p->d_goptcdf;
+  if (dev) {
+    a.out = vals;
+    a.vals = vals;
+    a.ld = ld;
+    a.total = total;
+    a.active = active ? active : p->d_pt_act;
+    a.act_ld = active ? ld : m;
+    a.joint = joint ? joint : p->d_gjoint;
+    a.joint_ld = joint ? ld : m;
+    a.comp = comp ? comp : p->d_gcomp;
+    a.comp_ld = comp ? ld : m;
+    CKH(launch_group_sample(a, st));
+    CKH(launch_group_points(a, false, st));
+    return TPE_OK;
+  }
+  a.out = p->d_pt_vals;
+  a.vals = p->d_pt_vals;
+  a.ld = m;
+  a.total = p->d_pt_total;
+  a.active = p->d_pt_act;
+  a.act_ld = m;
+  a.joint = p->d_gjoint;
+  a.joint_ld = m;
+  a.comp = p->d_gcomp;
+  a.comp_ld = m;
+  CKH(launch_group_sample(a, st));
+  CKH(launch_group_points(a, false, st));
+  CKH(hipMemcpy2DAsync(vals, (size_t)ld * 8, p->d_pt_vals, (size_t)m * 8, (size_t)m * 8,
+                       (size_t)p->P, hipMemcpyDeviceToHost, st));
+  if (comp)
+    CKH(hipMemcpy2DAsync(comp, (size_t)ld * 4, p->d_gcomp, (size_t)m * 4, (size_t)m * 4,
+                         p->glay.groups.size(), hipMemcpyDeviceToHost, st));
+  {
+    const int rc = group_copy_back(h, p, m, ld, total, joint, active, st);
+    if (rc) return rc;
+  }
   CKH(hipStreamSynchronize(st));
   return TPE_OK;
 }

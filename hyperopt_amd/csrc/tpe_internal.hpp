@@ -807,6 +807,103 @@ size_t joint_sample_tables_bytes(int32_t n_hp);
 // k_joint_tables, k_joint_sample (values, activity, lists); the caller scores
 hipError_t launch_joint_sample(const JointSampleArgs &s, hipStream_t st);
 
+// One joint Parzen model per group of hps that are always active together
+// (tpe_group.hip; tpe_plan_group_*; tpe_group_plan.hpp).  Group
+// g's side s holds the rows of the split side in which the group is active,
+// K_gs = n_gs + 1 components; the kernels per dim are the root model's.  The
+// dims of all groups lie back to back (GroupDesc::dim_begin), the scoring
+// tables per group as the root model lays them out:
+//   [group][side][kcap / 8 blocks][ 8 log2 w | per dim of the group 3 x 8 ]
+// and everything per hp is indexed by the hp: [P][2][kcap].
+struct GroupDesc {
+  int32_t lead;       // the group's first hp in level_hps order: the walk decides the
+                      // group's activity (and the draw its component) there
+  int32_t dim_begin;  // its dims in the dims array, ascending hp index
+  int32_t n_dim;
+  int32_t n_slots;    // staged values per configuration (k_group_score)
+  int64_t tab_off;    // doubles before the group's tables
+};
+struct GroupFitArgs {
+  const tpe_hp *hps;
+  const JointDim *dims;         // [P]
+  const GroupDesc *groups;      // [G]
+  const int32_t *dim_of_hp;     // [P]
+  const int32_t *group_of_hp;   // [P]
+  int32_t n_group;
+  int32_t n_hp;
+  const double *vals;           // [P][ld] history
+  const uint8_t *active;        // [P][ld]
+  int64_t ld;
+  int64_t n;                    // history rows
+  const uint8_t *below;         // [n] the split of the last fit (k_split)
+  int32_t lf;
+  int32_t pad;
+  double prior_weight;
+  const double *pprior;
+  const MixInfo *info;          // the marginal fit: [2P]
+  const double *mw, *mmu, *msig;  // [2P][kcap]
+  int64_t kcap;
+  uint64_t *keys;               // [P][2][kcap] scratch: the rows' sort keys
+  // out
+  int32_t *rows;                // [G][2][kcap] rows[0] = -1
+  int32_t *count;               // [G][2] K_gs
+  JointSide *side;              // [G][2]
+  double *jw;                   // [G][2][kcap] component weights
+  double *cw, *cmu, *csig;      // [P][2][kcap] as JointFitArgs' (per hp)
+  double *tab;
+  double *optlog;               // [2][n_opt][3]
+  int64_t n_opt;
+};
+// k_group_rows, k_group_dims
+hipError_t launch_group_fit(const GroupFitArgs &a, hipStream_t st);
+
+// scoring and drawing whole configurations under the group models
+struct GroupArgs {
+  const tpe_hp *hps;
+  const JointDim *dims;
+  const GroupDesc *groups;
+  const int32_t *dim_of_hp, *group_of_hp;
+  const int32_t *level_hps;     // every hp id, parents first
+  const int32_t *cond_parent, *cond_branch;
+  int32_t n_hp, n_group;
+  int32_t max_slots;            // the widest group's staged values (dynamic LDS)
+  int32_t kb_max;               // bound on every group's below components (opt_cdf stride)
+  int64_t kcap;
+  const int32_t *K;             // [G][2]
+  const JointSide *side;        // [G][2]
+  const double *jw;             // [G][2][kcap]
+  const double *cmu, *csig;     // [P][2][kcap]
+  const double *tab;
+  const double *optlog;         // [2][n_opt][3]
+  int64_t n_opt;
+  const double *pprior;
+  double prior_weight;
+  // the configurations
+  const double *vals;           // [P][ld]
+  int64_t m, ld;
+  uint8_t *active;              // [P][act_ld] out
+  int64_t act_ld;
+  int32_t *idx;                 // [G][m] each non-root group's active configurations
+  uint32_t *count;              // [G] their number (zero before the call)
+  double *sides;                // [G][2][m] J_below, J_above (NaN where inactive)
+  double *joint;                // [G][joint_ld] (+0.0 where inactive)
+  int64_t joint_ld;
+  double *total;                // [m] the groups' joint in group order
+  // the draw (out == vals)
+  double *out;
+  uint64_t seed;
+  int64_t begin;
+  DrawTableT<kTabCap> *dtab;    // [P] scratch: truncation constants per component
+  double *pick_cdf;             // [G][kcap] scratch: inclusive CDFs of the below weights
+  double *opt_cdf;              // [n_opt][kb_max] scratch: per CAT dim [K][upper] CDFs of kappa
+  int32_t *comp;                // [G][comp_ld] out: the picked component, -1 where inactive
+  int64_t comp_ld;
+};
+// k_group_active (walk: the caller's launch did not write the lists), k_group_score, k_group_sum
+hipError_t launch_group_points(const GroupArgs &a, bool walk, hipStream_t st);
+// k_group_tables, k_group_sample (values, components, activity, lists); the caller scores
+hipError_t launch_group_sample(const GroupArgs &a, hipStream_t st);
+
 // Device top-k of totals and the gather of the picked columns (tpe_topk.hip;
 // tpe_plan_topk_points, tpe_plan_gather_points)
 constexpr int kTopkMax = 4096;

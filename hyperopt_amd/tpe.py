@@ -293,15 +293,65 @@ def root_indices(cs):
     return [i for i, h in enumerate(cs.hps) if len(h.conds()) == 0]
 
 
+def hp_groups(cs):
+    """The hps of a space in groups that are always active together -- the
+    joint models of ``multivariate='groups'`` -- as a list of label tuples: a
+    group is a maximal set of hps with the same set of immediate
+    (parent, branch) alternatives (``conds()`` as a set); group 0 holds the
+    unconditional hps, the others follow in ascending order of their smallest
+    hp index, labels in hp index order.  A label shared by two branches has
+    both alternatives and is a group of its own."""
+    groups, where = [[]], {frozenset(): 0}
+    for h in cs.hps:
+        key = frozenset(h.conds())
+        if key not in where:
+            where[key] = len(groups)
+            groups.append([])
+        groups[where[key]].append(h.label)
+    return [tuple(g) for g in groups]
+
+
+def _mode(multivariate):
+    """``multivariate=`` checked: False (marginal), True (joint over the
+    unconditional hps) or 'groups' (one joint model per ``hp_groups`` group)."""
+    if isinstance(multivariate, (bool, np.bool_)):
+        return bool(multivariate)
+    if isinstance(multivariate, str) and multivariate == 'groups':
+        return 'groups'
+    raise ValueError("multivariate must be False, True or 'groups', got %r" % (multivariate,))
+
+
 def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate=False):
     """Push the history and fit, exactly as ``suggest`` does (st.lock held).
     ``multivariate``: also the joint model over the unconditional hps, which
-    every history row must hold (ValueError otherwise)."""
+    every history row must hold (ValueError otherwise); 'groups': the joint
+    model of every ``hp_groups`` group, whose hps must be active in exactly
+    the same history rows (ValueError otherwise)."""
+    multivariate = _mode(multivariate)
     engine = engine or E.default_engine()
     plan = st.plan_for(domain, hist.n, engine)
     hist.push(plan)
     plan.fit(gamma=gamma, prior_weight=prior_weight, lf=DEFAULT_LF)
-    if multivariate:
+    if multivariate == 'groups':
+        cs = domain.space
+        index = {lab: i for i, lab in enumerate(cs.labels)}
+        act = np.asarray(hist.active)[:, :hist.n] != 0
+        for g, labs in enumerate(hp_groups(cs)):
+            if not labs:
+                continue
+            rows = [index[lab] for lab in labs]
+            # the roots against all rows, every other group against its first hp
+            want = np.ones(hist.n, dtype=bool) if g == 0 else act[rows[0]]
+            bad = np.argwhere((act[rows] != want).T)       # (row, hp) in row order
+            if len(bad):
+                j, i = (int(x) for x in bad[0])
+                if g == 0:
+                    raise ValueError('multivariate TPE: history row %d has no value for the '
+                                     'unconditional hp %r' % (j, labs[i]))
+                raise ValueError('multivariate TPE: in history row %d the hps %r and %r of one '
+                                 'group are not active together' % (j, labs[0], labs[i]))
+        plan.group_fit()
+    elif multivariate:
         roots = root_indices(domain.space)
         act = np.asarray(hist.active)[roots, :hist.n]
         if not act.all():
@@ -333,7 +383,17 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     Optuna's ``multivariate=True``), which sees interactions
     between them: ``EI(c) = joint(c) + the conditional hps' terms``.  With
     ``return_terms`` the result is (EI, terms, active, joint[M]); the terms of
-    unconditional labels are 0.0."""
+    unconditional labels are 0.0.
+
+    ``multivariate='groups'``: every ``hp_groups`` group -- the unconditional
+    hps, and the hps of each branch -- is scored under a joint model of its
+    own, fitted on the history rows in which the group is active (Optuna's
+    ``group=True``), so interactions inside a branch are seen
+    too: ``EI(c) = the sum of joint_g(c) over the groups active in c``.  With
+    ``return_terms`` the result is (EI, terms, active, joint[G, M]) with
+    ``joint`` in ``hp_groups`` order (0.0 where a group is inactive); all
+    terms are 0.0.  Any other value of ``multivariate`` is a ValueError."""
+    multivariate = _mode(multivariate)
     cs = domain.space
     as_dicts = not isinstance(configs, np.ndarray)
     vals, present = config_columns(cs, configs)
@@ -344,7 +404,11 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
             raise ValueError('score_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
         joint = None
-        if multivariate:
+        if multivariate == 'groups':
+            total, active, joint = plan.group_score_points(vals, want_active=True,
+                                                           want_joint=True)
+            terms = np.zeros(vals.shape)
+        elif multivariate:
             total, terms, active, joint = plan.joint_score_points(
                 vals, want_terms=True, want_active=True, want_joint=True)
         else:
@@ -372,15 +436,18 @@ class _Pool(object):
 
     def totals(self, plan, multivariate=False):
         """EI of every pool configuration under ``plan``'s fit."""
+        groups = multivariate == 'groups'
         if not isinstance(self.source, np.ndarray) or self.m == 0:
-            return (plan.joint_score_points if multivariate else plan.score_points)(self.vals)
+            return (plan.group_score_points if groups else plan.joint_score_points
+                    if multivariate else plan.score_points)(self.vals)
         # an array pool lives on the device: uploaded once, scored in place
         eng = plan.engine
         if self._dev is None or self._dev[0] is not eng:
             self._dev = (eng, E.DeviceBuffer(eng, self.vals.nbytes).upload(self.vals),
                          E.DeviceBuffer(eng, 8 * self.m))
         _, v, out = self._dev
-        score = plan.joint_score_points_device if multivariate else plan.score_points_device
+        score = (plan.group_score_points_device if groups else plan.joint_score_points_device
+                 if multivariate else plan.score_points_device)
         score(v.ptr, self.m, self.m, out.ptr)
         return out.download(np.empty(self.m))
 
@@ -435,8 +502,10 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     a trial already in the history.  While the history has fewer than
     ``n_startup_jobs`` trials the picks are ``np.random.RandomState(seed)
     .choice(M, k, replace=False)`` over the whole pool.  ValueError when fewer
-    than ``len(new_ids)`` eligible configurations remain.  ``multivariate``:
-    the pool is ranked by ``score_configs(..., multivariate=True)``."""
+    than ``len(new_ids)`` eligible configurations remain.  ``multivariate``
+    (True or 'groups'): the pool is ranked by ``score_configs`` with that
+    argument."""
+    multivariate = _mode(multivariate)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -494,7 +563,12 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     below model -- the prior or one good trial -- and draws all its
     unconditional hps from that component's kernels, so they keep the good
     trials' correlations; the EI is ``score_configs(..., multivariate=True)``'s
-    (tpe_plan_joint_sample_points)."""
+    (tpe_plan_joint_sample_points).  ``multivariate='groups'``: every group
+    the configuration activates picks a component of its own below model and
+    draws the group's hps from it, parents first; the EI is
+    ``score_configs(..., multivariate='groups')``'s
+    (tpe_plan_group_sample_points)."""
+    multivariate = _mode(multivariate)
     cs = domain.space
     st = _state(domain)
     with st.lock:
@@ -502,7 +576,8 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
-        draw = plan.joint_sample_points if multivariate else plan.sample_points
+        draw = (plan.group_sample_points if multivariate == 'groups' else
+                plan.joint_sample_points if multivariate else plan.sample_points)
         vals, total = draw(batch_seeds(seed, 1)[0], int(n), begin=int(begin))
     if as_dicts:
         return columns_to_configs(cs, vals, ~np.isnan(vals)), total
@@ -624,8 +699,9 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     ValueError).
 
     ``multivariate``: the draw and its ranking are
-    ``sample_configs(..., multivariate=True)``'s; everything else is as
-    above."""
+    ``sample_configs``' with that argument (True or 'groups'); everything
+    else is as above."""
+    multivariate = _mode(multivariate)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -646,7 +722,8 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     with st.lock:
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
-        draw = plan.joint_sample_points_device if multivariate else plan.sample_points_device
+        draw = (plan.group_sample_points_device if multivariate == 'groups' else
+                plan.joint_sample_points_device if multivariate else plan.sample_points_device)
         draw(batch_seeds(seed, 1)[0], 0, n, n, d_vals.ptr, d_total.ptr)
         vals = eligible = None
         n_el = n

@@ -395,6 +395,79 @@ int tpe_plan_joint_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int
                                  double *joint, double *terms, uint8_t *active,
                                  int32_t on_device, void *stream);
 
+/* Multivariate TPE over conditional spaces: one joint Parzen model per group
+ * of hps that are always active together.  A group is a maximal set of hps
+ * with the same set of immediate (parent, branch) condition alternatives;
+ * group 0 holds the hps without a condition, the other groups follow in
+ * ascending order of their smallest hp index, and inside a group the hps keep
+ * ascending index.  tpe_plan_group_info writes each hp's group and the number
+ * of groups G (either output may be NULL; needs no fit).
+ * Group g's side s holds the rows of the last tpe_plan_fit's split side in
+ * which the group is active (the activity column of its hps, which must agree:
+ * not checked; group 0 takes every row, as the root model does), in row order, n_gs of them, and K_gs = n_gs + 1 components:
+ * component 0 the prior, component k that side's k-th such row, w_0 =
+ * prior_weight / (S + prior_weight), w_k = lw[k - 1] / (S + prior_weight) with
+ * lw the linear-forgetting weights over the n_gs rows (ones unless lf < n_gs)
+ * and S their sum; an empty side is the prior alone.  Per hp of the group the
+ * component's kernel is the root model's above: for a continuous hp the
+ * (mu, sigma) its marginal fit gave the row's observation, for a categorical
+ * hp kappa with a = prior_weight (upper - 1) / (S + prior_weight) on the
+ * group's own S; no truncation normaliser.
+ * J_gs(c) = logsumexp_k [log w_k + sum_{d in g} log kappa_dk(c_d)],
+ * joint_g(c) = J_g,below(c) - J_g,above(c), and EI(c) = the float64 sum, in
+ * ascending group order from +0.0, of joint_g(c) over the groups active in c
+ * (an inactive group adds +0.0).  A group is active in c when one of its
+ * (parent, branch) alternatives holds with the parent active; group 0 always.
+ * The root model of tpe_plan_joint_* is group 0 of this one, bit for bit.
+ * tpe_plan_group_fit builds every group's tables from the last tpe_plan_fit
+ * (TPE_E_INVALID before one, or for a space without an unconditional hp); a
+ * later fit invalidates them.  Stream-ordered.                              */
+int tpe_plan_group_info(tpe_plan_t p, int32_t *group_of_hp, int32_t *n_groups);
+int tpe_plan_group_fit(tpe_plan_t p, void *stream);
+/* tpe_plan_joint_get_mixture for hp `hp` of group `group`: its k = K_gs
+ * components in component order, rows[0] = -1; w, mu, sigma are the entries of
+ * the hp's marginal mixture that row owns, bit for bit (categorical: w = the
+ * component weight, mu = the observed option, sigma = a).  hp = -1: the
+ * group's component weights in w.  TPE_E_INVALID for an hp of another group
+ * or without a group fit.  Synchronizes the device.                          */
+int tpe_plan_group_get_mixture(tpe_plan_t p, int32_t group, int32_t hp, int32_t side,
+                               double *w, double *mu, double *sigma, int32_t *rows,
+                               int64_t cap, int64_t *k);
+/* EI of m whole configurations under the group models: total[m], and optional
+ * joint[G][ld] (joint_g per configuration, +0.0 where the group is inactive)
+ * and active[n_hp][ld].  Layouts, on_device, the NULL outputs, m == 0 and the
+ * errors are tpe_plan_joint_score_points'; there are no per-hp terms.  A NaN
+ * value, or a choice that is not an integer in [0, upper), inside an active
+ * group gives NaN joint_g and total and activates no child.  A
+ * configuration's numbers depend on its own values and the fit alone.
+ * TPE_E_INVALID without a group fit.                                        */
+int tpe_plan_group_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                                double *total, double *joint, uint8_t *active,
+                                int32_t on_device, void *stream);
+/* Debug: J_g,below and J_g,above (either may be NULL) of group `group` for the
+ * first m configurations of the plan's last tpe_plan_group_score_points or
+ * tpe_plan_group_sample_points call, NaN where the group was inactive.
+ * TPE_E_INVALID without a group fit (a later tpe_plan_fit drops the sides) or
+ * for more entries than that call held.  Synchronizes the device.           */
+int tpe_plan_group_sides(tpe_plan_t p, int32_t group, double *below, double *above,
+                         int64_t m);
+/* tpe_plan_sample_points under the group models.  The hps are visited parents
+ * first.  Where configuration c = begin + j activates group g, comp[g][j]
+ * (comp[G][ld], may be NULL) = tpe_sample(TPE_CAT, the group's below component
+ * weights, stream 2^29 | (n_hp + g), offset c), and every hp d of the group
+ * draws from that component as tpe_plan_joint_sample_points draws a root: a
+ * continuous hp tpe_sample of the one-component mixture (1.0, mu_d,comp,
+ * sigma_d,comp), a categorical one tpe_sample(TPE_CAT, kappa_d,comp), stream
+ * 2^29 | d, offset c.  Where the group is inactive its hps are NaN and comp is
+ * -1.  total, joint and active are what tpe_plan_group_score_points returns
+ * for the drawn vals, bit for bit.  The draws depend on (seed, c) only.
+ * TPE_E_INVALID as tpe_plan_sample_points, without a group fit, or with more
+ * than 2048 below components of a group or options of a choice.             */
+int tpe_plan_group_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m,
+                                 int64_t ld, double *vals, int32_t *comp, double *total,
+                                 double *joint, uint8_t *active, int32_t on_device,
+                                 void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
