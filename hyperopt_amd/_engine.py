@@ -50,7 +50,10 @@ EXPORTS = (
     'tpe_plan_joint_sides', 'tpe_plan_joint_sample_points', 'tpe_math_probe',
     'tpe_plan_group_info', 'tpe_plan_group_fit', 'tpe_plan_group_get_mixture',
     'tpe_plan_group_score_points', 'tpe_plan_group_sides', 'tpe_plan_group_sample_points',
+    'tpe_plan_group_batch_points',
 )
+
+BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
 # give byte-identical suggests (the large-draw value-bucketing block)
@@ -176,6 +179,8 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_group_sides': (C.c_int, [vp, i32, vp, vp, i64]),
             'tpe_plan_group_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, vp,
                                                        i32, vp]),
+            'tpe_plan_group_batch_points': (C.c_int, [vp, vp, i64, i64, vp, i32, vp, vp, vp, i32,
+                                                      vp]),
             'tpe_plan_gather_points': (C.c_int, [vp, vp, i64, vp, i32, vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
@@ -974,6 +979,45 @@ class Plan(object):
             e.check(e.lib.tpe_plan_group_sample_points(
                 self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
                 comp_ptr or None, total_ptr, joint_ptr or None, active_ptr or None, 1, stream))
+
+    def group_batch_points(self, vals, k, eligible=None, want_trace=False, stream=None):
+        """A batch of ``k`` configurations for parallel workers
+        (tpe_plan_group_batch_points): greedy picks over ``vals[n_hp, M]`` --
+        the configurations of the plan's last ``group_score_points`` /
+        ``group_sample_points`` call -- each pick joining the above side of its
+        active groups as a pending component before the next round.  Returns
+        (idx int32[k], gain[k]) with gain[t] the pick's score in its round;
+        ``want_trace`` adds trace[k, M], every configuration's score in every
+        round.  ValueError when fewer than ``k`` selectable ones remain."""
+        e = self.engine
+        vals = _f64(vals)
+        if vals.ndim != 2 or vals.shape[0] != self.n_hp:
+            raise ValueError('configurations must be a [n_hp, M] array')
+        m, k = vals.shape[1], int(k)
+        el = None if eligible is None else np.ascontiguousarray(
+            np.asarray(eligible).ravel() != 0, dtype=np.uint8)
+        if el is not None and el.size != m:
+            raise ValueError('eligible must have one entry per configuration')
+        idx = np.empty(max(k, 0), dtype=np.int32)
+        gain = np.empty(max(k, 0))
+        trace = np.empty((max(k, 0), m)) if want_trace else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_batch_points(
+                self.p, vals.ctypes.data, m, m, None if el is None else el.ctypes.data, k,
+                idx.ctypes.data, gain.ctypes.data, trace.ctypes.data if want_trace else None,
+                0, stream))
+        return (idx, gain, trace) if want_trace else (idx, gain)
+
+    def group_batch_points_device(self, vals_ptr, m, ld, k, idx_ptr, gain_ptr=0, eligible_ptr=0,
+                                  trace_ptr=0, stream=None):
+        """The same on device memory: vals[n_hp][ld], eligible[m] (0: all),
+        idx int32[k], gain[k] and trace[k][ld] (0: not wanted).  Stream-ordered
+        but for the read-back that reports a short batch."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_batch_points(
+                self.p, vals_ptr, int(m), int(ld), eligible_ptr or None, int(k), idx_ptr,
+                gain_ptr or None, trace_ptr or None, 1, stream))
 
     def topk_points(self, total, k, eligible=None, m=None, out=None, stream=None):
         """The ``k`` eligible entries that rank first, as ``tpe.rank_pool``

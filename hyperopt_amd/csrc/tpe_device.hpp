@@ -100,6 +100,16 @@ __device__ __forceinline__ uint64_t sort_key(double v) {
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
+// tpe.rank_pool's order of a total as an unsigned key (tpe_topk.hip,
+// tpe_batch.hip): descending unsigned key = the ranking, NaN 0, then -inf ..
+// -0 = +0 .. +inf
+__device__ __forceinline__ uint64_t topk_key(double x) {
+  if (x != x) return 0ull;
+  uint64_t b = (uint64_t)__double_as_longlong(x);
+  if ((b << 1) == 0ull) b = 0ull;  // -0.0 ranks with +0.0
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
 // (key, position) lexicographic order
 __device__ __forceinline__ bool kp_less(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb) {
   return ka < kb || (ka == kb && pa < pb);

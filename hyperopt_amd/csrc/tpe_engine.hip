@@ -162,6 +162,14 @@ struct tpe_plan : PlanShape {
   double *d_gsides = nullptr, *d_gjoint = nullptr;  // [G][2][m], [G][m] of the last group score
   size_t gpt_cap = 0;
   int64_t gpt_m = 0;         // configurations of the last group score (tpe_plan_group_sides)
+  // tpe_plan_group_batch_points (tpe_batch.hip): the call's state for bt_cap
+  // configurations, the picks of a host-mode call, and its trace rows
+  double *d_bt_ja = nullptr, *d_bt_score = nullptr, *d_bt_gain = nullptr, *d_bt_trace = nullptr;
+  uint8_t *d_bt_gact = nullptr, *d_bt_state = nullptr;
+  void *d_bt_slot = nullptr, *d_bt_rec = nullptr;
+  int32_t *d_bt_idx = nullptr;
+  size_t bt_cap = 0, bt_trace_cap = 0;
+  int64_t bt_m = -1;         // configurations of the last group score since the group fit
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // per-kind event ring around every scoring launch (tpe_plan_profile)
   struct Prof {
@@ -281,7 +289,9 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_gdims, p->d_ggroups, p->d_gdim_of_hp, p->d_ggroup_of_hp, p->d_grows,
                   p->d_gcount, p->d_gcomp, p->d_gside, p->d_gkeys, p->d_gw, p->d_gcw, p->d_gcmu,
                   p->d_gcsig, p->d_gtab, p->d_goptlog, p->d_gpick, p->d_goptcdf, p->d_gdraw,
-                  p->d_gsides, p->d_gjoint};
+                  p->d_gsides, p->d_gjoint, p->d_bt_ja, p->d_bt_score, p->d_bt_gain,
+                  p->d_bt_trace, p->d_bt_gact, p->d_bt_state, p->d_bt_slot, p->d_bt_rec,
+                  p->d_bt_idx};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -2515,6 +2525,7 @@ GroupArgs group_args(tpe_plan *p, int64_t m) {
   a.count = p->d_pt_count;
   a.sides = p->d_gsides;
   p->gpt_m = m;
+  p->bt_m = m;
   return a;
 }
 
@@ -2601,6 +2612,7 @@ int tpe_plan_group_fit(tpe_plan_t p, void *stream) {
   // (group 0 holds every row of a side; a group's below rows are among them)
   p->gkb_max = (int32_t)std::min<int64_t>(std::max<int64_t>(p->last_nb, 0), p->n) + 1;
   p->group_ok = true;
+  p->bt_m = -1;  // (the sides of an earlier fit's score are not this model's)
   return TPE_OK;
 }
 
@@ -2798,6 +2810,147 @@ int tpe_plan_group_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int
     if (rc) return rc;
   }
   CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+namespace {
+
+// the state of a greedy batch over m configurations
+int ensure_batch(tpe_engine *h, tpe_plan *p, size_t m) {
+  if (!p->d_bt_rec) {
+    const size_t G = p->glay.groups.size();
+    // [hdr | ng[G] | rec[P][kBatchRec] | pact[G]]: cleared as one range
+    const size_t bytes = sizeof(BatchHdr) + G * 4 + ((G * 4) % 8 ? 4 : 0) +
+                         (size_t)p->P * kBatchRec * 8 + G;
+    CKH(hipMalloc(&p->d_bt_rec, bytes));
+    CKH(dalloc(&p->d_bt_idx, (size_t)kBatchMax));
+    CKH(dalloc(&p->d_bt_gain, (size_t)kBatchMax));
+  }
+  if (m > p->bt_cap) {
+    dfree(p->d_bt_ja); dfree(p->d_bt_score); dfree(p->d_bt_gact); dfree(p->d_bt_state);
+    dfree(p->d_bt_slot);
+    p->d_bt_ja = p->d_bt_score = nullptr;
+    p->d_bt_gact = p->d_bt_state = nullptr;
+    p->d_bt_slot = nullptr;
+    p->bt_cap = 0;
+    const size_t G = p->glay.groups.size();
+    CKH(dalloc(&p->d_bt_ja, G * m));
+    CKH(dalloc(&p->d_bt_score, m));
+    CKH(dalloc(&p->d_bt_gact, G * m));
+    CKH(dalloc(&p->d_bt_state, m));
+    CKH(hipMalloc(&p->d_bt_slot, ((m + kBtThreads - 1) / kBtThreads) * sizeof(BatchSlot)));
+    p->bt_cap = m;
+  }
+  return TPE_OK;
+}
+
+}  // namespace
+
+// A batch for parallel workers: k greedy picks over the configurations of the
+// last group score or draw, each joining the above side of its active groups
+// as a pending component (tpe_batch.hip).
+int tpe_plan_group_batch_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                                const uint8_t *eligible, int32_t k, int32_t *idx, double *gain,
+                                double *trace, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (k < 1 || k > kBatchMax)
+    return fail(h, TPE_E_INVALID, "group_batch_points: need 1 <= k <= 1024");
+  if (m < 0 || m > (int64_t)INT32_MAX || ld < m)
+    return fail(h, TPE_E_INVALID, "group_batch_points: need 0 <= m <= ld, m <= 2^31 - 1");
+  if (!idx || !vals)
+    return fail(h, TPE_E_INVALID, "group_batch_points: vals and idx must not be null");
+  if (!p->group_ok)
+    return fail(h, TPE_E_INVALID, "group_batch_points: no group fit (tpe_plan_group_fit first)");
+  if (m != p->bt_m)
+    return fail(h, TPE_E_INVALID,
+                "group_batch_points: m is not that of the last group score or draw of this fit");
+  if (m < k) return fail(h, TPE_E_INVALID, "group_batch_points: fewer than k selectable configurations");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  {
+    const int rc = ensure_batch(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  const size_t G = p->glay.groups.size();
+  if (!dev && trace && (size_t)k * (size_t)m > p->bt_trace_cap) {
+    dfree(p->d_bt_trace);
+    p->d_bt_trace = nullptr;
+    p->bt_trace_cap = 0;
+    CKH(dalloc(&p->d_bt_trace, (size_t)k * (size_t)m));
+    p->bt_trace_cap = (size_t)k * (size_t)m;
+  }
+  BatchArgs a{};
+  a.hps = p->d_hps;
+  a.dims = p->d_gdims;
+  a.groups = p->d_ggroups;
+  a.group_of_hp = p->d_ggroup_of_hp;
+  a.level_hps = p->d_level_hps;
+  a.cond_parent = p->d_cp;
+  a.cond_branch = p->d_cb;
+  a.n_hp = p->P;
+  a.n_group = (int32_t)G;
+  a.kcap = p->kcap;
+  a.side = p->d_gside;
+  a.optlog = p->d_goptlog;
+  a.n_opt = p->glay.n_opt;
+  a.info = p->d_info;
+  a.mmu = p->d_mmu;
+  a.m = m;
+  a.sides = p->d_gsides;
+  a.ja = p->d_bt_ja;
+  a.gact = p->d_bt_gact;
+  a.state = p->d_bt_state;
+  a.slot = static_cast<BatchSlot *>(p->d_bt_slot);
+  unsigned char *rec = static_cast<unsigned char *>(p->d_bt_rec);
+  const size_t ng_bytes = G * 4 + ((G * 4) % 8 ? 4 : 0);
+  const size_t rec_bytes = sizeof(BatchHdr) + ng_bytes + (size_t)p->P * kBatchRec * 8 + G;
+  a.hdr = reinterpret_cast<BatchHdr *>(rec);
+  a.ng = reinterpret_cast<int32_t *>(rec + sizeof(BatchHdr));
+  a.rec = reinterpret_cast<double *>(rec + sizeof(BatchHdr) + ng_bytes);
+  a.pact = rec + sizeof(BatchHdr) + ng_bytes + (size_t)p->P * kBatchRec * 8;
+  a.k = k;
+  CKH(hipMemsetAsync(rec, 0, rec_bytes, st));
+  if (dev) {
+    a.vals = vals;
+    a.ld = ld;
+    a.eligible = eligible;
+    a.score = trace ? trace : p->d_bt_score;
+    a.score_ld = trace ? ld : 0;
+    a.idx = idx;
+    a.gain = gain ? gain : p->d_bt_gain;
+  } else {
+    // (the scratch holds the last group score's m configurations: pt_cap >= m)
+    if (ld == m)
+      CKH(hipMemcpyAsync(p->d_pt_vals, vals, (size_t)m * p->P * 8, hipMemcpyHostToDevice, st));
+    else
+      CKH(hipMemcpy2DAsync(p->d_pt_vals, (size_t)m * 8, vals, (size_t)ld * 8, (size_t)m * 8,
+                           (size_t)p->P, hipMemcpyHostToDevice, st));
+    if (eligible)  // (k_batch_init turns the bytes into the state in place)
+      CKH(hipMemcpyAsync(p->d_bt_state, eligible, (size_t)m, hipMemcpyHostToDevice, st));
+    a.vals = p->d_pt_vals;
+    a.ld = m;
+    a.eligible = eligible ? p->d_bt_state : nullptr;
+    a.score = trace ? p->d_bt_trace : p->d_bt_score;
+    a.score_ld = trace ? m : 0;
+    a.idx = p->d_bt_idx;
+    a.gain = p->d_bt_gain;
+  }
+  CKH(launch_group_batch(a, st));
+  // a short batch: one 4-byte read-back (in device mode too, as the masked top-k's count)
+  BatchHdr hdr{};
+  CKH(hipMemcpyAsync(&hdr.is_short, &a.hdr->is_short, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (!dev) {
+    CKH(hipMemcpyAsync(idx, p->d_bt_idx, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (gain) CKH(hipMemcpyAsync(gain, p->d_bt_gain, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+    if (trace)
+      CKH(hipMemcpy2DAsync(trace, (size_t)ld * 8, p->d_bt_trace, (size_t)m * 8, (size_t)m * 8,
+                           (size_t)k, hipMemcpyDeviceToHost, st));
+  }
+  CKH(hipStreamSynchronize(st));
+  if (hdr.is_short)
+    return fail(h, TPE_E_INVALID, "group_batch_points: fewer than k selectable configurations");
   return TPE_OK;
 }
 

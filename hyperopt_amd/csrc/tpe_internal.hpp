@@ -917,4 +917,63 @@ hipError_t launch_topk_rest(const double *total, const uint8_t *eligible, int64_
 hipError_t launch_gather_points(const double *vals, int64_t ld, int32_t n_hp, const int32_t *idx,
                                 int32_t k, double *out, hipStream_t st);
 
+// A batch of k configurations picked greedily under the group models, every
+// pick joining the above side of its active groups as a pending component
+// (tpe_batch.hip; tpe_plan_group_batch_points)
+constexpr int kBatchMax = 1024;
+constexpr int kBtThreads = 256;
+// a configuration's rank in a round: (tier, topk_key of its score, ~index),
+// larger first.  tier 2: selectable, 1: selectable but equal to a taken
+// configuration, 0: not selectable
+struct BatchSlot {
+  uint64_t key;
+  uint32_t tier;
+  uint32_t nidx;
+};
+struct BatchHdr {
+  int32_t pick;      // the last round's pick
+  int32_t is_short;  // a round found no selectable configuration
+  int32_t pad[2];
+};
+constexpr int kBatchRec = 4;  // doubles of a pick's record per hp: its value, then
+                              //   continuous: mu, 1 / max(sigma, EPS) (with q: 1 / max(sqrt2
+                              //   sigma, EPS)), the log normaliser (with q: 0)
+struct BatchArgs {
+  const tpe_hp *hps;
+  const JointDim *dims;
+  const GroupDesc *groups;
+  const int32_t *group_of_hp;
+  const int32_t *level_hps;     // every hp id, parents first
+  const int32_t *cond_parent, *cond_branch;
+  int32_t n_hp, n_group;
+  int64_t kcap;
+  const JointSide *side;        // [G][2]
+  const double *optlog;         // [2][n_opt][3]
+  int64_t n_opt;
+  const MixInfo *info;          // the marginal fit: [2P]
+  const double *mmu;            // [2P][kcap] its sorted mus
+  // the configurations and the sides of their last group score
+  const double *vals;           // [P][ld]
+  int64_t m, ld;
+  const uint8_t *eligible;      // [m] or null
+  const double *sides;          // [G][2][m]
+  // the call's state
+  double *ja;                   // [G][m] J_g,above with the pending components
+  uint8_t *gact;                // [G][m] the group is active in the configuration
+  uint8_t *state;               // [m] bit 0 eligible, bit 1 taken, bit 2 equal to a taken one
+  double *score;                // [k][score_ld] each round's scores (score_ld 0: one row, reused)
+  int64_t score_ld;
+  BatchSlot *slot;              // [ceil(m / kBtThreads)] the blocks' best of a round
+  BatchHdr *hdr;
+  int32_t *ng;                  // [G] earlier picks that activated the group
+  uint8_t *pact;                // [G] the last pick activated the group
+  double *rec;                  // [P][kBatchRec] the last pick's record
+  int32_t k;
+  int32_t *idx;                 // [k] out
+  double *gain;                 // [k] out
+};
+// k_batch_init, then per round k_batch_round and k_batch_pick (hdr, ng, pact
+// zero before the call)
+hipError_t launch_group_batch(const BatchArgs &a, hipStream_t st);
+
 }  // namespace tpe

@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <cstddef>
 
-#include "tpe_internal.hpp"
+#include "tpe_device.hpp"
 
 namespace tpe {
 
@@ -41,12 +41,7 @@ struct TopkScratch {
   uint32_t nidx[kTopkMax];
 };
 
-__device__ __forceinline__ uint64_t topk_key(double x) {
-  if (x != x) return 0ull;
-  uint64_t b = (uint64_t)__double_as_longlong(x);
-  if ((b << 1) == 0ull) b = 0ull;  // -0.0 ranks with +0.0
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// (topk_key: tpe_device.hpp)
 __device__ __forceinline__ uint32_t topk_digit(uint64_t key, uint32_t nidx, int pass) {
   return pass < 8 ? (uint32_t)(key >> (56 - 8 * pass)) & 255u
                   : (nidx >> (24 - 8 * (pass - 8))) & 255u;

@@ -669,10 +669,50 @@ def _joint_buffers(st, engine, P, n):
     return b[2:]
 
 
+PENDING_RERUNS = 3          # suggest_joint(batch='pending'): reruns before the full host mask
+
+
+def _pending_batch(plan, k, bufs, shape, vals, eligible, hv, ha, skip_seen):
+    """suggest_joint's ``batch='pending'`` selection over the draw in
+    ``bufs``: the columns [P, k] of the greedy picks.  ``skip_seen`` means the
+    greedy selection over the configurations that are not history rows: the
+    picks of a run are checked against the history on the host, the ones that
+    are history rows masked and the selection rerun -- a round's argmax over a
+    superset that lies in the subset is the subset's argmax, so a run without
+    a history row among its picks is the selection over the subset -- and
+    after ``PENDING_RERUNS`` reruns every history row of the draw is masked."""
+    d_vals, d_mask, d_idx, d_cols = bufs
+    P, n = shape
+    mask = None if eligible is None else np.array(eligible, dtype=bool)
+    for run in range(PENDING_RERUNS + 2):
+        if run == PENDING_RERUNS + 1:
+            # the full host mask: every configuration of the draw that is a history row
+            if vals is None:
+                vals = d_vals.download(np.empty((P, n)))
+            mask = (np.ones(n, dtype=bool) if mask is None else mask) & \
+                ~seen_in_history(vals, ~np.isnan(vals), hv, ha)
+        if mask is not None:
+            d_mask.upload(mask.astype(np.uint8))
+        plan.group_batch_points_device(d_vals.ptr, n, n, k, d_idx.ptr,
+                                       eligible_ptr=0 if mask is None else d_mask.ptr)
+        plan.gather_points(d_vals.ptr, d_idx.ptr, k=k, ld=n, out=d_cols.ptr)
+        cols = d_cols.download(np.empty((P, k)))
+        if not skip_seen:
+            return cols
+        seen = seen_in_history(cols, ~np.isnan(cols), hv, ha)
+        if not seen.any():
+            return cols
+        picks = d_idx.download(np.empty(k, dtype=np.int32))
+        if mask is None:
+            mask = np.ones(n, dtype=bool)
+        mask[picks[seen]] = False
+    raise AssertionError('a history row was picked under the full mask')
+
+
 def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, feasible=None,
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
-                  startup_stream='numpy', engine=None, multivariate=False):
+                  startup_stream='numpy', engine=None, multivariate=False, batch='topk'):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -700,8 +740,29 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
 
     ``multivariate``: the draw and its ranking are
     ``sample_configs``' with that argument (True or 'groups'); everything
-    else is as above."""
+    else is as above.
+
+    ``batch='pending'`` (with ``multivariate='groups'``) spreads a
+    batch for parallel workers: the k best of one draw are near-duplicates of
+    each other, so the picks are made greedily instead -- each pick counts as
+    a bad trial that is out for evaluation (the constant liar), joins the
+    above model of every group it activates as a pending component, and the
+    draw is rescored before the next pick (tpe_plan_group_batch_points).  The
+    first pick is ``batch='topk'``'s first.  Configurations equal to a taken
+    one rank below all others instead of being dropped, and with
+    ``skip_seen`` the selection runs over the configurations that are not
+    history rows; ValueError when fewer than k selectable ones remain, for
+    k > 1024, for any other ``multivariate`` (the marginal terms of False and
+    True hold no per-configuration above density a pending component could
+    join; without conditions 'groups' is True's model bit for bit) and for an
+    unknown ``batch``."""
     multivariate = _mode(multivariate)
+    if batch not in ('topk', 'pending'):
+        raise ValueError("batch must be 'topk' or 'pending', got %r" % (batch,))
+    if batch == 'pending' and multivariate != 'groups':
+        raise ValueError("batch='pending' needs multivariate='groups': only the group models "
+                         "hold an above density per configuration that a pending trial can "
+                         "join, got multivariate=%r" % (multivariate,))
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -735,7 +796,10 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         hv, ha = hist.vals[:, :hist.n], hist.active[:, :hist.n]
         chosen = None
         kk = min(n_el, TOPK_MAX, max(4 * k, 64))
-        if k <= kk:
+        if batch == 'pending':
+            chosen = _pending_batch(plan, k, (d_vals, d_mask, d_idx, d_cols), (P, n), vals,
+                                    eligible, hv, ha, skip_seen)
+        elif k <= kk:
             plan.topk_points(d_total.ptr, kk, eligible=None if eligible is None else d_mask.ptr,
                              m=n, out=d_idx.ptr)
             plan.gather_points(d_vals.ptr, d_idx.ptr, k=kk, ld=n, out=d_cols.ptr)

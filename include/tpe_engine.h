@@ -468,6 +468,55 @@ int tpe_plan_group_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int
                                  double *joint, uint8_t *active, int32_t on_device,
                                  void *stream);
 
+/* A batch for parallel workers: k greedy picks with a pending-trial penalty
+ * (the constant liar inside one call).  The input is the m configurations
+ * vals[n_hp][ld] of the plan's last tpe_plan_group_score_points or
+ * tpe_plan_group_sample_points call -- the same values, the same m -- whose
+ * per-group sides J_g,below(c), J_g,above(c) the plan still holds.
+ * With W_g = S_g,above + prior_weight (the unnormalised mass of group g's
+ * above side) and Ja_g^(0) = J_g,above, round t = 0..k-1 scores every
+ * configuration, score_t(c) = the float64 sum, in ascending group order from
+ * +0.0, of J_g,below(c) - Ja_g^(t)(c) over the groups active in c (score_0 is
+ * the call's total, bit for bit), and picks the first selectable
+ * configuration in tpe_plan_topk_points' order (highest score, ties to the
+ * lower index, -0.0 == +0.0, NaN last) with one tier above it: a
+ * configuration is selectable when eligible[c] != 0 (NULL: all) and it has
+ * not been taken; it is a duplicate when its activity and active values equal
+ * a taken one's (the sign of zero ignored), and every non-duplicate ranks
+ * above every duplicate.  After a pick p every group g active in p gets one
+ * pending component of unnormalised weight 1 (the linear-forgetting weight of
+ * a newest row): for each c with g active
+ *   Ja_g^(t+1)(c) = logaddexp(Ja_g^(t)(c) + log(W_g + n_g),
+ *                             sum_{d in g} log kappa_d(c_d; p_d))
+ *                   - log(W_g + n_g + 1),
+ * n_g the earlier picks that activated g; groups inactive in p or in c keep
+ * their value.  kappa_d is the kernel a refit would give the pick's value
+ * appended to hp d's above observations with every fitted component frozen.
+ * Continuous hp: mu = the transformed value; in the hp's sorted above mixture
+ * (tpe_plan_get_mixture, side 1, K components with the prior) the left
+ * neighbour is the last mu_k <= mu and the right one the first mu_k > mu
+ * (fitted components only, never earlier picks), sigma = the larger of the
+ * two gaps (one-sided at an end) clipped to [prior_sigma / min(100, 2 + K),
+ * prior_sigma], and prior_sigma / 2 when the prior is alone; the log kernel is
+ * the group model's form (the q = None log-density, or log(cdf(ub) - cdf(lb))
+ * with q; no truncation normaliser).  Categorical hp with picked option o:
+ * kappa(c) = ((c == o) + a pi[c]) / (1 + a) with the above side's a.
+ * idx[k]: the picks; gain[k] (may be NULL): gain[t] = score_t(idx[t]);
+ * trace[k][ld] (may be NULL, for tests): trace[t][c] = score_t(c) for every
+ * configuration, selectable or not.  1 <= k <= 1024, m <= 2^31 - 1.
+ * TPE_E_INVALID: no group fit, an m other than the last group score's or
+ * draw's since that fit, k or m out of range, ld < m, null vals / idx, or
+ * fewer than k selectable configurations -- a short batch, found after the
+ * rounds: idx[t] = -1 from the first round without one.  on_device as above,
+ * except that the call ends with one 4-byte read-back for the short batch.
+ * The history, the fit, the sides and the last suggest's results are not
+ * disturbed.  The same picks for every launch shape: all comparisons are on
+ * integers, there is no floating-point atomic.                             */
+int tpe_plan_group_batch_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                                const uint8_t *eligible, int32_t k, int32_t *idx,
+                                double *gain, double *trace, int32_t on_device,
+                                void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
