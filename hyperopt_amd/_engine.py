@@ -51,9 +51,11 @@ EXPORTS = (
     'tpe_plan_group_info', 'tpe_plan_group_fit', 'tpe_plan_group_get_mixture',
     'tpe_plan_group_score_points', 'tpe_plan_group_sides', 'tpe_plan_group_sample_points',
     'tpe_plan_group_batch_points',
+    'tpe_plan_set_objectives', 'tpe_plan_pareto_get', 'tpe_plan_pareto_shape',
 )
 
 BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
+MAX_OBJ = 8                 # include/tpe_engine.h TPE_MAX_OBJ
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
 # give byte-identical suggests (the large-draw value-bucketing block)
@@ -182,6 +184,9 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_group_batch_points': (C.c_int, [vp, vp, i64, i64, vp, i32, vp, vp, vp, i32,
                                                       vp]),
             'tpe_plan_gather_points': (C.c_int, [vp, vp, i64, vp, i32, vp, i32, vp]),
+            'tpe_plan_set_objectives': (C.c_int, [vp, vp, i32, i64, i64, i64, i32, vp]),
+            'tpe_plan_pareto_get': (C.c_int, [vp, vp, vp, vp, i64]),
+            'tpe_plan_pareto_shape': (C.c_int, [vp, i64, i32, i64, C.POINTER(i64)]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -517,6 +522,64 @@ class Plan(object):
             e.check(e.lib.tpe_plan_set_history(self.p, losses_ptr, vals_ptr, active_ptr, int(n),
                                                1, stream))
         self.n = int(n)
+
+    # ---- multi-objective TPE: the loss column from a Pareto ranking
+    def set_objectives(self, Y, n=None, obj0=0, stream=None):
+        """Rank the history by Pareto dominance (tpe_plan_set_objectives):
+        ``Y`` float64 [M, ld] C-contiguous, objective m of row r at
+        ``Y[m, r]``; rows [obj0, n) are copied (the rows below are the last
+        call's), all n rows are counted and the loss column of rows [0, n)
+        becomes the surrogate loss.  ``n`` (default ld) must be the history
+        length."""
+        e = self.engine
+        Y = np.asarray(Y)
+        if Y.ndim != 2 or Y.dtype != np.float64 or not Y.flags.c_contiguous:
+            raise ValueError('objectives must be a C-contiguous float64 [M, ld] array')
+        m, ld = Y.shape
+        n = ld if n is None else int(n)
+        obj0 = int(obj0)
+        if n > ld or not 0 <= obj0 <= n:
+            raise ValueError('need 0 <= obj0 <= n <= ld')
+        # (the source rows start at obj0: the leading dimension stays ld)
+        ptr = (Y.ctypes.data + 8 * obj0) if ld > 0 else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_set_objectives(self.p, ptr, int(m), n, int(ld), obj0, 0,
+                                                  stream))
+
+    def set_objectives_device(self, y_ptr, n_obj, n, ld, obj0=0, stream=None):
+        """The same from device memory: ``y_ptr`` points at row obj0 of
+        objective 0, objective m of row r at y_ptr[m * ld + (r - obj0)].
+        Stream-ordered, no host synchronisation."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_set_objectives(self.p, y_ptr, int(n_obj), int(n), int(ld),
+                                                  int(obj0), 1, stream))
+
+    def pareto_get(self, n):
+        """(dominated_by int32[n], dominates int32[n], surrogate float64[n])
+        of the last ``set_objectives`` (tpe_plan_pareto_get)."""
+        e = self.engine
+        n = int(n)
+        by = np.empty(max(n, 0), dtype=np.int32)
+        of = np.empty(max(n, 0), dtype=np.int32)
+        s = np.empty(max(n, 0))
+        with e.lock:
+            e.check(e.lib.tpe_plan_pareto_get(self.p, by.ctypes.data, of.ctypes.data,
+                                              s.ctypes.data, n))
+        return by, of, s
+
+    def pareto_shape(self, n, n_obj, force_splits=-1):
+        """(rows per tile, TPE_MAX_OBJ, j-splits, tiles) of the ranking launch
+        for ``n`` rows of ``n_obj`` objectives (tpe_plan_pareto_shape).
+        ``force_splits`` > 0 makes this plan's later ``set_objectives`` calls
+        take that many j-splits (tests), 0 restores the default, -1 leaves the
+        setting."""
+        e = self.engine
+        out = (C.c_int64 * 4)()
+        with e.lock:
+            e.check(e.lib.tpe_plan_pareto_shape(self.p, int(n), int(n_obj), int(force_splits),
+                                                out))
+        return tuple(int(v) for v in out)
 
     def fit(self, gamma=0.25, prior_weight=1.0, lf=25, gamma_cap=25, stream=None):
         e = self.engine

@@ -18,6 +18,7 @@
 #include "tpe_group_plan.hpp"
 #include "tpe_internal.hpp"
 #include "tpe_level_plan.hpp"
+#include "tpe_pareto_plan.hpp"
 #include "tpe_switches.hpp"
 
 using namespace tpe;
@@ -221,6 +222,14 @@ struct tpe_plan : PlanShape {
   int64_t an_cap = 0, an_nsug = 0;
   bool an_ready = false;   // keys / idx / T allocated
   bool an_order = false;   // d_an_hporder holds the host's order (tpe_plan_set_anneal_order)
+  // multi-objective TPE (tpe_plan_set_objectives, tpe_pareto.hip): allocated
+  // by its first call
+  double *d_obj = nullptr;      // [TPE_MAX_OBJ][ncap] the objective matrix
+  int32_t *d_pcount = nullptr;  // [2][ncap] dominated_by, dominates
+  int32_t obj_M = 0;            // objectives of the rows held (0: none)
+  int64_t obj_n = 0;            // ... and their number
+  int64_t pareto_n = -1;        // rows the counts are of (tpe_plan_pareto_get)
+  int64_t pareto_force = 0;     // j-splits forced by tpe_plan_pareto_shape (0: the plan's)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -291,7 +300,7 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_gcsig, p->d_gtab, p->d_goptlog, p->d_gpick, p->d_goptcdf, p->d_gdraw,
                   p->d_gsides, p->d_gjoint, p->d_bt_ja, p->d_bt_score, p->d_bt_gain,
                   p->d_bt_trace, p->d_bt_gact, p->d_bt_state, p->d_bt_slot, p->d_bt_rec,
-                  p->d_bt_idx};
+                  p->d_bt_idx, p->d_obj, p->d_pcount};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -1512,6 +1521,102 @@ int tpe_plan_update_history(tpe_plan_t p, int64_t n, int64_t row0, int64_t n_row
   if (!on_device) CKH(hipStreamSynchronize(st));
   return TPE_OK;
 }
+
+// ---- multi-objective TPE: the loss column from a Pareto ranking
+// Order against the deferred history patch: the patch (if any) is written
+// first, on the same stream, so the surrogate column is the last writer of
+// losses [0, n).
+int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_t n, int64_t ld,
+                            int64_t obj0, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (n_obj < 1 || n_obj > TPE_MAX_OBJ)
+    return fail(h, TPE_E_INVALID, "set_objectives: need 1 <= n_obj <= TPE_MAX_OBJ");
+  if (n != p->n) return fail(h, TPE_E_INVALID, "set_objectives: n is not the history length");
+  if (!Y) return fail(h, TPE_E_INVALID, "set_objectives: Y must not be null");
+  if (obj0 < 0 || obj0 > n) return fail(h, TPE_E_INVALID, "set_objectives: need 0 <= obj0 <= n");
+  if (ld < n - obj0) return fail(h, TPE_E_INVALID, "set_objectives: ld < n - obj0");
+  if (obj0 > 0 && (p->obj_M != n_obj || obj0 > p->obj_n))
+    return fail(h, TPE_E_INVALID,
+                "set_objectives: the rows below obj0 are not on the device with this n_obj");
+  if (n == 0) {  // an empty history: nothing to rank
+    p->obj_M = n_obj;
+    p->obj_n = 0;
+    p->pareto_n = 0;
+    return TPE_OK;
+  }
+  const ParetoPlan pp = pareto_plan(n, n_obj, p->pareto_force);
+  if (!pp.ok) return fail(h, TPE_E_INVALID, "set_objectives: need (n + 1)^2 < 2^53");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  if (!p->d_obj) {
+    CKH(dalloc(&p->d_obj, (size_t)TPE_MAX_OBJ * (size_t)p->ncap));
+    CKH(dalloc(&p->d_pcount, 2 * (size_t)p->ncap));
+  }
+  {
+    const int rc = flush_patch(h, p, st);
+    if (rc) return rc;
+  }
+  p->obj_M = 0;  // (not a consistent matrix until the copy is enqueued)
+  if (obj0 < n)
+    CKH(hipMemcpy2DAsync(p->d_obj + obj0, (size_t)p->ncap * 8, Y, (size_t)ld * 8,
+                         (size_t)(n - obj0) * 8, (size_t)n_obj,
+                         on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  p->obj_M = n_obj;
+  p->obj_n = n;
+  int32_t *by = p->d_pcount, *of = p->d_pcount + p->ncap;
+  p->pareto_n = -1;
+  CKH(hipMemsetAsync(p->d_pcount, 0, 2 * (size_t)p->ncap * sizeof(int32_t), st));
+  CKH(launch_pareto_count(p->d_obj, p->ncap, n, n_obj, pp.per_split, pp.splits, by, of, st));
+  CKH(launch_pareto_loss(p->d_obj, p->ncap, n, n_obj, by, of, p->d_losses, st));
+  p->pareto_n = n;
+  // a new loss column: nothing fitted on the old one stands
+  p->last_nb = -1;
+  p->tab_built = false;
+  p->joint_ok = false;
+  p->group_ok = false;
+  if (!on_device) CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+int tpe_plan_pareto_get(tpe_plan_t p, int32_t *dominated_by, int32_t *dominates, double *loss,
+                        int64_t n) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->pareto_n < 0 || n != p->pareto_n)
+    return fail(h, TPE_E_INVALID, "pareto_get: n is not that of the last tpe_plan_set_objectives");
+  if (n == 0) return TPE_OK;
+  CKH(hipSetDevice(h->device));
+  {
+    const int rc = flush_patch(h, p, h->stream);
+    if (rc) return rc;
+  }
+  CKH(hipDeviceSynchronize());
+  if (dominated_by)
+    CKH(hipMemcpy(dominated_by, p->d_pcount, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (dominates)
+    CKH(hipMemcpy(dominates, p->d_pcount + p->ncap, (size_t)n * sizeof(int32_t),
+                  hipMemcpyDeviceToHost));
+  if (loss) CKH(hipMemcpy(loss, p->d_losses, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+int tpe_plan_pareto_shape(tpe_plan_t p, int64_t n, int32_t n_obj, int64_t force_splits,
+                          int64_t *out) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!out) return fail(h, TPE_E_INVALID, "pareto_shape: out must not be null");
+  const int64_t force = force_splits < 0 ? p->pareto_force : force_splits;
+  const ParetoPlan pp = pareto_plan(n, n_obj, force);
+  if (!pp.ok) return fail(h, TPE_E_INVALID, "pareto_shape: (n, n_obj) out of range");
+  p->pareto_force = force;
+  out[0] = kParetoTile;
+  out[1] = TPE_MAX_OBJ;
+  out[2] = pp.splits;
+  out[3] = pp.tiles;
+  return TPE_OK;
+}
+static_assert(kParetoMaxObj == TPE_MAX_OBJ, "tpe_pareto_plan.hpp's constant is the header's");
 
 int tpe_plan_fit(tpe_plan_t p, double gamma, int32_t gamma_cap, double prior_weight, int32_t lf,
                  void *stream) {

@@ -976,4 +976,17 @@ struct BatchArgs {
 // zero before the call)
 hipError_t launch_group_batch(const BatchArgs &a, hipStream_t st);
 
+// Pareto ranking of an objective matrix Y[M][ld] (tpe_pareto.hip;
+// tpe_plan_set_objectives).  launch_pareto_count: the all-pairs
+// dominance counts of rows [0, n), added to dominated_by / dominates (zero
+// before the call) by a grid of ceil(n / kParetoTile) x splits blocks, each
+// walking per_split j tiles (tpe_pareto_plan.hpp).  launch_pareto_loss: the
+// surrogate loss of every row from its counts, +inf for a pending row.
+hipError_t launch_pareto_count(const double *Y, int64_t ld, int64_t n, int32_t M,
+                               int64_t per_split, int64_t splits, int32_t *dominated_by,
+                               int32_t *dominates, hipStream_t st);
+hipError_t launch_pareto_loss(const double *Y, int64_t ld, int64_t n, int32_t M,
+                              const int32_t *dominated_by, const int32_t *dominates,
+                              double *losses, hipStream_t st);
+
 }  // namespace tpe

@@ -18,6 +18,11 @@ a trial when its misc idxs entry equals the trial's (from_tid-aware) tid.
 A history that is a plain extension (new integer tids in increasing order,
 no from_tid) takes the incremental path; anything else rebuilds the columns
 from cached per-document rows.
+
+With ``objectives=M`` (multi-objective TPE) an objective store ``Y[M][cap]``
+is kept beside the losses, from ``result['objectives']`` of the ok trials, and
+``push`` has the device rank the history by Pareto dominance
+(``tpe_plan_set_objectives``) instead of sending the losses.
 """
 from __future__ import annotations
 
@@ -27,9 +32,43 @@ import weakref
 
 import numpy as np
 
+from .status import STATUS_OK
+
+MAX_OBJ = 8                     # include/tpe_engine.h TPE_MAX_OBJ
+
+
 def _loss_of(domain, doc):
     v = domain.loss(doc['result'], doc['spec'])
     return math.inf if v is None else float(v)
+
+
+def check_objectives(objectives):
+    """``objectives=`` checked: None (the scalar loss) or the number M >= 1 of
+    objectives every ok trial reports in ``result['objectives']``."""
+    if objectives is None:
+        return None
+    if isinstance(objectives, bool) or not isinstance(objectives, numbers.Integral) \
+            or not 1 <= objectives <= MAX_OBJ:
+        raise ValueError('objectives must be None or an int in [1, %d], got %r'
+                         % (MAX_OBJ, objectives))
+    return int(objectives)
+
+
+def _objectives_of(doc, M, tid):
+    """The M objectives of a row's document: those of an ok trial, NaN (a
+    pending row) for any other."""
+    res = doc['result']
+    if res.get('status') != STATUS_OK:
+        return np.full(M, np.nan)
+    y = res.get('objectives')
+    try:
+        ok = y is not None and len(y) == M
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("trial %r: result['objectives'] must be a sequence of %d numbers, got %r"
+                         % (tid, M, y))
+    return np.array([float(v) for v in y])
 
 
 def _is_int_tid(t):
@@ -45,6 +84,8 @@ class TrialHistory(object):
         self.labels = list(domain.space.labels)
         self.P = len(self.labels)
         self._cache = {}        # id(doc) -> (doc, tid, vals row, active row)
+        self.M = None           # objectives of the last sync (None: the scalar loss)
+        self.Y = None           # [M][cap] objective store beside losses (NaN: pending)
         self._alloc(64)
         self._forget()
 
@@ -66,6 +107,10 @@ class TrialHistory(object):
         self.losses[:self.n] = l[:self.n]
         self.vals[:, :self.n] = v[:, :self.n]
         self.active[:, :self.n] = a[:, :self.n]
+        if self.Y is not None:
+            y = self.Y
+            self.Y = np.full((y.shape[0], cap), np.nan)
+            self.Y[:, :self.n] = y[:, :self.n]
 
     def _forget(self):
         """Drop all rows: the next sync rebuilds from the documents."""
@@ -82,6 +127,10 @@ class TrialHistory(object):
         self._seen = 0          # visible documents consumed
         self._vals_dirty = 0    # rows >= this differ from the device copy
         self._loss_dirty = 0
+        self._obj_ok = False    # Y holds the objectives of every row not in _touched
+        self._touched = set()   # rows whose document was (re)read since Y was
+        self._obj_dirty = 0     # rows of Y >= this differ from the device copy
+        self._dev_mode = None   # what the device loss column holds: None the losses, M a ranking
         self._dev = None        # weakref to the plan holding the device copy
         self._plain = True      # rows == visible documents, integer tids ascending
 
@@ -119,10 +168,16 @@ class TrialHistory(object):
             self._pending.add(r)
         else:
             self._pending.discard(r)
+        self._touched.add(r)
 
     # -- sync ----------------------------------------------------------------
-    def sync(self, trials):
-        """Bring the columns up to date with ``trials.trials``."""
+    def sync(self, trials, objectives=None):
+        """Bring the columns up to date with ``trials.trials``.  ``objectives``
+        = M: also the objective store ``Y[M][cap]``, from every ok trial's
+        ``result['objectives']`` (ValueError naming the tid where an ok trial
+        has none, or not M of them); ``push`` then ranks the device history by
+        Pareto dominance instead of by the loss."""
+        objectives = check_objectives(objectives)
         view = trials.trials
         store = getattr(trials, '_store', None)
         journal = store.journal if store is not None else None
@@ -148,7 +203,29 @@ class TrialHistory(object):
         self._jgen = jgen
         self._jpos = jlen if fresh else 0
         self._seen = len(view)
+        self._sync_objectives(objectives)
         return self
+
+    def _sync_objectives(self, M):
+        """The objective store after the columns: the rows read since the last
+        sync when that one kept a store of M objectives too, every row
+        otherwise (a rebuild, a first call, another M, a call without
+        objectives in between)."""
+        self.M = M
+        if M is None:
+            self._obj_ok = False
+            self._touched.clear()
+            return
+        full = not self._obj_ok or self.Y is None or self.Y.shape != (M, self.cap)
+        if full:
+            self.Y = np.full((M, self.cap), np.nan)
+        rows = range(self.n) if full else sorted(r for r in self._touched if r < self.n)
+        self._obj_ok = False        # (until every row is read: an error leaves a full re-read)
+        for r in rows:
+            self.Y[:, r] = _objectives_of(self.docs[r], M, self.tids[r])
+        self._obj_dirty = 0 if full else min([self._obj_dirty] + list(rows))
+        self._touched.clear()
+        self._obj_ok = True
 
     def _incremental(self, view, changed):
         """Apply changed and appended documents; False = needs a rebuild."""
@@ -195,6 +272,7 @@ class TrialHistory(object):
                 self.losses[r] = loss
                 self._pending.discard(r)
                 self._loss_dirty = min(self._loss_dirty, r)
+                self._touched.add(r)
         new = view[self._seen:]
         self._grow(self.n + len(new))
         last = self.tids[-1] if self.tids else None
@@ -261,11 +339,25 @@ class TrialHistory(object):
         ``plan``'s device history."""
         if self._dev is None or self._dev() is not plan or \
                 getattr(plan, '_history_owner', None) is not self:
-            self._vals_dirty = self._loss_dirty = 0
+            self._vals_dirty = self._loss_dirty = self._obj_dirty = 0
+            self._dev_mode = None
         r0 = min(self._vals_dirty, self.n)
-        l0 = min(self._loss_dirty, r0, self.n)
-        plan.update_history(self.n, r0, self.vals, self.active, self.cap, l0, self.losses)
+        if self.M is None:
+            if self._dev_mode is not None:
+                self._loss_dirty = 0        # the column holds a ranking: every loss goes again
+            l0 = min(self._loss_dirty, r0, self.n)
+            plan.update_history(self.n, r0, self.vals, self.active, self.cap, l0, self.losses)
+            self._loss_dirty = self.n
+        else:
+            # no loss travels: set_objectives writes the whole column after the
+            # rows (and after a deferred patch of them, tpe_engine.h)
+            plan.update_history(self.n, r0, self.vals, self.active, self.cap, self.n,
+                                self.losses)
+            o0 = min(self._obj_dirty, self.n) if self._dev_mode == self.M else 0
+            plan.set_objectives(self.Y, n=self.n, obj0=o0)
+            self._obj_dirty = self.n
+        self._dev_mode = self.M
         plan._history_owner = self
         self._dev = weakref.ref(plan)
-        self._vals_dirty = self._loss_dirty = self.n
+        self._vals_dirty = self.n
         return self

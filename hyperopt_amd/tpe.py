@@ -37,7 +37,7 @@ import numpy as np
 
 from . import _engine as E
 from . import rand, rstream
-from .history import TrialHistory
+from .history import TrialHistory, check_objectives
 
 logger = logging.getLogger(__name__)
 
@@ -149,13 +149,24 @@ def suggest(new_ids, domain, trials, seed,
             n_EI_candidates=_default_n_EI_candidates,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
-            rng_stream='philox', startup_stream='numpy', engine=None):
+            rng_stream='philox', startup_stream='numpy', engine=None, objectives=None):
     """hyperopt/tpe.py:804-897 on the GPU, one document per id in
     ``new_ids``.  ``linear_forgetting`` is accepted and, as in the reference
     (tpe.py:809), not used: LF is fixed at 25.  The first ``n_startup_jobs``
     trials come from ``rand.suggest`` with ``startup_stream``: 'numpy' (the
     reference's RandomState stream, default) or 'philox' (device prior
-    draws, tpe_plan_sample_prior)."""
+    draws, tpe_plan_sample_prior).
+
+    ``objectives=M`` (multi-objective TPE): the model reads
+    ``result['objectives']``, a sequence of M numbers to minimise, from every
+    ok trial -- an ok trial without it, or with another length, is a
+    ValueError naming the tid -- and the good / bad split ranks the history by
+    Pareto dominance (``pareto_ranks``) instead of by ``result['loss']``,
+    which ``fmin`` still needs for its own bookkeeping.  Everything behind
+    the split is unchanged; with M = 1 and ``objectives = [loss]`` the
+    suggestions are those of ``objectives=None``.  Calls with different
+    ``objectives`` may alternate on one domain and one trials object."""
+    objectives = check_objectives(objectives)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -164,7 +175,7 @@ def suggest(new_ids, domain, trials, seed,
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials)
+        hist = st.history(domain, trials).sync(trials, objectives)
         startup = hist.n < n_startup_jobs
     if startup:
         # the reference's RandomState prior stream (numpy), or device prior
@@ -172,6 +183,8 @@ def suggest(new_ids, domain, trials, seed,
         return rand.suggest(new_ids, domain, trials, seed, rng_stream=startup_stream)
     with st.lock:
         engine = engine or E.default_engine()
+        if hist.M != objectives:    # (another thread's call in between)
+            hist.sync(trials, objectives)
         plan = st.plan_for(domain, hist.n, engine)
         hist.push(plan)
         seeds = batch_seeds(seed, len(new_ids))
@@ -363,7 +376,8 @@ def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate
 
 
 def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
-                  gamma=_default_gamma, engine=None, return_terms=False, multivariate=False):
+                  gamma=_default_gamma, engine=None, return_terms=False, multivariate=False,
+                  objectives=None):
     """What the fitted TPE model thinks of configurations the caller holds.
 
     The history of ``trials`` is synced, pushed and fitted as ``suggest``
@@ -392,14 +406,18 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     too: ``EI(c) = the sum of joint_g(c) over the groups active in c``.  With
     ``return_terms`` the result is (EI, terms, active, joint[G, M]) with
     ``joint`` in ``hp_groups`` order (0.0 where a group is inactive); all
-    terms are 0.0.  Any other value of ``multivariate`` is a ValueError."""
+    terms are 0.0.  Any other value of ``multivariate`` is a ValueError.
+
+    ``objectives=M``: the model is fitted on the Pareto ranking of the
+    trials' ``result['objectives']`` (``suggest``)."""
     multivariate = _mode(multivariate)
+    objectives = check_objectives(objectives)
     cs = domain.space
     as_dicts = not isinstance(configs, np.ndarray)
     vals, present = config_columns(cs, configs)
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials)
+        hist = st.history(domain, trials).sync(trials, objectives)
         if hist.n == 0:
             raise ValueError('score_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
@@ -491,7 +509,8 @@ def rank_pool(total, eligible, k):
 def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
                       prior_weight=_default_prior_weight,
                       n_startup_jobs=_default_n_startup_jobs,
-                      gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False):
+                      gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False,
+                      objectives=None):
     """``algo=`` for a constrained or discrete search: the next trials are the
     ``len(new_ids)`` configurations of ``pool`` the fitted model scores
     highest (``score_configs``' EI), distinct, ties to the lower pool index,
@@ -504,8 +523,10 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     .choice(M, k, replace=False)`` over the whole pool.  ValueError when fewer
     than ``len(new_ids)`` eligible configurations remain.  ``multivariate``
     (True or 'groups'): the pool is ranked by ``score_configs`` with that
-    argument."""
+    argument.  ``objectives=M``: the model is fitted on the Pareto ranking of
+    the trials' ``result['objectives']`` (``suggest``)."""
     multivariate = _mode(multivariate)
+    objectives = check_objectives(objectives)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -516,7 +537,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     k = len(new_ids)
     with st.lock:
         pl = _pool_for(st, cs, pool)
-        hist = st.history(domain, trials).sync(trials)
+        hist = st.history(domain, trials).sync(trials, objectives)
         if hist.n < n_startup_jobs:
             if pl.m < k:
                 raise ValueError('the pool holds %d configurations, %d asked for' % (pl.m, k))
@@ -545,7 +566,7 @@ STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
 
 def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
                    gamma=_default_gamma, engine=None, begin=0, as_dicts=False,
-                   multivariate=False):
+                   multivariate=False, objectives=None):
     """``n`` whole configurations drawn from the fitted model's *below*
     mixtures, each with its joint EI (``score_configs``' total of it).
 
@@ -567,12 +588,14 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     the configuration activates picks a component of its own below model and
     draws the group's hps from it, parents first; the EI is
     ``score_configs(..., multivariate='groups')``'s
-    (tpe_plan_group_sample_points)."""
+    (tpe_plan_group_sample_points).  ``objectives=M``: the model is fitted on
+    the Pareto ranking of the trials' ``result['objectives']`` (``suggest``)."""
     multivariate = _mode(multivariate)
+    objectives = check_objectives(objectives)
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials)
+        hist = st.history(domain, trials).sync(trials, objectives)
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
@@ -712,7 +735,8 @@ def _pending_batch(plan, k, bufs, shape, vals, eligible, hv, ha, skip_seen):
 def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, feasible=None,
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
-                  startup_stream='numpy', engine=None, multivariate=False, batch='topk'):
+                  startup_stream='numpy', engine=None, multivariate=False, batch='topk',
+                  objectives=None):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -755,8 +779,12 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     k > 1024, for any other ``multivariate`` (the marginal terms of False and
     True hold no per-configuration above density a pending component could
     join; without conditions 'groups' is True's model bit for bit) and for an
-    unknown ``batch``."""
+    unknown ``batch``.
+
+    ``objectives=M``: the model is fitted on the Pareto ranking of the
+    trials' ``result['objectives']`` (``suggest``)."""
     multivariate = _mode(multivariate)
+    objectives = check_objectives(objectives)
     if batch not in ('topk', 'pending'):
         raise ValueError("batch must be 'topk' or 'pending', got %r" % (batch,))
     if batch == 'pending' and multivariate != 'groups':
@@ -771,7 +799,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     k = len(new_ids)
     n = int(n_configs)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials)
+        hist = st.history(domain, trials).sync(trials, objectives)
         startup = hist.n < n_startup_jobs
     if startup:
         if feasible is None:
@@ -781,6 +809,8 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
     P = len(cs.labels)
     with st.lock:
+        if hist.M != objectives:    # (another thread's call in between)
+            hist.sync(trials, objectives)
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
         draw = (plan.group_sample_points_device if multivariate == 'groups' else
@@ -818,6 +848,43 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
             chosen = vals[:, joint_select(total, eligible, vals, hv, ha, k, skip_seen)]
     cfgs = columns_to_configs(cs, chosen, ~np.isnan(chosen))
     return [_new_doc(domain, trials, cs, i, c) for i, c in zip(new_ids, cfgs)]
+
+
+# --------------------------------------------------------------------------
+# multi-objective TPE: the Pareto ranking the split reads
+# --------------------------------------------------------------------------
+def _pareto(domain, trials, objectives, engine):
+    """(docs, tids, dominated_by, dominates, surrogate) of the synced history,
+    ranked on the device."""
+    objectives = check_objectives(objectives)
+    if objectives is None:
+        raise ValueError('the Pareto ranking needs objectives=M')
+    st = _state(domain)
+    with st.lock:
+        hist = st.history(domain, trials).sync(trials, objectives)
+        if hist.n == 0:
+            return [], [], np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
+        plan = st.plan_for(domain, hist.n, engine or E.default_engine())
+        hist.push(plan)
+        return (list(hist.docs), list(hist.tids)) + plan.pareto_get(hist.n)
+
+
+def pareto_ranks(domain, trials, objectives, engine=None):
+    """(tids, dominated_by, dominates, surrogate) of the history of
+    ``trials`` under ``objectives=M``, read back from the device
+    (tpe_plan_pareto_get): per trial in tid order the number of complete
+    trials that dominate it (0: on the Pareto front), the number it
+    dominates, and the surrogate loss ``dominated_by (n + 1) + (n -
+    dominates)`` the split ranks by; a trial that is not ok, or has a NaN or
+    +inf objective, is pending: counts 0 and surrogate +inf."""
+    return _pareto(domain, trials, objectives, engine)[1:]
+
+
+def pareto_front(domain, trials, objectives, engine=None):
+    """The trial documents on the Pareto front of ``result['objectives']``
+    -- complete trials no complete trial dominates -- in tid order."""
+    docs, _, by, _, s = _pareto(domain, trials, objectives, engine)
+    return [docs[r] for r in np.flatnonzero((by == 0) & np.isfinite(s))]
 
 
 # --------------------------------------------------------------------------

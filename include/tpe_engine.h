@@ -517,6 +517,55 @@ int tpe_plan_group_batch_points(tpe_plan_t p, const double *vals, int64_t m, int
                                 double *gain, double *trace, int32_t on_device,
                                 void *stream);
 
+/* ---- multi-objective TPE: the history ranked by Pareto dominance ----------
+ * (DESIGN 5.17).  Every objective is minimised.  A row is complete when none
+ * of its n_obj objectives is NaN or +inf, pending otherwise.  For complete
+ * rows, j dominates i when y_j[m] <= y_i[m] for every m and y_j[m] < y_i[m]
+ * for some m (IEEE comparison: -0.0 == +0.0, -inf an ordinary value).
+ *   dominated_by[i] = #{complete j : j dominates i}   (0: nondominated)
+ *   dominates[i]    = #{complete j : i dominates j}
+ *   s[i] = dominated_by[i] (n + 1) + (n - dominates[i]),  +inf if i is pending
+ * (counts 0 / 0 for a pending row).  s is an exact integer; a dominates b
+ * implies s[a] < s[b]; with one objective and distinct losses s sorts as the
+ * loss does.
+ *
+ * tpe_plan_set_objectives copies rows [obj0, n) of every objective from Y
+ * (row r of objective m at Y[m * ld + (r - obj0)]) into the plan's objective
+ * matrix (allocated by the first call, at the plan's trial capacity; rows
+ * below obj0 are those of the last call, which must have had the same n_obj
+ * and at least obj0 rows), counts over all rows [0, n) and overwrites the loss
+ * column of rows [0, n) with s: the fits, the joint and group models, the
+ * batch and the draws then rank the history by Pareto dominance with no other
+ * change.  n must be the plan's history length.  Stream-ordered like every
+ * plan call; a deferred tpe_plan_update_history is written first, so none of
+ * its losses can land on s -- a later history update that carries losses
+ * overwrites s in its turn.  The fit, the joint fit and the group fit are
+ * invalidated.  The counts use integer atomics only: they depend on Y alone,
+ * not on the launch shape.  TPE_E_INVALID: n_obj outside [1, TPE_MAX_OBJ], n
+ * other than the history length, (n + 1)^2 >= 2^53, obj0 outside [0, n] or
+ * above the rows held, ld < n - obj0, or a null Y.  An empty history (n = 0)
+ * is accepted and ranks nothing.                                            */
+#define TPE_MAX_OBJ 8
+int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_t n,
+                            int64_t ld, int64_t obj0, int32_t on_device, void *stream);
+
+/* Host copies of the last tpe_plan_set_objectives' results: dominated_by[n],
+ * dominates[n] and the loss column s[n] as the device holds it now (each may
+ * be NULL).  n must be that call's.  Waits for the device.                   */
+int tpe_plan_pareto_get(tpe_plan_t p, int32_t *dominated_by, int32_t *dominates,
+                        double *loss, int64_t n);
+
+/* The launch the ranking takes for n rows of n_obj objectives, and a test
+ * hook: out[0] = rows per tile, out[1] = TPE_MAX_OBJ, out[2] = the j-splits
+ * (blocks that share a tile of rows i and split the rows j), out[3] = the
+ * tiles.  force_splits > 0: plan with that many j-splits, in this call and in
+ * this plan's later tpe_plan_set_objectives calls (at most one per tile; the
+ * plan rounds to a count without an empty split); 0: back to the default;
+ * < 0: leave the plan's setting.  TPE_E_INVALID when (n, n_obj) is out of
+ * range.                                                                     */
+int tpe_plan_pareto_shape(tpe_plan_t p, int64_t n, int32_t n_obj, int64_t force_splits,
+                          int64_t *out);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
