@@ -796,6 +796,7 @@ StepShape step_shape(const tpe_plan *p, int64_t n_sug, int64_t n_cand, int64_t c
   s.fit = f;
   s.prune_mode = p->prune_mode;
   s.lattice_on = p->lattice_on;
+  s.screen_run = step_screen_run(switches());
   return s;
 }
 
@@ -962,7 +963,7 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, const StepShape &s, hipStre
                                    st);
             if (e == hipSuccess)
               e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats,
-                                       c.screen_guide >= 0, st);
+                                       c.screen_guide >= 0, c.screen_run, st);
           } else if (e == hipSuccess) {
             e = launch_draw_pruned(a, c.small_table, c.fast, p->d_cpos, st);
           }
@@ -1815,7 +1816,8 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
     int32_t *pos_out = nullptr;
     const DrawZone *zones = nullptr;  // (k_draw_sorted_screen's zones and counters)
     unsigned long long *stats = nullptr;
-    void *args[4] = {&da, &jobs, &lat_out, &stats};
+    int32_t run = 0;  // (k_draw_sorted_screen_run's sort blocks per block)
+    void *args[5] = {&da, &jobs, &lat_out, &stats, &run};
     if (kp.func == lattice_draw_kernel_fn()) {
       jobs = *static_cast<const LatJobs *>(kp.kernelParams[1]);
       lat_out = *static_cast<double2 *const *>(kp.kernelParams[2]);
@@ -1826,6 +1828,7 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
         zones = *static_cast<const DrawZone *const *>(kp.kernelParams[2]);
         stats = *static_cast<unsigned long long *const *>(kp.kernelParams[3]);
         args[2] = &zones;
+        if (is_screen_run_kernel_fn(kp.func)) run = *static_cast<const int32_t *>(kp.kernelParams[4]);
       }
     }
     kp.kernelParams = args;

@@ -580,6 +580,11 @@ struct __attribute__((aligned(16))) DrawZone {
   uint64_t thrI[kFuseTab][kZoneEdges];
   uint64_t pickB[kFuseTab];
   uint16_t guide[1 << kGuideBitsMax];
+  // the slot's draw table (DrawTableT<kFuseTab>'s cdf, base, mass, mode), as
+  // k_draw_zone builds it for its thresholds; written whenever nz > 0 is left.
+  // k_draw_sorted_screen_run copies it instead of building it per sort block
+  double tcdf[kFuseTab], tbase[kFuseTab], tmass[kFuseTab];
+  unsigned char tmode[kFuseTab];
 };
 // the zones of a launch's slots: after k_table_pilot, ahead of the screened draw
 // (tiles: pilot wave tiles of widening per side; margin: |x drawn - x true| / sigma covered;
@@ -588,10 +593,15 @@ hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, 
                             int32_t guide_bits, hipStream_t st);
 // launch_draw_pruned's fast small-table launch with the screen; stats: two
 // counters (blocks screened << 40 | elements inverted; blocks fallen back);
-// integer: the screen on integer uniforms (zones from a guide_bits >= 0 launch_draw_zone)
+// integer: the screen on integer uniforms (zones from a guide_bits >= 0 launch_draw_zone);
+// run >= 1 (with integer): k_draw_sorted_screen_run, a block per run of `run`
+// sort blocks (at most kScreenRunMax); 0: a block per sort block, as ever
+constexpr int kScreenRunMax = 16;
 hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
-                                unsigned long long *stats, bool integer, hipStream_t st);
-bool is_screen_draw_kernel_fn(const void *f);  // k_draw_sorted_screen's, both (tpe_screen.hip)
+                                unsigned long long *stats, bool integer, int32_t run,
+                                hipStream_t st);
+bool is_screen_draw_kernel_fn(const void *f);  // k_draw_sorted_screen's, all three (tpe_screen.hip)
+bool is_screen_run_kernel_fn(const void *f);   // ... the one with the run length as fifth parameter
 // k_table_pilot of the launch's wave-tile class on its own, for the draw that
 // needs the hot intervals (launch_score with tab_pref 2 does not launch it)
 hipError_t launch_table_pilot(const ScoreArgs &a, hipStream_t st);

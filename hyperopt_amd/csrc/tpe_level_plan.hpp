@@ -192,13 +192,21 @@ struct StepShape {
   bool lattice_on = true;
   bool capturing = false;  // under graph capture: replays patch the seeds of the draw nodes only
   bool publish = false;    // results go to the host and the last launch may publish them
+  // the run length of the integer screened draw (step_screen_run of the
+  // process switches): its grid depends on it
+  int32_t screen_run = 0;
   bool operator==(const StepShape &o) const {
     return n_sug == o.n_sug && n_cand == o.n_cand && cand_begin == o.cand_begin &&
            n_total == o.n_total && below == o.below && fit == o.fit &&
            prune_mode == o.prune_mode && lattice_on == o.lattice_on &&
-           capturing == o.capturing && publish == o.publish;
+           capturing == o.capturing && publish == o.publish && screen_run == o.screen_run;
   }
 };
+// StepShape::screen_run under the switches: TPE_DRAW_SCREEN_RUN for the integer
+// screen, 0 (a block per sort block) for the float one
+inline int32_t step_screen_run(const Switches &sw) {
+  return sw.draw_screen && sw.draw_screen_int ? (int32_t)sw.draw_screen_run : 0;
+}
 
 // Scoring grid of one launch: runs of equal-kind slots become groups of the
 // 1-D grid (tiles of tile_cands(kind) candidates); pstride: the partial-record
@@ -291,6 +299,7 @@ struct ChunkPlan {
   bool fast = false;         // the sorted draw without the out-of-line draws
   int32_t screen_tiles = 0;  // Draw::SortedScreened: the zones' widening
   int32_t screen_guide = -1; // ... the integer screen's guide bits; -1: the float screen
+  int32_t screen_run = 0;    // ... its sort blocks per block (k_draw_sorted_screen_run); 0: one, as ever
   bool bucket = false;       // k_bucket follows the draw
   bool cand_pos = false;     // the scoring launch reads candidate positions
   // the main scoring launch: ScoreArgs::tab_on / tab_pref (2 behind a pruning
@@ -500,6 +509,7 @@ inline LevelPlan plan_level(const PlanShape &ps, const Switches &sw, const StepS
       c.draw = screen ? Draw::SortedScreened : prune ? Draw::SortedPruned : Draw::Sorted;
       c.screen_tiles = (int32_t)sw.draw_screen_tiles;
       c.screen_guide = sw.draw_screen_int ? (int32_t)sw.draw_screen_guide_bits : -1;
+      c.screen_run = screen && c.screen_guide >= 0 ? s.screen_run : 0;
       if (prune) c.tab_pref = 2;
     } else {
       c.draw = Draw::Plain;

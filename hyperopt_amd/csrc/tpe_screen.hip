@@ -11,14 +11,18 @@
 // candidate, inverts only the ones inside a zone, and composes the kept tiles
 // from those alone where it can prove that the layout is the full draw's.
 // Where it cannot, the sort block runs sorted_block_prune_body from scratch.
-// k_draw_sorted_screen_int (the default) makes the same decisions on the
-// uniforms' 53-bit integers: the pick from a guide table on the top bits of
-// U0, the class from integer thresholds on U1, no double before the inversion.
+// k_draw_sorted_screen_int makes the same decisions on the uniforms' 53-bit
+// integers: the pick from a guide table on the top bits of U0, the class from
+// integer thresholds on U1, no double before the inversion.
+// k_draw_sorted_screen_run (the default) is that kernel by runs of sort blocks:
+// the slot's state once per run, its table from k_draw_zone, Philox in the row
+// form and the uniforms in their word form (tpe_philox_row.hpp).
 #include <float.h>
 #include <math.h>
 
 #include "tpe_draw.hpp"
 #include "tpe_internal.hpp"
+#include "tpe_philox_row.hpp"
 
 namespace tpe {
 
@@ -190,6 +194,16 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
   if (nz == 0) return;
   const double *bw = A.mw + sb * A.kcap, *bmu = A.mmu + sb * A.kcap, *bsg = A.msig + sb * A.kcap;
   build_table(H, K, bw, bmu, bsg, T);
+  // the table for k_draw_sorted_screen_run.  The draw's own build_table gives
+  // these bits: with K <= kFuseTab every element sits in wave 0, one per
+  // thread, in this block of 256 threads as in the draw's of 512
+  static_assert(kFuseTab <= 64 && kFuseTab <= kZoneThreads, "the table's scan stays in wave 0");
+  if (t < K) {
+    Z->tcdf[t] = T.cdf[t];
+    Z->tbase[t] = T.base[t];
+    Z->tmass[t] = T.mass[t];
+    Z->tmode[t] = T.mode[t];
+  }
   if (gbits >= 0) {
     // pick boundary j: the smallest U in [0, 2^53] with cdf[j] <= fl(U 2^-53
     // cdf_last) -- the draw's own product, monotone in U -- by bisection
@@ -343,6 +357,102 @@ __device__ __forceinline__ int screen_bucket(double key, double lo, double scale
   return b;
 }
 
+// Phase 2 of a screened sort block and the composition of its kept tiles, for
+// screened_block and screened_block_run: the wave's ncl inverted elements sit
+// in its list, [lo, hi] is the block's key range and (y_lo, y_hi, nh) the head
+// of the slot's hot intervals.  False: a live bucket may hold a cold element
+// (nothing is written).
+template <int NT>
+__device__ __forceinline__ bool screen_compose(const ScoreArgs &A, int s, int hp, int64_t base,
+                                               int64_t off, int n, int nz, int ncl, double lo,
+                                               double hi, double mu, const TabHot *hot,
+                                               double y_lo, double y_hi, int nh,
+                                               const DrawZone *__restrict__ Z,
+                                               int32_t *__restrict__ pos_out, ScreenLds<NT> &L,
+                                               int t) {
+  constexpr int NW = NT / 64;
+  const int lane = t & 63, wv = t >> 6;
+  double *cx = L.cx[wv];
+  uint32_t *ci = L.ci[wv];
+  uint32_t *mine = L.cnt + wv * (kSortBuckets / 2);
+  double *out = const_cast<double *>(A.cand) + off;
+  // phase 2: buckets and the hot test of the inverted elements, as
+  // sorted_block_prune_body's second pass
+  const double scale = hi > lo ? (double)kSortBuckets / (hi - lo) : 0.0;
+#pragma unroll 1
+  for (int j0 = 0; j0 < ncl; j0 += 64) {
+    const int j = j0 + lane;
+    if (j < ncl) {
+      const double x = cx[j];
+      const int b = screen_bucket(x, lo, scale);
+      ci[j] = (ci[j] & 0xffffu) | ((uint32_t)b << 16);
+      __hip_atomic_fetch_add(&mine[b >> 1], 1u << ((b & 1) * 16), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+      const double y = x - mu;
+      const double yc = fmin(fmax(y, y_lo), y_hi);
+      bool hit = y != y;
+      for (int q = 0; q < nh; ++q) hit |= yc >= hot->lo[q] && yc <= hot->hi[q];
+      if (hit) L.hotb[b] = 1;
+    }
+  }
+  // a gap's cold elements: counted in the bucket of the zone edge below them
+  // (their own buckets lie between that and the bucket of the edge above)
+  if (lane < nz - 1) {
+    const int c = L.gapc[wv][lane];
+    if (c > 0) {
+      const int b = screen_bucket(Z->gap_lo[lane], lo, scale);
+      __hip_atomic_fetch_add(&mine[b >> 1], (uint32_t)c << ((b & 1) * 16), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  bucket_bases_scan<NW>(L.cnt);
+  int bb = 0, be = 0;
+  if (t < kSortBuckets) {
+    bb = (int)((L.cnt[t >> 1] >> ((t & 1) * 16)) & 0xffffu);
+    be = t == kSortBuckets - 1 ? n : (int)((L.cnt[(t + 1) >> 1] >> (((t + 1) & 1) * 16)) & 0xffffu);
+    if (be > bb && L.hotb[t]) atomicOr(&L.keep, tile_bits(bb >> 7, (be - 1) >> 7));
+  }
+  __syncthreads();
+  const unsigned long long keep = L.keep;
+  if (t < kSortBuckets) {
+    const bool live = be > bb && (keep & tile_bits(bb >> 7, (be - 1) >> 7)) != 0ull;
+    L.liveb[t] = live ? 1 : 0;
+    // a live bucket inside the bucket range a gap's cold elements can occupy:
+    // its base or its members may differ from the full draw's
+    if (live) {
+      for (int g = 0; g < nz - 1; ++g) {
+        int c = 0;
+        for (int w = 0; w < NW; ++w) c += L.gapc[w][g];
+        if (c > 0 && t >= screen_bucket(Z->gap_lo[g], lo, scale) &&
+            t <= screen_bucket(Z->gap_hi[g], lo, scale))
+          L.fail = 1;
+      }
+    }
+  }
+  __syncthreads();
+  if (L.fail) return false;
+  // every hot and every live bucket holds inverted elements only, and each
+  // cold element's bucket is on its proxy's side of every live bucket: keep,
+  // the live buckets' bases and the ranks are the full draw's
+  int32_t *po = pos_out + off;
+  double *__restrict__ wm = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * 8 + (base >> 7);
+  const int ntile = (n + 127) >> 7;
+  if (t < ntile) wm[t] = ((keep >> t) & 1ull) ? INFINITY : -INFINITY;
+#pragma unroll 1
+  for (int j0 = 0; j0 < ncl; j0 += 64) {
+    const int j = j0 + lane;
+    const uint32_t ik = j < ncl ? ci[j] : 0u;
+    const bool lv = j < ncl && L.liveb[ik >> 16] != 0;
+    const int p = bucket_rank(mine, lv ? ik >> 16 : 0u, lv);
+    if (lv && ((keep >> (p >> 7)) & 1ull)) {
+      out[p] = cx[j];
+      po[p] = (int32_t)(base + (ik & 0xffffu));
+    }
+  }
+  return true;
+}
+
 // One sort block of a screened slot (Z.nz >= 2: a bounded GMM slot, not
 // quantized, K <= CAP, pruned by sorted_block_prune_body).  True: the block's
 // kept tiles and tab_wmax marks are written, as that body writes them.
@@ -382,7 +492,6 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
   const uint64_t seed = suggestion_seed(A, s);
   const int n = (int)min<int64_t>((int64_t)1 << A.sort_log2, A.n_cand - base);
   const int64_t off = (int64_t)s * A.cand_sstride + (int64_t)slot * A.n_cand + base;
-  double *out = const_cast<double *>(A.cand) + off;
   // the wave's rows: bucket_bases' [r0, r1)
   const int per = ((n + NW * 64 - 1) / (NW * 64)) * 64;
   int r0 = wv * per, r1 = min(n, r0 + per);
@@ -510,86 +619,13 @@ __device__ __forceinline__ bool screened_block(const ScoreArgs &A, int slot, int
   // every cold element lies strictly between the tails' edges: with an
   // inverted element at or beyond each, the key range is the full draw's
   if (L.fail || !(lo <= Z->gap_lo[0]) || !(hi >= Z->gap_hi[nz - 2])) return false;
-  // phase 2: buckets and the hot test of the inverted elements, as
-  // sorted_block_prune_body's second pass
-  const double scale = hi > lo ? (double)kSortBuckets / (hi - lo) : 0.0;
   const double mu = H.prior_mu;
   const TabHot *hot = A.tab_hot + ((int64_t)s * A.n_hp + hp);
   const double y_lo = hot->y_lo, y_hi = hot->y_hi;
   int nh = 0;
   while (nh < kHotIv && hot->lo[nh] <= hot->hi[nh]) ++nh;
-#pragma unroll 1
-  for (int j0 = 0; j0 < ncl; j0 += 64) {
-    const int j = j0 + lane;
-    if (j < ncl) {
-      const double x = cx[j];
-      const int b = screen_bucket(x, lo, scale);
-      ci[j] = (ci[j] & 0xffffu) | ((uint32_t)b << 16);
-      __hip_atomic_fetch_add(&mine[b >> 1], 1u << ((b & 1) * 16), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-      const double y = x - mu;
-      const double yc = fmin(fmax(y, y_lo), y_hi);
-      bool hit = y != y;
-      for (int q = 0; q < nh; ++q) hit |= yc >= hot->lo[q] && yc <= hot->hi[q];
-      if (hit) L.hotb[b] = 1;
-    }
-  }
-  // a gap's cold elements: counted in the bucket of the zone edge below them
-  // (their own buckets lie between that and the bucket of the edge above)
-  if (lane < nz - 1) {
-    const int c = L.gapc[wv][lane];
-    if (c > 0) {
-      const int b = screen_bucket(Z->gap_lo[lane], lo, scale);
-      __hip_atomic_fetch_add(&mine[b >> 1], (uint32_t)c << ((b & 1) * 16), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  }
-  __syncthreads();
-  bucket_bases_scan<NW>(L.cnt);
-  int bb = 0, be = 0;
-  if (t < kSortBuckets) {
-    bb = (int)((L.cnt[t >> 1] >> ((t & 1) * 16)) & 0xffffu);
-    be = t == kSortBuckets - 1 ? n : (int)((L.cnt[(t + 1) >> 1] >> (((t + 1) & 1) * 16)) & 0xffffu);
-    if (be > bb && L.hotb[t]) atomicOr(&L.keep, tile_bits(bb >> 7, (be - 1) >> 7));
-  }
-  __syncthreads();
-  const unsigned long long keep = L.keep;
-  if (t < kSortBuckets) {
-    const bool live = be > bb && (keep & tile_bits(bb >> 7, (be - 1) >> 7)) != 0ull;
-    L.liveb[t] = live ? 1 : 0;
-    // a live bucket inside the bucket range a gap's cold elements can occupy:
-    // its base or its members may differ from the full draw's
-    if (live) {
-      for (int g = 0; g < nz - 1; ++g) {
-        int c = 0;
-        for (int w = 0; w < NW; ++w) c += L.gapc[w][g];
-        if (c > 0 && t >= screen_bucket(Z->gap_lo[g], lo, scale) &&
-            t <= screen_bucket(Z->gap_hi[g], lo, scale))
-          L.fail = 1;
-      }
-    }
-  }
-  __syncthreads();
-  if (L.fail) return false;
-  // every hot and every live bucket holds inverted elements only, and each
-  // cold element's bucket is on its proxy's side of every live bucket: keep,
-  // the live buckets' bases and the ranks are the full draw's
-  int32_t *po = pos_out + off;
-  double *__restrict__ wm = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * 8 + (base >> 7);
-  const int ntile = (n + 127) >> 7;
-  if (t < ntile) wm[t] = ((keep >> t) & 1ull) ? INFINITY : -INFINITY;
-#pragma unroll 1
-  for (int j0 = 0; j0 < ncl; j0 += 64) {
-    const int j = j0 + lane;
-    const uint32_t ik = j < ncl ? ci[j] : 0u;
-    const bool lv = j < ncl && L.liveb[ik >> 16] != 0;
-    const int p = bucket_rank(mine, lv ? ik >> 16 : 0u, lv);
-    if (lv && ((keep >> (p >> 7)) & 1ull)) {
-      out[p] = cx[j];
-      po[p] = (int32_t)(base + (ik & 0xffffu));
-    }
-  }
-  return true;
+  return screen_compose<NT>(A, s, hp, base, off, n, nz, ncl, lo, hi, mu, hot, y_lo, y_hi, nh, Z,
+                            pos_out, L, t);
 }
 
 // k_draw_sorted_prune with the screen: the same grid, the same slots; a slot
@@ -647,18 +683,322 @@ void k_draw_sorted_screen_int(ScoreArgs A, int32_t *__restrict__ pos_out,
   draw_sorted_screen_body<CAP, FAST, true>(A, pos_out, zones, stats);
 }
 
+// ------------------------------------------------------------------------
+// k_draw_sorted_screen_run
+// ------------------------------------------------------------------------
+// The integer screen with what the sort blocks of a slot share taken out of
+// them.  A block draws a run of consecutive sort blocks of its (suggestion,
+// slot row) and reads the slot's descriptors, seed, hot intervals' head and
+// DrawZone once per run -- the draw table included, which k_draw_zone leaves
+// there, so no sort block builds it.  Philox runs in the row form and the
+// uniforms are compared in their word form (tpe_philox_row.hpp).  Every kept
+// tile, position and mark is k_draw_sorted_screen_int's.
+
+// a block-uniform value into scalar registers (a load behind the kernel's
+// first store is a vector load, whatever its address)
+__device__ __forceinline__ int run_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double run_uniform(double v) {
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return __longlong_as_double((long long)(
+      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b)));
+}
+
+// what the sort blocks of a run share (wave-uniform, but for m0lane)
+struct RunSlot {
+  int hp, K, nz, gsh, nh;
+  uint32_t k0, k1;
+  double low, high, high_prev, mu, y_lo, y_hi;
+  double gap_first, gap_last;  // Z->gap_lo[0], Z->gap_hi[nz - 2]
+  const double *bmu, *bsg;
+  const TabHot *hot;
+  uint64_t m0lane;             // philox_row_lane_term of the lane
+};
+
+// The slot's state in LDS: the draw table from the DrawZone, the thresholds
+// and the pick boundaries in word form (the edges from E up: none), the guide.
+// The caller's barrier follows.
+template <int NT>
+__device__ __forceinline__ void run_slot_lds(const DrawZone *__restrict__ Z, int K, int nz, int G,
+                                             ScreenLds<NT> &L, int t) {
+  const int E = 2 * (nz - 1);
+  if (t < K) {
+    L.T.cdf[t] = Z->tcdf[t];
+    L.T.base[t] = Z->tbase[t];
+    L.T.mass[t] = Z->tmass[t];
+    L.T.mode[t] = Z->tmode[t];
+  }
+  for (int idx = t; idx < K * kZoneEdges; idx += NT)
+    L.thrI[idx] = u53_word_threshold(idx % kZoneEdges < E ? (&Z->thrI[0][0])[idx] : 1ull << 53);
+  for (int idx = t; idx < (1 << G); idx += NT) L.guide[idx] = Z->guide[idx];
+  if (t < kFuseTab) L.pickB[t] = u53_word_threshold(Z->pickB[t]);
+}
+
+// screened_block<CAP, NT, true> for one sort block of a run: the slot's LDS
+// state is in place (run_slot_lds) and hotb, keep and fail are reset, both
+// behind a barrier.  t: the thread's index in the block.
+template <int CAP, int NT>
+__device__ __forceinline__ bool screened_block_run(const ScoreArgs &A, const RunSlot &R, int slot,
+                                                   int s, int64_t base,
+                                                   int32_t *__restrict__ pos_out,
+                                                   const DrawZone *__restrict__ Z,
+                                                   ScreenLds<NT> &L, int t, int &nexact) {
+  constexpr int NW = NT / 64;
+  const int lane = t & 63, wv = t >> 6;
+  const int nz = R.nz, E = 2 * (nz - 1), gsh = R.gsh;
+  const int n = (int)min<int64_t>((int64_t)1 << A.sort_log2, A.n_cand - base);
+  const int64_t off = (int64_t)s * A.cand_sstride + (int64_t)slot * A.n_cand + base;
+  const int per = ((n + NW * 64 - 1) / (NW * 64)) * 64;
+  const int r0 = __builtin_amdgcn_readfirstlane(wv * per);
+  const int r1 = __builtin_amdgcn_readfirstlane(min(n, wv * per + per));
+  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  double *cx = L.cx[wv];
+  uint32_t *ci = L.ci[wv];
+  // phase 1, as screened_block's integer one
+  int ncl = 0;  // (wave-uniform)
+  int gc[kZoneMax - 1];
+#pragma unroll
+  for (int g = 0; g < kZoneMax - 1; ++g) gc[g] = 0;
+#pragma unroll 1
+  for (int rb = r0; rb < r1; rb += 64) {
+    const int i = rb + lane;
+    const bool v = i < r1;
+    // the row's first counter, wave-uniform; its lanes' are g0 + lane
+    const uint64_t gr = (uint64_t)(A.cand_begin + base + rb);
+    const uint64_t g0 =
+        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(gr >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gr);
+    PhiloxWords r;
+    if (philox_row_ok((uint32_t)g0)) {  // (a scalar branch)
+      PhiloxRow row = philox_row_setup(g0, (uint32_t)R.hp, R.k0, R.k1);
+      // (the uniform product through an empty asm statement: it stays a scalar
+      // one, not folded with the lane's term into a per-lane multiply-add)
+      asm volatile("" : "+s"(row.p0));
+      r = philox_row(row, R.m0lane, R.k0, R.k1);
+    } else {  // the low word wraps inside the row
+      const uint64_t gi = g0 + (uint64_t)lane;
+      const U4 q = philox(U4{(uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)R.hp, 0u}, R.k0, R.k1);
+      r = PhiloxWords{q.x, q.y, q.z, q.w};
+    }
+    const uint64_t W0 = u53_word(r.x, r.y), W1 = u53_word(r.z, r.w);
+    const uint32_t ge = L.guide[(r.x >> 1) >> gsh];
+    const uint32_t kl = ge & 0xffu;
+    const int k = (int)(kl + (W0 >= L.pickB[kl] ? ge >> 8 : 0u));
+    const ulonglong2 *th = reinterpret_cast<const ulonglong2 *>(L.thrI + k * kZoneEdges);
+    static_assert(kZoneEdges == 10, "five threshold pairs");
+    int c;
+    {
+      const ulonglong2 a = th[0], b = th[1];
+      c = (W1 >= a.x ? 1 : 0) + (W1 >= a.y ? 1 : 0) + (W1 >= b.x ? 1 : 0) + (W1 >= b.y ? 1 : 0);
+    }
+    if (E > 4) {
+      const ulonglong2 a = th[2], b = th[3], d = th[4];
+      c += (W1 >= a.x ? 1 : 0) + (W1 >= a.y ? 1 : 0) + (W1 >= b.x ? 1 : 0) + (W1 >= b.y ? 1 : 0) +
+           (W1 >= d.x ? 1 : 0) + (W1 >= d.y ? 1 : 0);
+    }
+    const uint64_t vm = __builtin_amdgcn_ballot_w64(v);
+    const uint64_t bal = __builtin_amdgcn_ballot_w64((c & 1) == 0) & vm;
+    const bool exact = __builtin_amdgcn_inverse_ballot_w64(bal);
+    const int pos = ncl + __popcll(bal & below);
+    if (exact && pos < kScreenList) {
+      cx[pos] = __longlong_as_double((long long)W1);  // (the list keeps U1's word form)
+      ci[pos] = (uint32_t)i | ((uint32_t)k << 16);
+    }
+    ncl += __popcll(bal);
+#pragma unroll
+    for (int g = 0; g < kZoneMax - 1; ++g) {
+      if (g >= nz - 1) continue;
+      gc[g] += __popcll(__builtin_amdgcn_ballot_w64(c == 2 * g + 1) & vm);
+    }
+  }
+  const bool over = ncl > kScreenList;  // (a list overflow: the block falls back)
+  if (over) ncl = 0;
+  if (lane == 0) {
+    L.ncl[wv] = ncl;
+#pragma unroll
+    for (int g = 0; g < kZoneMax - 1; ++g) L.gapc[wv][g] = gc[g];
+    if (over) L.fail = 1;
+  }
+  // the inversion of the listed elements, in dense rows
+  double lo = INFINITY, hi = -INFINITY;
+#pragma unroll 1
+  for (int j0 = 0; j0 < ncl; j0 += 64) {
+    const int j = j0 + lane;
+    const bool v = j < ncl;
+    // (an idle lane inverts u1 = 0.5)
+    const double u1 = u53_word_value(v ? (uint64_t)__double_as_longlong(cx[j]) : 1ull << 58);
+    const int k = v ? (int)(ci[j] >> 16) : 0;
+    const double x = draw_bounded_invert<CAP>(L.T, k, u1, R.bmu, R.bsg, R.low, R.high, R.high_prev,
+                                              false, false, 0.0);
+    if (v) {
+      cx[j] = x;
+      if (fabs(x) < INFINITY) { lo = fmin(lo, x); hi = fmax(hi, x); }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, o, 64));
+    hi = fmax(hi, __shfl_xor(hi, o, 64));
+  }
+  if (lane == 0) { L.red[0][wv] = lo; L.red[1][wv] = hi; }
+  uint32_t *mine = L.cnt + wv * (kSortBuckets / 2);
+  for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
+  __syncthreads();
+  lo = INFINITY; hi = -INFINITY;
+  nexact = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    lo = fmin(lo, L.red[0][w]);
+    hi = fmax(hi, L.red[1][w]);
+    nexact += L.ncl[w];
+  }
+  if (L.fail || !(lo <= R.gap_first) || !(hi >= R.gap_last)) return false;
+  return screen_compose<NT>(A, s, R.hp, base, off, n, nz, ncl, lo, hi, R.mu, R.hot, R.y_lo, R.y_hi,
+                            R.nh, Z, pos_out, L, t);
+}
+
+// Block x of the grid takes the sort blocks x run + 1 .. min(x run + run, the
+// last) of its row.  A sort block whose screen cannot prove its layout runs
+// sorted_block_prune_body, which overwrites the union: those run behind the
+// run's last screened sort block, so the slot's LDS state is loaded once.  The
+// two counters get the run's totals.
+template <int CAP, bool FAST>
+__device__ __forceinline__ void draw_sorted_screen_run_body(const ScoreArgs &A,
+                                                            int32_t *__restrict__ pos_out,
+                                                            const DrawZone *__restrict__ zones,
+                                                            unsigned long long *stats, int run) {
+  static_assert(CAP == kFuseTab && FAST, "the small-table inline draw only");
+  __shared__ __attribute__((aligned(16))) ScreenUnion<CAP, kScreenThreads> U;
+  const int s = blockIdx.z;
+  const int slot = row_slot(A, s, 0, A.n_slots, blockIdx.y);
+  if (slot < 0) return;
+  const int hp = A.level_hps[slot];
+  if (!A.force_active && !A.compact &&
+      !hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch))
+    return;
+  const int kind = slot_kind(A, slot);
+  if ((kind == KIND_CAT || kind == KIND_LAT) && lookup_inline(A, A.info[2 * hp].K)) return;
+  const bool tabk = kind == KIND_LSE_GW || kind == KIND_LSE_LW;
+  if (tabk && blockIdx.x == 0 && threadIdx.x < (1 << A.sort_log2) / 128 &&
+      (int64_t)threadIdx.x * 128 < A.n_cand)
+    A.tab_wmax[((int64_t)s * A.n_hp + hp) * A.pstride * 8 + threadIdx.x] = INFINITY;
+  // the sort blocks behind the pilot's: 1 .. nsb; this block's: j0 + 1 .. j1
+  const int nsb = (int)(((A.n_cand + ((int64_t)1 << A.sort_log2) - 1) >> A.sort_log2) - 1);
+  const int j0 = (int)blockIdx.x * run, j1 = min(j0 + run, nsb);
+  const bool bucket = kind_lse(kind) || kind == KIND_ERF_G || kind == KIND_ERF_L;
+  const bool lg = kind_logn(kind);
+  const DrawZone *Z = zones + ((int64_t)s * A.n_hp + hp);
+  const int nz = kind == KIND_LSE_GW ? __builtin_amdgcn_readfirstlane(Z->nz) : 0;
+  const bool scr = nz >= 2 && nz <= kZoneMax;  // (block-uniform)
+  RunSlot R{};
+  if (scr) {
+    const tpe_hp &H = A.hps[hp];
+    const int64_t sb = 2 * (int64_t)hp;
+    const uint64_t seed = suggestion_seed(A, s);
+    R.hp = hp;
+    R.K = run_uniform(A.info[sb].K);
+    R.nz = nz;
+    R.gsh = 31 - min(max(__builtin_amdgcn_readfirstlane(Z->gbits), 0), kGuideBitsMax);
+    R.k0 = (uint32_t)run_uniform((int)(uint32_t)seed);
+    R.k1 = (uint32_t)run_uniform((int)(uint32_t)(seed >> 32));
+    R.low = run_uniform(H.low);
+    R.high = run_uniform(H.high);
+    R.high_prev = run_uniform(nextafter(H.high, -INFINITY));
+    R.mu = run_uniform(H.prior_mu);
+    R.bmu = A.mmu + sb * A.kcap;
+    R.bsg = A.msig + sb * A.kcap;
+    R.hot = A.tab_hot + ((int64_t)s * A.n_hp + hp);
+    R.y_lo = run_uniform(R.hot->y_lo);
+    R.y_hi = run_uniform(R.hot->y_hi);
+    while (R.nh < kHotIv && R.hot->lo[R.nh] <= R.hot->hi[R.nh]) ++R.nh;
+    R.nh = run_uniform(R.nh);
+    R.gap_first = run_uniform(Z->gap_lo[0]);
+    R.gap_last = run_uniform(Z->gap_hi[nz - 2]);
+    R.m0lane = philox_row_lane_term(threadIdx.x & 63);
+  }
+  unsigned long long screened = 0ull;  // (blocks screened << 40 | elements inverted)
+  // the run's sort blocks left to sorted_block_prune_body (bit j - j0): all of
+  // a slot without zones, else the ones whose screen could not prove its layout
+  static_assert(kScreenRunMax <= 31, "a run's sort blocks: one mask");
+  uint32_t todo = scr ? 0u : (1u << (j1 - j0)) - 1u;
+  if (scr) {
+    run_slot_lds(Z, R.K, nz, 31 - R.gsh, U.S, (int)threadIdx.x);
+#pragma unroll 1
+    for (int j = j0; j < j1; ++j) {
+      // (the thread's index through an empty asm statement: what a sort block
+      // derives from it -- its lane masks and addresses -- is computed per
+      // sort block, not kept in registers, phase beside phase, across the run)
+      int t = threadIdx.x;
+      asm volatile("" : "+v"(t));
+      // (the sort block before this one may still be read)
+      if (j > j0) __syncthreads();
+      if (t < kSortBuckets) U.S.hotb[t] = 0;
+      if (t == 0) { U.S.keep = 0ull; U.S.fail = 0; }
+      __syncthreads();
+      int nexact = 0;
+      if (screened_block_run<CAP, kScreenThreads>(A, R, slot, s, (int64_t)(j + 1) << A.sort_log2,
+                                                  pos_out, Z, U.S, t, nexact))
+        screened += (1ull << 40) | (unsigned long long)nexact;
+      else
+        todo |= 1u << (j - j0);
+    }
+  }
+  // (behind the run's screened sort blocks, in a loop of their own: that body
+  // overwrites the union, and its registers stay out of the loop above)
+  const int fallen = scr ? __popc(todo) : 0;
+#pragma unroll 1
+  for (int j = j0; todo != 0u; ++j, todo >>= 1) {
+    if (__builtin_expect_with_probability(!(todo & 1u), 1, 0.9999999)) continue;
+    __syncthreads();
+    // (the slot and the LDS address through an empty asm statement: nothing
+    // of what that body derives from them is kept in registers across this
+    // loop)
+    int fslot = slot, fs = s;
+    typedef PruneDrawLds<CAP, kScreenThreads> __attribute__((address_space(3))) *PruneLds;
+    PruneLds lds = (PruneLds)&U.P;
+    asm volatile("" : "+s"(fslot), "+s"(fs), "+v"(lds));
+    sorted_block_prune_body<CAP, kScreenThreads, FAST>(A, fslot, fs, (int64_t)(j + 1) << A.sort_log2,
+                                                       bucket, lg, tabk, pos_out,
+                                                       *(PruneDrawLds<CAP, kScreenThreads> *)lds);
+  }
+  if (threadIdx.x == 0) {
+    if (screened) atomicAdd(stats, screened);
+    if (fallen) atomicAdd(stats + 1, (unsigned long long)fallen);
+  }
+}
+template <int CAP, bool FAST>
+__global__ __launch_bounds__(kScreenThreads) __attribute__((amdgpu_waves_per_eu(4)))
+void k_draw_sorted_screen_run(ScoreArgs A, int32_t *__restrict__ pos_out,
+                              const DrawZone *__restrict__ zones, unsigned long long *stats,
+                              int32_t run) {
+  draw_sorted_screen_run_body<CAP, FAST>(A, pos_out, zones, stats, run);
+}
+
+bool is_screen_run_kernel_fn(const void *f) {
+  return f == reinterpret_cast<const void *>(&k_draw_sorted_screen_run<kFuseTab, true>);
+}
 bool is_screen_draw_kernel_fn(const void *f) {
   return f == reinterpret_cast<const void *>(&k_draw_sorted_screen<kFuseTab, true>) ||
-         f == reinterpret_cast<const void *>(&k_draw_sorted_screen_int<kFuseTab, true>);
+         f == reinterpret_cast<const void *>(&k_draw_sorted_screen_int<kFuseTab, true>) ||
+         is_screen_run_kernel_fn(f);
 }
 
 hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
-                                unsigned long long *stats, bool integer, hipStream_t st) {
+                                unsigned long long *stats, bool integer, int32_t run,
+                                hipStream_t st) {
   const int64_t sbk = (int64_t)1 << a.sort_log2;
   if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
-  if (sbk != kSortedBlock || !a.tab_wmax || !a.tab_hot || !a.tab_hdr || !zones || !stats)
+  if (sbk != kSortedBlock || !a.tab_wmax || !a.tab_hot || !a.tab_hdr || !zones || !stats ||
+      run < 0 || run > kScreenRunMax)
     return hipErrorInvalidValue;
-  const dim3 g((unsigned)((a.n_cand + sbk - 1) / sbk - 1), (unsigned)a.slot_rows, a.n_suggest);
+  const int64_t nsb = (a.n_cand + sbk - 1) / sbk - 1;
+  if (integer && run >= 1) {
+    const dim3 gr((unsigned)((nsb + run - 1) / run), (unsigned)a.slot_rows, a.n_suggest);
+    k_draw_sorted_screen_run<kFuseTab, true><<<gr, kScreenThreads, 0, st>>>(a, pos_out, zones, stats,
+                                                                            run);
+    return hipGetLastError();
+  }
+  const dim3 g((unsigned)nsb, (unsigned)a.slot_rows, a.n_suggest);
   if (integer)
     k_draw_sorted_screen_int<kFuseTab, true><<<g, kScreenThreads, 0, st>>>(a, pos_out, zones, stats);
   else

@@ -57,6 +57,11 @@ struct Switches {
   // slot with two distinct pick boundaries in one bucket is not screened
   // (the sweep behind the default)
   int64_t draw_screen_guide_bits;
+  // the integer screen by runs: a block of k_draw_sorted_screen_run draws this
+  // many consecutive sort blocks of its slot and reads the slot's state once
+  // (the sweep behind the default); 0: k_draw_sorted_screen_int, a
+  // block per sort block
+  int64_t draw_screen_run;
   // candidate buffer per scoring chunk, MB.  8 GB (+ 4 GB of positions): config
   // 4's 1e9 candidates of a level in one draw + one scoring launch, config 5's
   // 32-suggestion calls in one chunk (config 4 79.3 -> 78.8 ms, config 5 461.3
@@ -73,6 +78,7 @@ struct Switches {
 };
 
 constexpr int64_t kDrawScreenMin = (int64_t)1 << 26;
+constexpr int64_t kDrawScreenRun = 4;
 
 // how a variable's text becomes the switch
 enum class SwitchRule {
@@ -123,6 +129,8 @@ inline const SwitchDef *switch_table(int *n) {
        hi},
       {"TPE_DRAW_SCREEN_GUIDE_BITS", R::ValueIfNonEmpty, 9, nullptr, &S::draw_screen_guide_bits, 0,
        kGuideBitsMax},
+      {"TPE_DRAW_SCREEN_RUN", R::ValueIfNonEmpty, kDrawScreenRun, nullptr, &S::draw_screen_run, 0,
+       kScreenRunMax},
       {"TPE_CHUNK_MB", R::ValueIfSet, 8192, nullptr, &S::chunk_mb, lo, hi},
       {"TPE_SHIFT_MIN_K", R::ValueIfSet, 512, nullptr, &S::lse_shift_min, lo, hi},
   };
