@@ -44,6 +44,7 @@ EXPORTS = (
     'tpe_plan_sample_prior', 'tpe_plan_score_candidates_sorted', 'tpe_plan_census_n',
     'tpe_plan_tie_counts', 'tpe_plan_tab_wmax', 'tpe_plan_anneal', 'tpe_plan_anneal_trace',
     'tpe_plan_set_anneal_order', 'tpe_plan_tab_bound', 'tpe_plan_tab_hot',
+    'tpe_plan_tab_panels', 'tpe_plan_tab_cert', 'tpe_plan_tie_list',
     'tpe_plan_cand_dump', 'tpe_plan_draw_screen_stats', 'tpe_plan_score_points',
     'tpe_plan_sample_points', 'tpe_plan_topk_points', 'tpe_plan_gather_points',
     'tpe_plan_joint_fit', 'tpe_plan_joint_get_mixture', 'tpe_plan_joint_score_points',
@@ -200,6 +201,9 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_tab_wmax': (C.c_int, [vp, i32, vp]),
             'tpe_plan_tab_bound': (C.c_int, [vp, i32, vp]),
             'tpe_plan_tab_hot': (C.c_int, [vp, i32, vp]),
+            'tpe_plan_tab_panels': (C.c_int, [vp, i32, i32, vp, vp, vp, vp]),
+            'tpe_plan_tab_cert': (C.c_int, [vp, i32, i32, vp]),
+            'tpe_plan_tie_list': (C.c_int, [vp, i32, i32, vp]),
             'tpe_plan_cand_dump': (C.c_int64, [vp, i32, i32, vp, vp]),
             'tpe_plan_draw_screen_stats': (C.c_int, [vp, vp]),
             'tpe_plan_set_lattice': (C.c_int, [vp, i32]),
@@ -1212,6 +1216,46 @@ class Plan(object):
             e.check(min(n, 0))
             out = np.empty(n, dtype=np.float64)
             e.check(e.lib.tpe_plan_tab_bound(self.p, int(hp), out.ctypes.data))
+        return out
+
+    def tab_panels(self, hp, side):
+        """Debug (tpe_plan_tab_panels): the Chebyshev table of (hp, side; 0 below,
+        1 above) as the last fit left it: dict(y_lo, inv_w, P, ncert, panels) with
+        panels uint8 [P][144], the raw records (16 coefficients, M, one unused
+        double)."""
+        e = self.engine
+        y_lo, inv_w, ncert = C.c_double(), C.c_double(), C.c_int32()
+        buf = np.zeros((64, 144), dtype=np.uint8)
+        with e.lock:
+            n = e.lib.tpe_plan_tab_panels(self.p, int(hp), int(side), C.addressof(y_lo),
+                                          C.addressof(inv_w), C.addressof(ncert), buf.ctypes.data)
+            e.check(min(n, 0))
+        return dict(y_lo=y_lo.value, inv_w=inv_w.value, P=int(n), ncert=int(ncert.value),
+                    panels=buf[:n].copy())
+
+    def tab_cert(self, hp, side):
+        """Debug (tpe_plan_tab_cert): float64 [P][3] = (le, lr, lg), the log2 of
+        each panel's interpolation bound, rounding bound and lower bound of the
+        mixture as the last build computed them (certified: max(le, lr) + 1 <=
+        lg - 28)."""
+        e = self.engine
+        out = np.zeros((64, 3), dtype=np.float64)
+        with e.lock:
+            n = e.lib.tpe_plan_tab_cert(self.p, int(hp), int(side), out.ctypes.data)
+            e.check(min(n, 0))
+        return out[:n].copy()
+
+    def tie_list(self, s, hp):
+        """Debug (tpe_plan_tie_list): int32 [tie_counts[s][hp]], the wave tiles of
+        (suggestion s, hp) the direct pass of the last scoring launch that took
+        the tables was given, in list order."""
+        e = self.engine
+        with e.lock:
+            n = e.lib.tpe_plan_tie_list(self.p, int(s), int(hp), None)
+            e.check(min(n, 0))
+            out = np.empty(n, dtype=np.int32)
+            if n:
+                e.check(min(e.lib.tpe_plan_tie_list(self.p, int(s), int(hp), out.ctypes.data), 0))
         return out
 
     def tab_hot(self, n_suggest):

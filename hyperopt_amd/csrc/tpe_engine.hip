@@ -70,6 +70,12 @@ struct tpe_plan : PlanShape {
   int32_t *d_tie_cnt = nullptr;  // [s_cap][P] ... and their number per slot (-1: never gathered)
   int32_t tab_pstride = 0;       // pstride of the last launch that took the tables (tab_on 1)
   double *d_tab_bound = nullptr; // [P][kBndCells] bound lattices, built with the tables
+  // per-component certificate terms and per-slot largest a^2 of the lean build
+  // (table_terms_doubles; Switches::table_lean; null: k_table_build)
+  double *d_tab_terms = nullptr;
+  // [2P][kTabMaxPanels][3] debug: each panel's certificate (tpe_plan_tab_cert
+  // allocates it; null in every normal run)
+  double *d_tab_cert = nullptr;
   TabHot *d_tab_hot = nullptr;   // [s_cap][P] hot intervals of a launch (ScoreArgs::tab_hot)
   DrawZone *d_draw_zone = nullptr;  // [s_cap][P] the screened draw's zones (k_draw_zone)
   unsigned long long *d_screen_stats = nullptr;  // [2] tpe_plan_draw_screen_stats
@@ -290,6 +296,7 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_ticket, p->d_sortbuf, p->d_census, p->d_lat_info, p->d_lat, p->d_coef32, p->d_coefm,
                   p->d_coefm8, p->d_coefe, p->d_coefmh, p->d_tab_hdr, p->d_tab,
                   p->d_tab_max, p->d_tab_wmax, p->d_tie_list, p->d_tie_cnt, p->d_tab_bound,
+                  p->d_tab_terms, p->d_tab_cert,
                   p->d_tab_hot, p->d_draw_zone, p->d_screen_stats, p->d_pt_vals, p->d_pt_terms,
                   p->d_pt_total, p->d_pt_act, p->d_pt_idx, p->d_pt_count, p->d_pt_tab, p->d_tk,
                   p->d_tk_idx, p->d_jdims, p->d_jdim_of_hp, p->d_jrows, p->d_jcount, p->d_jcomp,
@@ -477,6 +484,7 @@ int plan_build(tpe_engine *h, const tpe_space *sp, int64_t max_trials, tpe_plan 
   CKH(hipMemset(p->d_tab_hdr, 0, (size_t)slots * sizeof(TabHdr)));
   CKH(dalloc(&p->d_tab, (size_t)slots * kTabMaxPanels));
   CKH(dalloc(&p->d_tab_bound, (size_t)p->P * kBndCells));
+  if (switches().table_lean) CKH(dalloc(&p->d_tab_terms, table_terms_doubles(p->P, kcap)));
   // expected activity of every hp (mom_width): an hp conditioned on branch b
   // of a categorical parent is active in ~1 / upper of the parent's trials
   // (levels are in dependency order: parents first)
@@ -751,7 +759,8 @@ int table_build(tpe_engine *h, tpe_plan *p, hipStream_t st) {
   if (p->tab_built) return TPE_OK;
   CKH(launch_table_build(p->d_hps, p->P, p->d_info, p->d_coef, p->kcap, p->d_tab_hdr, p->d_tab,
                          p->census ? p->d_census : nullptr, st,
-                         switches().table_prefilter ? p->d_tab_bound : nullptr));
+                         switches().table_prefilter ? p->d_tab_bound : nullptr, p->d_tab_terms,
+                         p->d_tab_cert));
   p->tab_built = true;
   return TPE_OK;
 }
@@ -797,6 +806,7 @@ StepShape step_shape(const tpe_plan *p, int64_t n_sug, int64_t n_cand, int64_t c
   s.prune_mode = p->prune_mode;
   s.lattice_on = p->lattice_on;
   s.screen_run = step_screen_run(switches());
+  s.table_lean = switches().table_lean;
   return s;
 }
 
@@ -3302,6 +3312,81 @@ int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out) {
   CKH(hipMemcpy(out, p->d_tab_bound + (int64_t)hp * kBndCells, kBndCells * sizeof(double),
                 hipMemcpyDeviceToHost));
   return TPE_OK;
+}
+
+// the tables of the current fit, built if no launch has yet, and the header
+// of (hp, side)
+static int tab_header(tpe_plan *p, int32_t hp, int32_t side, TabHdr *th) {
+  tpe_engine *h = p->eng;
+  if (hp < 0 || hp >= p->P || side < 0 || side > 1) return fail(h, TPE_E_INVALID, "bad args");
+  if (!table_hp(p->hps[hp])) return fail(h, TPE_E_INVALID, "hp has no Chebyshev table");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const int rc = table_build(h, p, h->stream);
+  if (rc) return rc;
+  CKH(hipMemcpyAsync(th, p->d_tab_hdr + 2 * (int64_t)hp + side, sizeof(*th), hipMemcpyDeviceToHost,
+                     h->stream));
+  CKH(hipStreamSynchronize(h->stream));
+  if (th->P < 0 || th->P > kTabMaxPanels) return fail(h, TPE_E_HIP, "table header out of range");
+  return TPE_OK;
+}
+
+int tpe_plan_tab_panels(tpe_plan_t p, int32_t hp, int32_t side, double *y_lo, double *inv_w,
+                        int32_t *ncert, void *panels) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  TabHdr th;
+  const int rc = tab_header(p, hp, side, &th);
+  if (rc) return rc;
+  if (y_lo) *y_lo = th.y_lo;
+  if (inv_w) *inv_w = th.inv_w;
+  if (ncert) *ncert = (int32_t)th.ncert;
+  if (panels && th.P > 0)
+    CKH(hipMemcpy(panels, p->d_tab + (2 * (int64_t)hp + side) * kTabMaxPanels,
+                  (size_t)th.P * sizeof(TabPanel), hipMemcpyDeviceToHost));
+  return th.P;
+}
+
+int tpe_plan_tab_cert(tpe_plan_t p, int32_t hp, int32_t side, double *out) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!p->d_tab_cert) {
+    // the first read: the buffer, and a build that fills it (a captured step
+    // holds the build without it)
+    CKH(hipSetDevice(h->device));
+    CKH(hipDeviceSynchronize());
+    graph_reset(p);
+    const size_t n = (size_t)2 * p->P * kTabMaxPanels * 3;
+    CKH(dalloc(&p->d_tab_cert, n));
+    CKH(hipMemset(p->d_tab_cert, 0xff, n * sizeof(double)));
+    p->tab_built = false;
+  }
+  TabHdr th;
+  const int rc = tab_header(p, hp, side, &th);
+  if (rc) return rc;
+  if (out && th.P > 0)
+    CKH(hipMemcpy(out, p->d_tab_cert + (2 * (int64_t)hp + side) * kTabMaxPanels * 3,
+                  (size_t)th.P * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return th.P;
+}
+
+int tpe_plan_tie_list(tpe_plan_t p, int32_t s, int32_t hp, int32_t *out) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (hp < 0 || hp >= p->P || s < 0 || s >= p->s_cap || p->tab_pstride <= 0 ||
+      ((size_t)s * p->P + hp + 1) * p->tab_pstride > p->partial_cap)
+    return fail(h, TPE_E_INVALID, "hp / suggestion not of the last launch that took the tables");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  int32_t n = 0;
+  CKH(hipMemcpy(&n, p->d_tie_cnt + (int64_t)s * p->P + hp, sizeof(n), hipMemcpyDeviceToHost));
+  const int64_t row = (int64_t)p->tab_pstride * 8;
+  if (n < 0) return 0;
+  if (n > row) return fail(h, TPE_E_HIP, "tie count out of range");
+  if (out && n > 0)
+    CKH(hipMemcpy(out, p->d_tie_list + ((int64_t)s * p->P + hp) * row, (size_t)n * sizeof(int32_t),
+                  hipMemcpyDeviceToHost));
+  return n;
 }
 
 int tpe_plan_draw_screen_stats(tpe_plan_t p, int64_t *out) {

@@ -633,9 +633,20 @@ hipError_t launch_math_probe(int which, const double *x, int64_t n, double *out,
 // zeroed first); census: optional pair counters ([3] and [5] += node pairs);
 // bound (optional): then the bound lattice of every hp whose two tables are
 // certified (k_table_bound)
+// terms (optional): table_terms_doubles(n_hp, kcap) doubles of scratch -- the
+// lean form (Switches::table_lean): k_table_terms writes each component's
+// certificate terms ([2 n_hp][kcap][kTabTermDoubles]) and each slot's largest
+// a^2 ([2 n_hp]) once and k_table_build_lean's panels read them; null:
+// k_table_build.
+// cert (optional, debug): [2 n_hp][kTabMaxPanels][3] = le, lr, lg of each panel
+constexpr int kTabTermDoubles = 4;
+inline size_t table_terms_doubles(int32_t n_hp, int64_t kcap) {
+  return (size_t)2 * n_hp * ((size_t)kcap * kTabTermDoubles + 1);
+}
 hipError_t launch_table_build(const tpe_hp *hps, int32_t n_hp, const MixInfo *info,
                               const Coef *coef, int64_t kcap, TabHdr *hdr, TabPanel *tab,
-                              unsigned long long *census, hipStream_t st, double *bound = nullptr);
+                              unsigned long long *census, hipStream_t st, double *bound = nullptr,
+                              double *terms = nullptr, double *cert = nullptr);
 
 // small history updates travel as kernel arguments (tpe_plan_update_history):
 // one launch, no staging copy and no host synchronisation

@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "tpe_draw.hpp"
+#include "tpe_tab_add.hpp"
 
 namespace tpe {
 
@@ -825,15 +826,7 @@ hipError_t launch_sample(const tpe_hp *hp_dev, const double *mw, const double *m
 constexpr int kTabThreads = 256;
 constexpr double kTabSkip = 64.0;
 
-struct TabAcc {
-  double m, s;  // value = 2^m * s, m integer-valued or -inf
-};
-__device__ __forceinline__ void tab_add(TabAcc &a, double t) {
-  const double mn = fmax(a.m, ceil(t));
-  a.s = ldexp(a.s, (int)fmax(a.m - mn, -2100.0));
-  a.m = mn;
-  a.s += exp2(t - (mn == -INFINITY ? 0.0 : mn));
-}
+// (TabAcc, tab_add, tab_add_noop: tpe_tab_add.hpp)
 __device__ __forceinline__ void tab_merge(TabAcc &a, const TabAcc &b) {
   const double M = fmax(a.m, b.m);
   const double ms = M == -INFINITY ? 0.0 : M;
@@ -849,10 +842,80 @@ __device__ __forceinline__ TabAcc tab_wave_sum(TabAcc a) {
   return a;
 }
 
-__global__ __launch_bounds__(kTabThreads) void k_table_build(
+// The lean form's certificate terms, once per (slot, component) (k_table_terms;
+// Switches::table_lean): the panel loop of k_table_build recomputed them for
+// every panel -- two fp64 divisions and an fp64 log2 per (component, panel).
+// The expressions and their contraction are the ones the compiler makes of
+// k_table_build's source (read from its code: cc = fma(ak mu, mu, x), the
+// scaling by 8 exact), written out so that they cannot fuse differently here.
+struct __attribute__((aligned(32))) TabTerm {
+  double mu;  // y / (2 ak)
+  double cc;  // x + ak mu^2
+  double Ak;  // cc + 8 log2(2 ak / log2 e)
+  double ak;  // -z
+};
+constexpr double kTabL2E = 1.4426950408889634;
+#pragma clang fp contract(off)
+__device__ __forceinline__ TabTerm tab_term(double x, double y, double z) {
+  TabTerm t;
+  t.ak = -z;
+  t.mu = y / (2.0 * t.ak);
+  t.cc = __builtin_fma(t.ak * t.mu, t.mu, x);
+  t.Ak = t.cc + 8.0 * log2(2.0 * t.ak / kTabL2E);
+  return t;
+}
+// the panel's two certificate terms of a component: E's and G's (log2)
+__device__ __forceinline__ void tab_cert_terms(const TabTerm &t, double pl, double ph, double &te,
+                                               double &tg) {
+  const double d = fmax(0.0, fmax(pl - t.mu, t.mu - ph)), df = fmax(t.mu - pl, ph - t.mu);
+  te = __builtin_fma(-((0.5 * t.ak) * d), d, t.Ak);
+  tg = __builtin_fma(-(t.ak * df), df, t.cc);
+}
+#pragma clang fp contract(fast)
+
+// one thread per (component, slot); the slot's first block also leaves the
+// mixture's largest a^2 (k_table_build's own reduction: a maximum, the same
+// bits in any order) in a2s[slot], four loads in flight per thread
+__global__ __launch_bounds__(kTabThreads) void k_table_terms(
+    const tpe_hp *__restrict__ hps, const MixInfo *__restrict__ info,
+    const Coef *__restrict__ coef, int64_t kcap, TabTerm *__restrict__ terms,
+    double *__restrict__ a2s) {
+  const int slot = blockIdx.y, tid = threadIdx.x, k = blockIdx.x * kTabThreads + tid;
+  if (!table_hp(hps[slot >> 1])) return;  // (block-uniform, as the next)
+  const int K = info[slot].K;
+  if (K < 1 || K > kcap) return;
+  const double *__restrict__ cf = reinterpret_cast<const double *>(coef + (int64_t)slot * kcap);
+  if (k < K)
+    terms[(int64_t)slot * kcap + k] =
+        tab_term(cf[coef_off(k, 0)], cf[coef_off(k, 1)], cf[coef_off(k, 2)]);
+  if (blockIdx.x != 0) return;
+  __shared__ double red[4];
+  double a2 = 0.0;
+  for (int k0 = tid; k0 < K; k0 += 4 * kTabThreads) {
+    double z[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = cf[coef_off(min(k0 + j * kTabThreads, K - 1), 2)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a2 = fmax(a2, -z[j]);  // (a clamped index repeats a component)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a2 = fmax(a2, __shfl_xor(a2, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = a2;
+  __syncthreads();
+  if (tid == 0) a2s[slot] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+// (LEAN: the slot's largest a^2 and the certificate's per-component terms
+// come from k_table_terms, and the additions that change no bit are skipped,
+// tab_add_noop; everything else is one code.
+// cert: debug, [2P][kTabMaxPanels][3] = le, lr, lg of every panel built)
+template <bool LEAN>
+__device__ __forceinline__ void table_build_body(
     const tpe_hp *__restrict__ hps, const MixInfo *__restrict__ info,
     const Coef *__restrict__ coef, int64_t kcap, TabHdr *__restrict__ hdr,
-    TabPanel *__restrict__ tab, unsigned long long *__restrict__ census) {
+    TabPanel *__restrict__ tab, unsigned long long *__restrict__ census,
+    const TabTerm *__restrict__ terms, const double *__restrict__ a2s,
+    double *__restrict__ cert_out) {
   const int slot = blockIdx.y, p = blockIdx.x, tid = threadIdx.x;
   const tpe_hp H = hps[slot >> 1];
   if (!table_hp(H)) return;
@@ -867,13 +930,19 @@ __global__ __launch_bounds__(kTabThreads) void k_table_build(
   __shared__ unsigned live_n;
   // the mixture's largest a^2 (its smallest sigma)
   double a2 = 0.0;
-  for (int k = tid; k < K; k += kTabThreads) a2 = fmax(a2, -cf[coef_off(k, 2)]);
+  if constexpr (LEAN) {  // (k_table_terms has reduced it, once per slot)
+    if (tid == 0) live_n = 0u;
+    __syncthreads();
+    a2 = a2s[slot];
+  } else {
+    for (int k = tid; k < K; k += kTabThreads) a2 = fmax(a2, -cf[coef_off(k, 2)]);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a2 = fmax(a2, __shfl_xor(a2, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = a2;
-  if (tid == 0) live_n = 0u;
-  __syncthreads();
-  a2 = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    for (int o = 32; o > 0; o >>= 1) a2 = fmax(a2, __shfl_xor(a2, o, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = a2;
+    if (tid == 0) live_n = 0u;
+    __syncthreads();
+    a2 = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  }
   const double L2E = 1.4426950408889634;
   const double y_lo = H.low - H.prior_mu, y_hi = H.high - H.prior_mu;
   const double sig = sqrt(0.5 * L2E / a2);
@@ -933,12 +1002,36 @@ __global__ __launch_bounds__(kTabThreads) void k_table_build(
   // certificate sums: E = sum c_k sigma_k^-16 exp(-d_k^2 / 4 sigma_k^2) (log2:
   // cc + 8 log2(2 a^2 / log2 e) - a^2 d^2 / 2), G = sum c_k exp(-dfar_k^2 / 2 sigma_k^2)
   TabAcc ce{-INFINITY, 0.0}, cg{-INFINITY, 0.0};
-  for (int k = tid; k < K; k += kTabThreads) {
-    const double x = cf[coef_off(k, 0)], y = cf[coef_off(k, 1)], z = cf[coef_off(k, 2)];
-    const double ak = -z, mu = y / (2.0 * ak), cc = x + ak * mu * mu;
-    const double d = fmax(0.0, fmax(pl - mu, mu - ph)), df = fmax(mu - pl, ph - mu);
-    tab_add(ce, cc + 8.0 * log2(2.0 * ak / L2E) - 0.5 * ak * d * d);
-    tab_add(cg, cc - ak * df * df);
+  if constexpr (LEAN) {
+    // (components are sorted by mean and a wave takes 64 neighbours: far from
+    // the panel the whole wave skips)
+    // Two records in flight per thread; a component takes the additions only
+    // if one of its two terms is no no-op (tab_add on a no-op term changes no
+    // bit either: one slow path for both sums).
+    const TabTerm *__restrict__ tt = terms + (int64_t)slot * kcap;
+    for (int k = tid; k < K; k += 2 * kTabThreads) {
+      const int k1 = k + kTabThreads;
+      const TabTerm t0 = tt[k], t1 = tt[min(k1, K - 1)];
+      double te0, tg0, te1, tg1;
+      tab_cert_terms(t0, pl, ph, te0, tg0);
+      tab_cert_terms(t1, pl, ph, te1, tg1);
+      if (!(tab_add_noop(ce, te0) && tab_add_noop(cg, tg0))) {
+        tab_add(ce, te0);
+        tab_add(cg, tg0);
+      }
+      if (k1 < K && !(tab_add_noop(ce, te1) && tab_add_noop(cg, tg1))) {
+        tab_add(ce, te1);
+        tab_add(cg, tg1);
+      }
+    }
+  } else {
+    for (int k = tid; k < K; k += kTabThreads) {
+      const double x = cf[coef_off(k, 0)], y = cf[coef_off(k, 1)], z = cf[coef_off(k, 2)];
+      const double ak = -z, mu = y / (2.0 * ak), cc = x + ak * mu * mu;
+      const double d = fmax(0.0, fmax(pl - mu, mu - ph)), df = fmax(mu - pl, ph - mu);
+      tab_add(ce, cc + 8.0 * log2(2.0 * ak / L2E) - 0.5 * ak * d * d);
+      tab_add(cg, cc - ak * df * df);
+    }
   }
   ce = tab_wave_sum(ce);
   cg = tab_wave_sum(cg);
@@ -992,6 +1085,31 @@ __global__ __launch_bounds__(kTabThreads) void k_table_build(
   ok = ok && le == le && le < INFINITY && lg > -INFINITY && lg < INFINITY &&
        fmax(le, lr) + 1.0 <= lg - 28.0;
   if (ok) atomicAdd(&hdr[slot].ncert, 1u);
+  if (cert_out) {
+    double *c = cert_out + ((int64_t)slot * kTabMaxPanels + p) * 3;
+    c[0] = le;
+    c[1] = lr;
+    c[2] = lg;
+  }
+}
+
+__global__ __launch_bounds__(kTabThreads) void k_table_build(
+    const tpe_hp *__restrict__ hps, const MixInfo *__restrict__ info,
+    const Coef *__restrict__ coef, int64_t kcap, TabHdr *__restrict__ hdr,
+    TabPanel *__restrict__ tab, unsigned long long *__restrict__ census,
+    double *__restrict__ cert_out) {
+  table_build_body<false>(hps, info, coef, kcap, hdr, tab, census, nullptr, nullptr, cert_out);
+}
+// (six waves per SIMD, k_table_build's occupancy: the kernel lives on loads in
+// flight, and left alone the allocator takes 104 VGPRs -- four waves -- for it)
+__global__ __launch_bounds__(kTabThreads) __attribute__((amdgpu_waves_per_eu(6)))
+void k_table_build_lean(
+    const tpe_hp *__restrict__ hps, const MixInfo *__restrict__ info,
+    const Coef *__restrict__ coef, int64_t kcap, TabHdr *__restrict__ hdr,
+    TabPanel *__restrict__ tab, unsigned long long *__restrict__ census,
+    const TabTerm *__restrict__ terms, const double *__restrict__ a2s,
+    double *__restrict__ cert_out) {
+  table_build_body<true>(hps, info, coef, kcap, hdr, tab, census, terms, a2s, cert_out);
 }
 
 // ---- bound lattice of the table score ("Bound lattice") ----
@@ -1099,14 +1217,26 @@ __global__ __launch_bounds__(kBndThreads) void k_table_bound(
   bound[(int64_t)hp * kBndCells + cell] = ok ? U : INFINITY;
 }
 
+static_assert(sizeof(TabTerm) == kTabTermDoubles * sizeof(double), "terms scratch");
 hipError_t launch_table_build(const tpe_hp *hps, int32_t n_hp, const MixInfo *info,
                               const Coef *coef, int64_t kcap, TabHdr *hdr, TabPanel *tab,
-                              unsigned long long *census, hipStream_t st, double *bound) {
+                              unsigned long long *census, hipStream_t st, double *bound,
+                              double *terms, double *cert) {
   if (n_hp <= 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(hdr, 0, (size_t)2 * n_hp * sizeof(TabHdr), st);
   if (e != hipSuccess) return e;
-  k_table_build<<<dim3(kTabMaxPanels, 2 * n_hp), kTabThreads, 0, st>>>(hps, info, coef, kcap, hdr,
-                                                                       tab, census);
+  const dim3 gb(kTabMaxPanels, 2 * n_hp);
+  if (terms) {  // the lean form (Switches::table_lean)
+    // (the slots' largest a^2 behind the records: table_terms_doubles)
+    TabTerm *tt = reinterpret_cast<TabTerm *>(terms);
+    double *a2s = terms + (int64_t)2 * n_hp * kcap * kTabTermDoubles;
+    k_table_terms<<<dim3((unsigned)((kcap + kTabThreads - 1) / kTabThreads), 2 * n_hp), kTabThreads,
+                    0, st>>>(hps, info, coef, kcap, tt, a2s);
+    k_table_build_lean<<<gb, kTabThreads, 0, st>>>(hps, info, coef, kcap, hdr, tab, census, tt, a2s,
+                                                   cert);
+  } else {
+    k_table_build<<<gb, kTabThreads, 0, st>>>(hps, info, coef, kcap, hdr, tab, census, cert);
+  }
   if (bound)
     k_table_bound<<<dim3(kBndCells / kBndThreads, n_hp), kBndThreads, 0, st>>>(hps, hdr, tab, bound);
   return hipGetLastError();

@@ -195,11 +195,15 @@ struct StepShape {
   // the run length of the integer screened draw (step_screen_run of the
   // process switches): its grid depends on it
   int32_t screen_run = 0;
+  // the lean table path (Switches::table_lean): the build takes a node more
+  // (k_table_terms)
+  bool table_lean = true;
   bool operator==(const StepShape &o) const {
     return n_sug == o.n_sug && n_cand == o.n_cand && cand_begin == o.cand_begin &&
            n_total == o.n_total && below == o.below && fit == o.fit &&
            prune_mode == o.prune_mode && lattice_on == o.lattice_on &&
-           capturing == o.capturing && publish == o.publish && screen_run == o.screen_run;
+           capturing == o.capturing && publish == o.publish && screen_run == o.screen_run &&
+           table_lean == o.table_lean;
   }
 };
 // StepShape::screen_run under the switches: TPE_DRAW_SCREEN_RUN for the integer

@@ -2910,6 +2910,103 @@ __global__ __launch_bounds__(kWaves * 64) void k_table_map_dp(ScoreArgs A) {
   }
 }
 
+// The lean form of k_table_map_dp (Switches::table_lean): the same grid, the
+// same marks, the same per-tile code -- and so the same tab_wmax bytes: a
+// tile's entry is still written by one lane from that tile's candidates
+// alone -- but the block's live tiles go through one list in LDS.  Each wave
+// ballots its 64 marks as before; the eight counts are scanned behind one
+// barrier, the tile numbers written to the list (at most kMapDpTiles entries,
+// in wave order, ascending within a wave), and behind a second barrier wave w
+// takes the entries w, w + 8, ...: no wave has more than one tile over the
+// block's average, where the interleaved marks left the block waiting for
+// its busiest wave.  A wave loads the candidates of its next entry before it
+// scores the current one.  Every return ahead of the barriers -- the compact
+// grid's empty row, the uncertified slot, the inactive hp -- depends on the
+// block's (group, slot, suggestion) alone: block-uniform.
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) void k_table_map_dp_lean(ScoreArgs A) {
+  constexpr int KR = kMapRows, PW = kMapDpTiles / kWaves;
+  static_assert(PW == 64, "a wave's tile mask: one entry per lane");
+  __shared__ int wcnt[kWaves];
+  __shared__ int live[kMapDpTiles];
+  const int b = blockIdx.x;
+  int g = 0, b0 = 0;  // the block's group and that group's first block
+  for (; g + 1 < A.n_groups; ++g) {
+    const int nb = table_map_dp_blocks(A, g);
+    if (b < b0 + nb) break;
+    b0 += nb;
+  }
+  const int ntw = A.grp_tiles[g] * kWaves, nsb = (ntw + kMapDpTiles - 1) / kMapDpTiles;
+  const int local = b - b0;
+  int slot = A.grp_slot0[g] + local / nsb;
+  const int s = blockIdx.y;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], local / nsb);
+    if (slot < 0) return;  // (block-uniform)
+  }
+  const int hp = A.level_hps[slot];
+  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
+  if (!(tab_valid(A.tab_hdr[sb]) && tab_valid(A.tab_hdr[sa]))) return;  // (block-uniform)
+  if (!(A.force_active || A.compact ||
+        hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent, A.cond_branch)))
+    return;  // (block-uniform)
+  const bool logn = A.grp_kind[g] == KIND_LSE_LW;
+  const double mu = A.hps[hp].prior_mu;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  double *__restrict__ wmax = A.tab_wmax + ((int64_t)s * A.n_hp + hp) * A.pstride * kWaves;
+  // (k_table_map_dp's marks: lane j of wave w reads wave tile wt0 + 8 j)
+  const int wt0 = (local % nsb) * kMapDpTiles + wave;
+  const int wl = wt0 + kWaves * lane;
+  const bool in = wl < ntw;
+  const bool drop = in && (int64_t)wl * (64 * KR) < A.n_cand && wmax[wl] == -INFINITY;
+  const bool run = in && !drop;
+  const uint64_t todo = __ballot(run);
+  if constexpr (CENSUS) {
+    uint64_t dr = __ballot(drop);
+    while (dr) {  // (wave-uniform)
+      const int wt = wt0 + kWaves * (int)__builtin_ctzll(dr);
+      dr &= dr - 1;
+      if (lane == 0) {
+        const unsigned long long c =
+            (unsigned long long)min<int64_t>(64 * KR, A.n_cand - (int64_t)wt * (64 * KR)) *
+            (unsigned long long)(A.info[sb].K + A.info[sa].K);
+        atomicAdd(A.census + 3, c);
+        atomicAdd(A.census + 12, c);
+      }
+    }
+  }
+  if (lane == 0) wcnt[wave] = __popcll(todo);
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const int c = wcnt[w];
+    before += w < wave ? c : 0;
+    total += c;
+  }
+  if (run) live[before + __popcll(todo & (((uint64_t)1 << lane) - 1))] = wl;
+  __syncthreads();
+  total = __builtin_amdgcn_readfirstlane(total);
+  if (wave >= total) return;
+  int wt = __builtin_amdgcn_readfirstlane(live[wave]);
+  double x[KR];
+  table_wave_load(A, s, slot, logn, wt, x);
+  for (int e = wave; e < total; e += kWaves) {  // (wave-uniform)
+    const bool more = e + kWaves < total;
+    const int wn = more ? __builtin_amdgcn_readfirstlane(live[e + kWaves]) : wt;
+    double xn[KR];
+    if (more) table_wave_load(A, s, slot, logn, wn, xn);
+    const double best = table_wave_tile<CENSUS, true>(A, s, hp, logn, wt, mu, x);
+    if (lane == 0) wmax[wt] = best;
+    if (more) {
+#pragma unroll
+      for (int r = 0; r < KR; ++r) x[r] = xn[r];
+    }
+    wt = wn;
+  }
+}
+
 // Ahead of the table pass of a tab_on 1 launch with the prefilter: one block
 // per (row, suggestion), k_tie_gather's row -> slot mapping; slots that are
 // inactive or without two certified tables need nothing (their map blocks
@@ -3127,6 +3224,155 @@ __global__ __launch_bounds__(kGatherThreads) void k_tie_gather(ScoreArgs A) {
     // (never: the wave holding tab_max is hot.  Were the list empty no block
     // of the direct pass would run, so the record is left here)
     if (base == 0 && !A.accumulate) A.results[sh] = Partial{NAN, NAN, -1, 1, 0};
+  }
+}
+// The lean form of k_tie_gather (Switches::table_lean): the same records,
+// tab_max, lists and counts; the inactive and the uncertified branches are that
+// kernel's.  Wave w owns a contiguous span of whole 64-entry rows of the
+// slot's wave scores and reads it eight rows at a time: the max pass; a sweep
+// that counts the span's hot entries (ballot + popcount, no barrier); one scan
+// over the 16 totals behind one barrier; and, where the span holds a hot entry
+// at all, a second sweep -- an L2 hit -- that writes list[entries of the waves
+// before + hot entries before in the span + rank in the row]: the same
+// ascending list, from the same predicate.
+__global__ __launch_bounds__(kGatherThreads) void k_tie_gather_lean(ScoreArgs A) {
+  constexpr int NW = kGatherThreads / 64;
+  constexpr int WC = 64 * tile_rows(KIND_LSE_GW);  // candidates per wave tile
+  static_assert(tile_rows(KIND_LSE_GW) == tile_rows(KIND_LSE_LW), "one wave-tile shape");
+  __shared__ double red_s[NW];
+  __shared__ int red_n[NW];
+  __shared__ int wsum[NW];
+  const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int row = blockIdx.x;
+  const int g = row_group(A, row);
+  const int nt = A.grp_tiles[g];
+  int slot = A.grp_slot0[g] + row;
+  if (A.compact) {
+    if (row == 0 && tid < 64) {  // (mark_inactive, with the empty lists)
+      Partial *res = A.results + (int64_t)s * A.n_hp;
+      for (int i = tid; i < A.grp_slots[g]; i += 64) {
+        const int hp = A.level_hps[A.grp_slot0[g] + i];
+        if (!hp_active(A.hps[hp], res, A.cond_parent, A.cond_branch)) {
+          res[hp] = Partial{NAN, NAN, -1, 0, 0};
+          A.tie_cnt[(int64_t)s * A.n_hp + hp] = 0;
+        }
+      }
+    }
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], row);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  const int64_t sh = (int64_t)s * A.n_hp + hp;
+  const bool act = A.force_active || A.compact ||
+                   hp_active(A.hps[hp], A.results + (int64_t)s * A.n_hp, A.cond_parent,
+                             A.cond_branch);
+  if (!act) {
+    if (tid == 0) {
+      A.results[sh] = Partial{NAN, NAN, -1, 0, 0};
+      A.tie_cnt[sh] = 0;
+    }
+    return;
+  }
+  const int ntw = nt * kWaves;  // the slot's wave tiles (<= pstride * kWaves)
+  int32_t *list = A.tie_list + sh * A.pstride * kWaves;
+  if (!(tab_valid(A.tab_hdr[2 * (int64_t)hp]) && tab_valid(A.tab_hdr[2 * (int64_t)hp + 1]))) {
+    // entry 8 j + w: wave w of tile j (score_tile's mapping)
+    const int SBB = (1 << A.sort_log2) / tile_cands(KIND_LSE_GW);
+    for (int e = tid; e < ntw; e += kGatherThreads) {
+      const int j = e / kWaves, w = e % kWaves;
+      const int sb = j / SBB, q = j % SBB;
+      const int nbs = min(SBB, nt - sb * SBB);
+      list[e] = sb * SBB * kWaves + q + nbs * w;
+    }
+    if (tid == 0) A.tie_cnt[sh] = ntw;
+    return;
+  }
+  const double *wm = A.tab_wmax + sh * A.pstride * kWaves;
+  const int nrec = (int)min<int64_t>(ntw, (A.n_cand + WC - 1) / WC);  // waves holding a record
+  double m = -INFINITY;
+  int nan = 0;
+  // (the max pass over the wave's span of whole rows, GB rows in flight:
+  // k_tie_gather's one-load loop waits out a memory latency per 1024 entries.
+  // A maximum and an "any NaN": the same bits in any order)
+  constexpr int GB = 8;
+  const int nrow = (ntw + 63) / 64, rpw = (nrow + NW - 1) / NW;
+  const int r0 = min(wave * rpw, nrow), r1 = min(r0 + rpw, nrow);  // (wave-uniform)
+  // entries r * 64 + lane of GB rows from row r on (past `lim`: `fill`)
+  auto load_rows = [&](int r, int lim, double fill, double (&v)[GB]) {
+#pragma unroll
+    for (int j = 0; j < GB; ++j) {
+      const int i = (r + j) * 64 + lane;
+      const double x = wm[min(i, lim - 1)];
+      v[j] = (r + j < r1 && i < lim) ? x : fill;
+    }
+  };
+  if (nrec > 0) {
+    for (int r = r0; r < r1; r += GB) {
+      double v[GB];
+      load_rows(r, nrec, -INFINITY, v);
+#pragma unroll
+      for (int j = 0; j < GB; ++j) {
+        nan |= v[j] != v[j];
+        m = fmax(m, v[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m = fmax(m, __shfl_xor(m, o, 64));
+    nan |= __shfl_xor(nan, o, 64);
+  }
+  if (lane == 0) { red_s[wave] = m; red_n[wave] = nan; }
+  __syncthreads();
+  m = red_s[0];
+  nan = red_n[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) { m = fmax(m, red_s[w]); nan |= red_n[w]; }
+  const double tm = (nan || nrec <= 0) ? NAN : m;
+  if (tid == 0) A.tab_max[sh] = tm;
+  const double wthr = tm - A.tab_tie * fmax(1.0, fabs(tm));
+  // (tab_pref 2: a wave tile the draw dropped holds nothing -- never listed,
+  // whatever tab_max is; with a finite tab_max -inf < wthr says so already)
+  const bool dp = A.tab_pref == 2;
+  int32_t *__restrict__ lw = list;
+  // (k_tie_gather's predicate on entry i of value v)
+  auto hot_of = [&](int i, double v) {
+    return i < ntw && !(v < wthr) && !(dp && i < nrec && v == -INFINITY);
+  };
+  int cnt = 0;
+  for (int r = r0; r < r1; r += GB) {  // (ntw >= 1: the group has tiles)
+    double v[GB];
+    load_rows(r, ntw, 0.0, v);
+#pragma unroll
+    for (int j = 0; j < GB; ++j)
+      cnt += __popcll(__ballot(r + j < r1 && hot_of((r + j) * 64 + lane, v[j])));
+  }
+  if (lane == 0) wsum[wave] = cnt;
+  __syncthreads();
+  int run = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const int c = wsum[w];
+    run += w < wave ? c : 0;
+    total += c;
+  }
+  if (cnt) {  // (wave-uniform; the list is almost empty)
+    for (int r = r0; r < r1; r += GB) {
+      double v[GB];
+      load_rows(r, ntw, 0.0, v);
+#pragma unroll
+      for (int j = 0; j < GB; ++j) {
+        const int i = (r + j) * 64 + lane;
+        const bool hot = r + j < r1 && hot_of(i, v[j]);
+        const uint64_t bal = __ballot(hot);
+        if (hot) lw[run + __popcll(bal & (((uint64_t)1 << lane) - 1))] = i;
+        run += __popcll(bal);
+      }
+    }
+  }
+  if (tid == 0) {
+    A.tie_cnt[sh] = total;
+    if (total == 0 && !A.accumulate) A.results[sh] = Partial{NAN, NAN, -1, 1, 0};
   }
 }
 // the one-row wave tiles (KIND_LSE_GW1 / LW1) in a kernel of their own: the
@@ -3399,6 +3645,9 @@ constexpr int kTieBlocksPerCu = 16;
 // tab_eval -- k_table_map and k_score_table<., false, true> -- unless off, which
 // takes the per-lane kernels k_score_table<., true> and k_score_table<.>.
 static bool table_scalar_on() { return switches().table_scalar; }
+// ... and the lean forms of the map behind the pruning draw and of the gather
+// (Switches::table_lean, A/B): off launches k_table_map_dp and k_tie_gather
+static bool table_lean_on() { return switches().table_lean; }
 
 // one launch of a single class's groups
 static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStream_t st) {
@@ -3450,8 +3699,13 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
         int32_t mb = 0;
         for (int i = 0; i < a.n_groups; ++i) mb += table_map_dp_blocks(a, i);
         const dim3 gm((unsigned)mb, a.n_suggest);
-        if (a.census) k_table_map_dp<true><<<gm, kWaves * 64, 0, st>>>(a);
-        else k_table_map_dp<false><<<gm, kWaves * 64, 0, st>>>(a);
+        if (table_lean_on()) {
+          if (a.census) k_table_map_dp_lean<true><<<gm, kWaves * 64, 0, st>>>(a);
+          else k_table_map_dp_lean<false><<<gm, kWaves * 64, 0, st>>>(a);
+        } else {
+          if (a.census) k_table_map_dp<true><<<gm, kWaves * 64, 0, st>>>(a);
+          else k_table_map_dp<false><<<gm, kWaves * 64, 0, st>>>(a);
+        }
       } else if (table_scalar_on()) {
         int32_t mb = 0;
         for (int i = 0; i < a.n_groups; ++i) mb += table_map_blocks(a, i);
@@ -3462,7 +3716,10 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
         if (a.census) k_score_table<true, true><<<g, kWaves * 64, 0, st>>>(a);
         else k_score_table<false, true><<<g, kWaves * 64, 0, st>>>(a);
       }
-      k_tie_gather<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
+      if (table_lean_on())
+        k_tie_gather_lean<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
+      else
+        k_tie_gather<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
       // persistent blocks per slot: ~kTieBlocksPerCu blocks per CU over
       // the launch's (row, suggestion) pairs, so that a single all-hot slot
       // still fills the chip; never more than the slot has tiles

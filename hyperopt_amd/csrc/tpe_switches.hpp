@@ -32,6 +32,11 @@ struct Switches {
   bool draw_screen_int;
   bool table_prefilter;  // wave tiles a certified bound rules out are not table-scored
   bool table_scalar;  // the scalar-panel table kernels; 0: the per-lane ones
+  // the lean table path: per-component certificate terms once per slot and no
+  // no-op additions in the build, a block-wide live-tile list in the map behind
+  // the pruning draw, a one-scan gather; 0: k_table_build, k_table_map_dp and
+  // k_tie_gather as they were (the same bytes everywhere)
+  bool table_lean;
   // value-bucketed, pruned log-sum-exp slots on small draws: opt-in.  Measured
   // at config 2 (4096 candidates): the skip drops 80 % of the pairs and k_score
   // from 33 to 23 us, but the extra k_bucket launch costs more (70 -> 78 us)
@@ -119,6 +124,7 @@ inline const SwitchDef *switch_table(int *n) {
       {"TPE_DRAW_SCREEN_INT", R::OffIfNonEmptyZero, 1, &S::draw_screen_int, nullptr, 0, 0},
       {"TPE_TABLE_PREFILTER", R::OffIfNonEmptyZero, 1, &S::table_prefilter, nullptr, 0, 0},
       {"TPE_TABLE_SCALAR", R::OffIfNonEmptyZero, 1, &S::table_scalar, nullptr, 0, 0},
+      {"TPE_TABLE_LEAN", R::OffIfNonEmptyZero, 1, &S::table_lean, nullptr, 0, 0},
       {"TPE_SMALL_SORT", R::OnIfNonZero, 0, &S::small_sort, nullptr, 0, 0},
       {"TPE_SIDE_STREAMS", R::OnIfSet, 0, &S::side_streams, nullptr, 0, 0},
       {"TPE_GRAPH", R::OnIfSet, 0, &S::graph, nullptr, 0, 0},

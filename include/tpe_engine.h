@@ -641,6 +641,31 @@ int tpe_plan_tab_wmax(tpe_plan_t p, int32_t n_suggest, double *out);
  * TPE_E_INVALID when the hp takes no table, either side's table is not
  * certified or the prefilter is off (no lattice).  Synchronizes the device.  */
 int tpe_plan_tab_bound(tpe_plan_t p, int32_t hp, double *out);
+/* Debug: the Chebyshev table of (hp, side) -- side 0 the below mixture, 1 the
+ * above one -- as the last fit left it: *y_lo and *inv_w of its header,
+ * *ncert its certified panels (the table is used when ncert equals the panel
+ * count) and panels[i], i < P, the panels as raw 144-byte records (16
+ * coefficients, the exponent M, one unused double).  Any pointer may be NULL;
+ * panels holds up to 64 records.  Builds the tables of the current fit if no
+ * launch has yet.  Returns P (0: no table), or a negative status.
+ * Synchronizes the device.                                                  */
+int tpe_plan_tab_panels(tpe_plan_t p, int32_t hp, int32_t side, double *y_lo, double *inv_w,
+                        int32_t *ncert, void *panels);
+/* Debug: out[3 i + ...] = le, lr, lg of panel i < P of (hp, side): the log2 of
+ * the interpolation bound, of the rounding bound and of the lower bound of the
+ * mixture on the panel -- the panel is certified when max(le, lr) + 1 <= lg -
+ * 28 (and everything is finite) -- as the last build computed them.  The first
+ * call allocates the record and builds the tables again; later builds fill it
+ * as they go.  out may be NULL.  Returns P, or a negative status.
+ * Synchronizes the device.                                                  */
+int tpe_plan_tab_cert(tpe_plan_t p, int32_t hp, int32_t side, double *out);
+/* Debug: out[i], i < n, the wave tiles of (suggestion s, hp) the direct pass
+ * of the plan's last scoring launch that took the tables was given, in list
+ * order; n is that launch's tpe_plan_tie_counts entry (0 where it is -1).
+ * out may be NULL (n alone); it holds up to the W of tpe_plan_tab_wmax
+ * entries.  Adds no launch; synchronizes the device.  Returns n, or a
+ * negative status.                                                          */
+int tpe_plan_tie_list(tpe_plan_t p, int32_t s, int32_t hp, int32_t *out);
 /* Debug: out[(s * n_hp + hp) * 18 + ...] = y_lo, y_hi, lo[8], hi[8], s <
  * n_suggest (at most the last call's): the hot intervals of hp -- closed
  * intervals [lo[i], hi[i]] of the centred fitted-domain value, an unused one
