@@ -53,6 +53,7 @@ EXPORTS = (
     'tpe_plan_group_score_points', 'tpe_plan_group_sides', 'tpe_plan_group_sample_points',
     'tpe_plan_group_batch_points',
     'tpe_plan_set_objectives', 'tpe_plan_pareto_get', 'tpe_plan_pareto_shape',
+    'tpe_plan_set_hv', 'tpe_plan_hv_get',
 )
 
 BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
@@ -188,6 +189,8 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_set_objectives': (C.c_int, [vp, vp, i32, i64, i64, i64, i32, vp]),
             'tpe_plan_pareto_get': (C.c_int, [vp, vp, vp, vp, i64]),
             'tpe_plan_pareto_shape': (C.c_int, [vp, i64, i32, i64, C.POINTER(i64)]),
+            'tpe_plan_set_hv': (C.c_int, [vp, i32, vp, i32, i32, i32, C.c_uint64, i32]),
+            'tpe_plan_hv_get': (C.c_int, [vp, vp, vp, vp, C.POINTER(i32), i32]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -584,6 +587,49 @@ class Plan(object):
             e.check(e.lib.tpe_plan_pareto_shape(self.p, int(n), int(n_obj), int(force_splits),
                                                 out))
         return tuple(int(v) for v in out)
+
+    # ---- hypervolume subset selection inside the front
+    def set_hv(self, ref, n_obj=None, n_pick=32, n_samples=1024, seed=0, method=0):
+        """The setting the next ``set_objectives`` reads (tpe_plan_set_hv):
+        ``ref`` None turns the mode off; a sequence of ``n_obj`` (default its
+        length) finite floats is the reference point of the greedy hypervolume
+        subset selection inside the Pareto front, ``n_pick`` rounds,
+        ``n_samples`` Monte-Carlo samples per row from the Philox stream of
+        ``seed``; ``method`` 0 auto (exact with two objectives), 1 exact,
+        2 Monte-Carlo."""
+        e = self.engine
+        with e.lock:
+            if ref is None:
+                e.check(e.lib.tpe_plan_set_hv(self.p, 0, None, 0, 0, 0, 0, 0))
+                self._hv_on = False
+                return
+            r = np.ascontiguousarray(ref, dtype=np.float64).reshape(-1)
+            m = len(r) if n_obj is None else int(n_obj)
+            if m > len(r):
+                raise ValueError('the reference point has fewer than n_obj entries')
+            e.check(e.lib.tpe_plan_set_hv(self.p, 1, r.ctypes.data, m, int(n_pick),
+                                          int(n_samples), int(seed) & (2 ** 64 - 1),
+                                          int(method)))
+            self._hv_on = True
+
+    def hv_get(self, cap=256):
+        """(picks int32[k], keys float64[k], counts int32[k], R) of the last
+        ranking's selection (tpe_plan_hv_get), k = min(cap, its n_pick): rows in
+        pick order (-1 from round R on), each pick's key as the device holds it
+        (Monte-Carlo: vol * alive, not divided by the sample count) and its
+        alive samples (-1 on the exact path).  R = 0 and empty arrays when that
+        ranking ran no selection."""
+        e = self.engine
+        cap = int(cap)
+        picks = np.full(max(cap, 0), -2, dtype=np.int32)
+        keys = np.zeros(max(cap, 0))
+        counts = np.zeros(max(cap, 0), dtype=np.int32)
+        R = C.c_int32(0)
+        with e.lock:
+            e.check(e.lib.tpe_plan_hv_get(self.p, picks.ctypes.data, keys.ctypes.data,
+                                          counts.ctypes.data, C.byref(R), cap))
+        k = int(np.count_nonzero(picks != -2))      # (entries the engine wrote)
+        return picks[:k], keys[:k], counts[:k], int(R.value)
 
     def fit(self, gamma=0.25, prior_weight=1.0, lf=25, gamma_cap=25, stream=None):
         e = self.engine

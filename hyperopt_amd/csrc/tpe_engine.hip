@@ -19,6 +19,7 @@
 #include "tpe_internal.hpp"
 #include "tpe_level_plan.hpp"
 #include "tpe_pareto_plan.hpp"
+#include "tpe_hv_plan.hpp"
 #include "tpe_switches.hpp"
 
 using namespace tpe;
@@ -236,6 +237,22 @@ struct tpe_plan : PlanShape {
   int64_t obj_n = 0;            // ... and their number
   int64_t pareto_n = -1;        // rows the counts are of (tpe_plan_pareto_get)
   int64_t pareto_force = 0;     // j-splits forced by tpe_plan_pareto_shape (0: the plan's)
+  // hypervolume subset selection inside the front (tpe_plan_set_hv, tpe_hv.hip):
+  // nothing allocated or launched while hv_mode is 0
+  int32_t hv_mode = 0;          // 0 off, 1 on: read by the next tpe_plan_set_objectives
+  int32_t hv_M = 0, hv_n_pick = 0, hv_S = 0, hv_method = 0;
+  uint64_t hv_seed = 0;
+  double hv_ref[TPE_MAX_OBJ] = {};
+  int32_t *d_hv_i32 = nullptr;  // [2][ncap] state, cnt; then picks, counts [kHvMaxPick], R
+  double *d_hv_f64 = nullptr;   // [3][ncap] vol, right, top; then keys [kHvMaxPick]
+  uint64_t *d_hv_alive = nullptr;  // [hv_words_cap][ncap] alive words (Monte-Carlo)
+  int64_t hv_words_cap = 0;
+  double *d_hv_u = nullptr;     // [kHvMaxSamples][TPE_MAX_OBJ] the sample table
+  bool hv_u_ok = false;         // ... holds (hv_u_seed, hv_u_S, hv_u_M)
+  uint64_t hv_u_seed = 0;
+  int32_t hv_u_S = 0, hv_u_M = 0;
+  int32_t hv_last_pick = 0;     // n_pick of the last ranking's selection (0: it ran none)
+  bool hv_last_exact = false;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -307,7 +324,8 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_gcsig, p->d_gtab, p->d_goptlog, p->d_gpick, p->d_goptcdf, p->d_gdraw,
                   p->d_gsides, p->d_gjoint, p->d_bt_ja, p->d_bt_score, p->d_bt_gain,
                   p->d_bt_trace, p->d_bt_gact, p->d_bt_state, p->d_bt_slot, p->d_bt_rec,
-                  p->d_bt_idx, p->d_obj, p->d_pcount};
+                  p->d_bt_idx, p->d_obj, p->d_pcount, p->d_hv_i32, p->d_hv_f64, p->d_hv_alive,
+                  p->d_hv_u};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -1533,6 +1551,111 @@ int tpe_plan_update_history(tpe_plan_t p, int64_t n, int64_t row0, int64_t n_row
   return TPE_OK;
 }
 
+// ---- hypervolume subset selection inside the front
+namespace {
+
+// the rounds and the surrogate column after the counts, on st (no host
+// synchronisation); buffers at the plan's trial capacity on first use
+int hv_rank(tpe_engine *h, tpe_plan *p, int64_t n, int32_t M, const int32_t *by,
+            const int32_t *of, hipStream_t st) {
+  const HvPlan hp = hv_plan(n, M, p->hv_n_pick, p->hv_S, p->hv_method);
+  if (!hp.ok) return fail(h, TPE_E_INVALID, "set_objectives: the hypervolume setting is out of range");
+  const size_t cap = (size_t)p->ncap;
+  if (!p->d_hv_i32) {
+    CKH(dalloc(&p->d_hv_i32, 2 * cap + 2 * (size_t)kHvMaxPick + 1));
+    CKH(dalloc(&p->d_hv_f64, 3 * cap + (size_t)kHvMaxPick));
+  }
+  if (!hp.exact) {
+    if (hp.words > p->hv_words_cap) {
+      CKH(hipStreamSynchronize(st));  // (earlier rounds may still read the old words)
+      dfree(p->d_hv_alive);
+      p->d_hv_alive = nullptr;
+      p->hv_words_cap = 0;
+      CKH(dalloc(&p->d_hv_alive, hp.alive_words(p->ncap)));
+      p->hv_words_cap = hp.words;
+    }
+    if (!p->d_hv_u) CKH(dalloc(&p->d_hv_u, (size_t)kHvMaxSamples * TPE_MAX_OBJ));
+  }
+  HvArgs a{};
+  a.Y = p->d_obj; a.ld = p->ncap; a.n = n; a.M = M;
+  for (int m = 0; m < TPE_MAX_OBJ; ++m) a.ref[m] = p->hv_ref[m];
+  a.n_pick = hp.n_pick; a.S = hp.S; a.exact = hp.exact; a.seed = p->hv_seed;
+  a.make_u = !hp.exact && !(p->hv_u_ok && p->hv_u_seed == p->hv_seed && p->hv_u_S == hp.S &&
+                            p->hv_u_M == M);
+  a.dominated_by = by; a.dominates = of;
+  a.state = p->d_hv_i32; a.cnt = p->d_hv_i32 + cap;
+  a.picks = p->d_hv_i32 + 2 * cap; a.counts = a.picks + kHvMaxPick;
+  a.n_picked = a.counts + kHvMaxPick;
+  a.vol = p->d_hv_f64; a.right = p->d_hv_f64 + cap; a.top = p->d_hv_f64 + 2 * cap;
+  a.keys = p->d_hv_f64 + 3 * cap;
+  a.alive = p->d_hv_alive; a.u = p->d_hv_u;
+  a.losses = p->d_losses;
+  if (a.make_u) p->hv_u_ok = false;
+  CKH(launch_hv_select(a, st));
+  if (!hp.exact) {
+    p->hv_u_ok = true; p->hv_u_seed = p->hv_seed; p->hv_u_S = hp.S; p->hv_u_M = M;
+  }
+  p->hv_last_pick = hp.n_pick;
+  p->hv_last_exact = hp.exact;
+  return TPE_OK;
+}
+
+}  // namespace
+
+int tpe_plan_set_hv(tpe_plan_t p, int32_t mode, const double *ref, int32_t n_obj, int32_t n_pick,
+                    int32_t n_samples, uint64_t seed, int32_t method) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (mode == 0) {
+    p->hv_mode = 0;
+    return TPE_OK;
+  }
+  if (mode != 1) return fail(h, TPE_E_INVALID, "set_hv: mode is 0 or 1");
+  if (n_obj < 1 || n_obj > TPE_MAX_OBJ)
+    return fail(h, TPE_E_INVALID, "set_hv: need 1 <= n_obj <= TPE_MAX_OBJ");
+  if (!ref) return fail(h, TPE_E_INVALID, "set_hv: ref must not be null");
+  for (int m = 0; m < n_obj; ++m)
+    if (!std::isfinite(ref[m])) return fail(h, TPE_E_INVALID, "set_hv: ref must be finite");
+  if (n_pick < 1 || n_pick > kHvMaxPick)
+    return fail(h, TPE_E_INVALID, "set_hv: need 1 <= n_pick <= 256");
+  if (n_samples < kHvMinSamples || n_samples > kHvMaxSamples || n_samples % kHvWord != 0)
+    return fail(h, TPE_E_INVALID, "set_hv: n_samples is a multiple of 64 in [64, 4096]");
+  if (method != kHvAuto && method != kHvExact && method != kHvMc)
+    return fail(h, TPE_E_INVALID, "set_hv: method is 0 (auto), 1 (exact) or 2 (Monte-Carlo)");
+  if (method == kHvExact && n_obj != 2)
+    return fail(h, TPE_E_INVALID, "set_hv: the exact method needs n_obj = 2");
+  p->hv_mode = 1;
+  p->hv_M = n_obj;
+  p->hv_n_pick = n_pick;
+  p->hv_S = n_samples;
+  p->hv_seed = seed;
+  p->hv_method = method;
+  for (int m = 0; m < TPE_MAX_OBJ; ++m) p->hv_ref[m] = m < n_obj ? ref[m] : 0.0;
+  return TPE_OK;
+}
+
+int tpe_plan_hv_get(tpe_plan_t p, int32_t *picks, double *keys, int32_t *counts,
+                    int32_t *n_picked, int32_t cap) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->pareto_n < 0) return fail(h, TPE_E_INVALID, "hv_get: no ranking to read");
+  if (cap < 0) return fail(h, TPE_E_INVALID, "hv_get: cap must not be negative");
+  if (n_picked) *n_picked = 0;
+  if (p->hv_last_pick == 0) return TPE_OK;  // the last ranking ran no selection
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const size_t ncap = (size_t)p->ncap;
+  const size_t k = (size_t)std::min<int32_t>(cap, p->hv_last_pick);
+  const int32_t *d_picks = p->d_hv_i32 + 2 * ncap;
+  if (picks && k) CKH(hipMemcpy(picks, d_picks, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (counts && k)
+    CKH(hipMemcpy(counts, d_picks + kHvMaxPick, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (keys && k) CKH(hipMemcpy(keys, p->d_hv_f64 + 3 * ncap, k * 8, hipMemcpyDeviceToHost));
+  if (n_picked)
+    CKH(hipMemcpy(n_picked, d_picks + 2 * kHvMaxPick, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
 // ---- multi-objective TPE: the loss column from a Pareto ranking
 // Order against the deferred history patch: the patch (if any) is written
 // first, on the same stream, so the surrogate column is the last writer of
@@ -1550,10 +1673,13 @@ int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_
   if (obj0 > 0 && (p->obj_M != n_obj || obj0 > p->obj_n))
     return fail(h, TPE_E_INVALID,
                 "set_objectives: the rows below obj0 are not on the device with this n_obj");
+  if (p->hv_mode && p->hv_M != n_obj)
+    return fail(h, TPE_E_INVALID, "set_objectives: n_obj is not that of tpe_plan_set_hv");
   if (n == 0) {  // an empty history: nothing to rank
     p->obj_M = n_obj;
     p->obj_n = 0;
     p->pareto_n = 0;
+    p->hv_last_pick = 0;
     return TPE_OK;
   }
   const ParetoPlan pp = pareto_plan(n, n_obj, p->pareto_force);
@@ -1579,7 +1705,13 @@ int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_
   p->pareto_n = -1;
   CKH(hipMemsetAsync(p->d_pcount, 0, 2 * (size_t)p->ncap * sizeof(int32_t), st));
   CKH(launch_pareto_count(p->d_obj, p->ncap, n, n_obj, pp.per_split, pp.splits, by, of, st));
-  CKH(launch_pareto_loss(p->d_obj, p->ncap, n, n_obj, by, of, p->d_losses, st));
+  p->hv_last_pick = 0;
+  if (p->hv_mode && n_obj >= 2) {
+    const int rc = hv_rank(h, p, n, n_obj, by, of, st);
+    if (rc) return rc;
+  } else {
+    CKH(launch_pareto_loss(p->d_obj, p->ncap, n, n_obj, by, of, p->d_losses, st));
+  }
   p->pareto_n = n;
   // a new loss column: nothing fitted on the old one stands
   p->last_nb = -1;

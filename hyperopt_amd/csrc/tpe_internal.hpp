@@ -1010,4 +1010,33 @@ hipError_t launch_pareto_loss(const double *Y, int64_t ld, int64_t n, int32_t M,
                               const int32_t *dominated_by, const int32_t *dominates,
                               double *losses, hipStream_t st);
 
+// Greedy hypervolume subset selection inside the Pareto front and the
+// surrogate column that follows from it (tpe_hv.hip; tpe_plan_set_hv; DESIGN
+// 5.18), after launch_pareto_count on the same stream: k_hv_init, per round
+// k_hv_round (from the second on) and k_hv_pick, then k_hv_loss in the place
+// of k_pareto_loss.  Every per-row buffer has the row stride ld.
+struct HvArgs {
+  const double *Y;              // [M][ld]
+  int64_t ld, n;
+  int32_t M;
+  double ref[8];                // the reference point
+  int32_t n_pick, S;
+  bool exact;                   // the M = 2 area gain, otherwise Monte-Carlo
+  uint64_t seed;
+  bool make_u;                  // write the sample table first (Monte-Carlo)
+  const int32_t *dominated_by, *dominates;
+  int32_t *state;               // [ld] the round a row was picked in, < 0 otherwise
+  int32_t *cnt;                 // [ld] alive samples (Monte-Carlo)
+  double *vol;                  // [ld] the box volume; exact: the current gain
+  double *right, *top;          // [ld] the clipped box (exact)
+  uint64_t *alive;              // [S / 64][ld] (Monte-Carlo)
+  double *u;                    // [S / 64][M][64] the sample table (Monte-Carlo)
+  int32_t *picks;               // [n_pick] out: rows in pick order, -1 from the end on
+  double *keys;                 // [n_pick] out: the key of each pick
+  int32_t *counts;              // [n_pick] out: its alive samples (-1: exact)
+  int32_t *n_picked;            // out: R
+  double *losses;               // [ld] out: the surrogate column
+};
+hipError_t launch_hv_select(const HvArgs &a, hipStream_t st);
+
 }  // namespace tpe

@@ -22,7 +22,9 @@ from cached per-document rows.
 With ``objectives=M`` (multi-objective TPE) an objective store ``Y[M][cap]``
 is kept beside the losses, from ``result['objectives']`` of the ok trials, and
 ``push`` has the device rank the history by Pareto dominance
-(``tpe_plan_set_objectives``) instead of sending the losses.
+(``tpe_plan_set_objectives``) instead of sending the losses.  With
+``hypervolume=`` the nondominated rows are ordered by a greedy hypervolume
+subset selection against a reference point (``tpe_plan_set_hv``).
 """
 from __future__ import annotations
 
@@ -52,6 +54,57 @@ def check_objectives(objectives):
         raise ValueError('objectives must be None or an int in [1, %d], got %r'
                          % (MAX_OBJ, objectives))
     return int(objectives)
+
+
+def check_hypervolume(hypervolume, objectives):
+    """``hypervolume=`` checked against the checked ``objectives``: False (off,
+    the default), True (the default reference point, ``default_reference``) or
+    a tuple of M finite floats, the reference point of the hypervolume subset
+    selection inside the Pareto front."""
+    if hypervolume is False:
+        return False
+    if objectives is None:
+        raise ValueError('hypervolume needs objectives=M')
+    if hypervolume is True:
+        return True
+    if isinstance(hypervolume, (str, bytes)):
+        raise ValueError('hypervolume must be False, True or a sequence of %d finite numbers, '
+                         'got %r' % (objectives, hypervolume))
+    try:
+        ref = tuple(hypervolume)
+        ok = len(ref) == objectives and all(
+            isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)
+            for v in ref)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError('hypervolume must be False, True or a sequence of %d finite numbers, '
+                         'got %r' % (objectives, hypervolume))
+    return tuple(float(v) for v in ref)
+
+
+def default_reference(Y):
+    """The default reference point of ``Y[M, n]``: per objective, over the
+    finite values of complete rows (no NaN, no +inf), ``hi + 0.1 (hi - lo)``, or
+    ``hi + 1`` when ``hi == lo``.  None without a complete row."""
+    Y = np.asarray(Y, dtype=np.float64)
+    ok = ~(np.isnan(Y) | (Y == np.inf)).any(axis=0)
+    if not ok.any():
+        return None
+    ref = []
+    for m in range(Y.shape[0]):
+        v = Y[m, ok]
+        v = v[np.isfinite(v)]
+        if len(v) == 0:                 # (every complete row holds -inf here)
+            ref.append(1.0)
+            continue
+        hi, lo = float(v.max()), float(v.min())
+        ref.append(hi + 1.0 if hi == lo else hi + 0.1 * (hi - lo))
+    return tuple(ref)
+
+
+# tpe_plan_set_hv's defaults (include/tpe_engine.h)
+HV_N_PICK, HV_N_SAMPLES, HV_SEED, HV_METHOD = 32, 1024, 0, 0
 
 
 def _objectives_of(doc, M, tid):
@@ -86,6 +139,7 @@ class TrialHistory(object):
         self._cache = {}        # id(doc) -> (doc, tid, vals row, active row)
         self.M = None           # objectives of the last sync (None: the scalar loss)
         self.Y = None           # [M][cap] objective store beside losses (NaN: pending)
+        self.hv = False         # hypervolume= of the last sync: False, True or the reference point
         self._alloc(64)
         self._forget()
 
@@ -130,7 +184,9 @@ class TrialHistory(object):
         self._obj_ok = False    # Y holds the objectives of every row not in _touched
         self._touched = set()   # rows whose document was (re)read since Y was
         self._obj_dirty = 0     # rows of Y >= this differ from the device copy
-        self._dev_mode = None   # what the device loss column holds: None the losses, M a ranking
+        # what the device loss column holds: None the losses, M a ranking, (M, hv) a
+        # ranking with the hypervolume order inside the front
+        self._dev_mode = None
         self._dev = None        # weakref to the plan holding the device copy
         self._plain = True      # rows == visible documents, integer tids ascending
 
@@ -171,13 +227,15 @@ class TrialHistory(object):
         self._touched.add(r)
 
     # -- sync ----------------------------------------------------------------
-    def sync(self, trials, objectives=None):
+    def sync(self, trials, objectives=None, hypervolume=False):
         """Bring the columns up to date with ``trials.trials``.  ``objectives``
         = M: also the objective store ``Y[M][cap]``, from every ok trial's
         ``result['objectives']`` (ValueError naming the tid where an ok trial
         has none, or not M of them); ``push`` then ranks the device history by
-        Pareto dominance instead of by the loss."""
+        Pareto dominance instead of by the loss.  ``hypervolume``: the front
+        is ordered by hypervolume subset selection (``check_hypervolume``)."""
         objectives = check_objectives(objectives)
+        self.hv = check_hypervolume(hypervolume, objectives)
         view = trials.trials
         store = getattr(trials, '_store', None)
         journal = store.journal if store is not None else None
@@ -333,6 +391,16 @@ class TrialHistory(object):
         return (list(self.tids), self.losses[:n].copy(), self.vals[:, :n].copy(),
                 self.active[:, :n].copy())
 
+    def reference(self):
+        """The reference point this sync's ``hypervolume`` means: the given
+        one, the default one of the rows held, or None (off: no setting, or the
+        default without a complete row)."""
+        if self.hv is False or self.M is None:
+            return None
+        if self.hv is True:
+            return default_reference(self.Y[:, :self.n])
+        return self.hv
+
     # -- device copy ------------------------------------------------------------
     def push(self, plan):
         """Copy the rows and losses that changed since the last push into
@@ -353,10 +421,18 @@ class TrialHistory(object):
             # rows (and after a deferred patch of them, tpe_engine.h)
             plan.update_history(self.n, r0, self.vals, self.active, self.cap, self.n,
                                 self.losses)
-            o0 = min(self._obj_dirty, self.n) if self._dev_mode == self.M else 0
+            mode = self.M if self.hv is False else (self.M, self.hv)
+            o0 = min(self._obj_dirty, self.n) if self._dev_mode == mode else 0
+            # the setting goes before the ranking that reads it; a plan that
+            # never saw one is off (Plan._hv_on), and is not told so again
+            ref = self.reference()
+            if ref is not None:
+                plan.set_hv(ref, self.M, HV_N_PICK, HV_N_SAMPLES, HV_SEED, HV_METHOD)
+            elif getattr(plan, '_hv_on', False):
+                plan.set_hv(None)
             plan.set_objectives(self.Y, n=self.n, obj0=o0)
             self._obj_dirty = self.n
-        self._dev_mode = self.M
+        self._dev_mode = self.M if self.M is None or self.hv is False else (self.M, self.hv)
         plan._history_owner = self
         self._dev = weakref.ref(plan)
         self._vals_dirty = self.n

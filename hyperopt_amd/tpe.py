@@ -37,7 +37,7 @@ import numpy as np
 
 from . import _engine as E
 from . import rand, rstream
-from .history import TrialHistory, check_objectives
+from .history import TrialHistory, check_objectives, check_hypervolume, HV_N_SAMPLES
 
 logger = logging.getLogger(__name__)
 
@@ -149,7 +149,8 @@ def suggest(new_ids, domain, trials, seed,
             n_EI_candidates=_default_n_EI_candidates,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
-            rng_stream='philox', startup_stream='numpy', engine=None, objectives=None):
+            rng_stream='philox', startup_stream='numpy', engine=None, objectives=None,
+            hypervolume=False):
     """hyperopt/tpe.py:804-897 on the GPU, one document per id in
     ``new_ids``.  ``linear_forgetting`` is accepted and, as in the reference
     (tpe.py:809), not used: LF is fixed at 25.  The first ``n_startup_jobs``
@@ -165,8 +166,21 @@ def suggest(new_ids, domain, trials, seed,
     which ``fmin`` still needs for its own bookkeeping.  Everything behind
     the split is unchanged; with M = 1 and ``objectives = [loss]`` the
     suggestions are those of ``objectives=None``.  Calls with different
-    ``objectives`` may alternate on one domain and one trials object."""
+    ``objectives`` may alternate on one domain and one trials object.
+
+    ``hypervolume`` (with ``objectives``): the order inside the
+    Pareto front, which decides the good side once the front is larger than
+    the split, becomes a greedy hypervolume subset selection -- the front
+    trial that adds the most hypervolume against a reference point first,
+    then the one that adds the most given the first, ... (``hv_picks``), as in
+    MOTPE.  ``True``: the default reference point, per objective ``hi + 0.1
+    (hi - lo)`` over the finite values of complete trials (``hi + 1`` when
+    they are all equal); a sequence of M finite floats: that reference point;
+    ``False`` (default): the order of DESIGN 5.17.  Anything else, or
+    ``hypervolume`` without ``objectives``, is a ValueError.  With M = 1 the
+    setting is ignored."""
     objectives = check_objectives(objectives)
+    hypervolume = check_hypervolume(hypervolume, objectives)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -175,7 +189,7 @@ def suggest(new_ids, domain, trials, seed,
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
         startup = hist.n < n_startup_jobs
     if startup:
         # the reference's RandomState prior stream (numpy), or device prior
@@ -183,8 +197,8 @@ def suggest(new_ids, domain, trials, seed,
         return rand.suggest(new_ids, domain, trials, seed, rng_stream=startup_stream)
     with st.lock:
         engine = engine or E.default_engine()
-        if hist.M != objectives:    # (another thread's call in between)
-            hist.sync(trials, objectives)
+        if hist.M != objectives or hist.hv != hypervolume:    # (another thread's call in between)
+            hist.sync(trials, objectives, hypervolume)
         plan = st.plan_for(domain, hist.n, engine)
         hist.push(plan)
         seeds = batch_seeds(seed, len(new_ids))
@@ -377,7 +391,7 @@ def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate
 
 def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
                   gamma=_default_gamma, engine=None, return_terms=False, multivariate=False,
-                  objectives=None):
+                  objectives=None, hypervolume=False):
     """What the fitted TPE model thinks of configurations the caller holds.
 
     The history of ``trials`` is synced, pushed and fitted as ``suggest``
@@ -409,15 +423,17 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     terms are 0.0.  Any other value of ``multivariate`` is a ValueError.
 
     ``objectives=M``: the model is fitted on the Pareto ranking of the
-    trials' ``result['objectives']`` (``suggest``)."""
+    trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
+    hypervolume order inside the front (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
+    hypervolume = check_hypervolume(hypervolume, objectives)
     cs = domain.space
     as_dicts = not isinstance(configs, np.ndarray)
     vals, present = config_columns(cs, configs)
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
         if hist.n == 0:
             raise ValueError('score_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
@@ -510,7 +526,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
                       prior_weight=_default_prior_weight,
                       n_startup_jobs=_default_n_startup_jobs,
                       gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False,
-                      objectives=None):
+                      objectives=None, hypervolume=False):
     """``algo=`` for a constrained or discrete search: the next trials are the
     ``len(new_ids)`` configurations of ``pool`` the fitted model scores
     highest (``score_configs``' EI), distinct, ties to the lower pool index,
@@ -524,9 +540,11 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     than ``len(new_ids)`` eligible configurations remain.  ``multivariate``
     (True or 'groups'): the pool is ranked by ``score_configs`` with that
     argument.  ``objectives=M``: the model is fitted on the Pareto ranking of
-    the trials' ``result['objectives']`` (``suggest``)."""
+    the trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with
+    the hypervolume order inside the front (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
+    hypervolume = check_hypervolume(hypervolume, objectives)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -537,7 +555,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     k = len(new_ids)
     with st.lock:
         pl = _pool_for(st, cs, pool)
-        hist = st.history(domain, trials).sync(trials, objectives)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
         if hist.n < n_startup_jobs:
             if pl.m < k:
                 raise ValueError('the pool holds %d configurations, %d asked for' % (pl.m, k))
@@ -566,7 +584,7 @@ STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
 
 def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
                    gamma=_default_gamma, engine=None, begin=0, as_dicts=False,
-                   multivariate=False, objectives=None):
+                   multivariate=False, objectives=None, hypervolume=False):
     """``n`` whole configurations drawn from the fitted model's *below*
     mixtures, each with its joint EI (``score_configs``' total of it).
 
@@ -589,13 +607,15 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     draws the group's hps from it, parents first; the EI is
     ``score_configs(..., multivariate='groups')``'s
     (tpe_plan_group_sample_points).  ``objectives=M``: the model is fitted on
-    the Pareto ranking of the trials' ``result['objectives']`` (``suggest``)."""
+    the Pareto ranking of the trials' ``result['objectives']`` (``suggest``);
+    ``hypervolume``: with the hypervolume order inside the front (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
+    hypervolume = check_hypervolume(hypervolume, objectives)
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
@@ -736,7 +756,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
                   startup_stream='numpy', engine=None, multivariate=False, batch='topk',
-                  objectives=None):
+                  objectives=None, hypervolume=False):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -782,9 +802,11 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     unknown ``batch``.
 
     ``objectives=M``: the model is fitted on the Pareto ranking of the
-    trials' ``result['objectives']`` (``suggest``)."""
+    trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
+    hypervolume order inside the front (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
+    hypervolume = check_hypervolume(hypervolume, objectives)
     if batch not in ('topk', 'pending'):
         raise ValueError("batch must be 'topk' or 'pending', got %r" % (batch,))
     if batch == 'pending' and multivariate != 'groups':
@@ -799,7 +821,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     k = len(new_ids)
     n = int(n_configs)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
         startup = hist.n < n_startup_jobs
     if startup:
         if feasible is None:
@@ -809,8 +831,8 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
     P = len(cs.labels)
     with st.lock:
-        if hist.M != objectives:    # (another thread's call in between)
-            hist.sync(trials, objectives)
+        if hist.M != objectives or hist.hv != hypervolume:    # (another thread's call in between)
+            hist.sync(trials, objectives, hypervolume)
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
         draw = (plan.group_sample_points_device if multivariate == 'groups' else
@@ -853,38 +875,63 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
 # --------------------------------------------------------------------------
 # multi-objective TPE: the Pareto ranking the split reads
 # --------------------------------------------------------------------------
-def _pareto(domain, trials, objectives, engine):
+def _pareto(domain, trials, objectives, engine, hypervolume=False, want_hv=False):
     """(docs, tids, dominated_by, dominates, surrogate) of the synced history,
-    ranked on the device."""
+    ranked on the device; ``want_hv``: and ``Plan.hv_get``'s tuple."""
     objectives = check_objectives(objectives)
     if objectives is None:
         raise ValueError('the Pareto ranking needs objectives=M')
+    hypervolume = check_hypervolume(hypervolume, objectives)
     st = _state(domain)
+    none = (np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0, dtype=np.int32), 0)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
         if hist.n == 0:
-            return [], [], np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
+            out = [], [], np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
+            return out + (none,) if want_hv else out
         plan = st.plan_for(domain, hist.n, engine or E.default_engine())
         hist.push(plan)
-        return (list(hist.docs), list(hist.tids)) + plan.pareto_get(hist.n)
+        out = (list(hist.docs), list(hist.tids)) + plan.pareto_get(hist.n)
+        return out + (plan.hv_get(),) if want_hv else out
 
 
-def pareto_ranks(domain, trials, objectives, engine=None):
+def pareto_ranks(domain, trials, objectives, engine=None, hypervolume=False):
     """(tids, dominated_by, dominates, surrogate) of the history of
     ``trials`` under ``objectives=M``, read back from the device
     (tpe_plan_pareto_get): per trial in tid order the number of complete
     trials that dominate it (0: on the Pareto front), the number it
     dominates, and the surrogate loss ``dominated_by (n + 1) + (n -
     dominates)`` the split ranks by; a trial that is not ok, or has a NaN or
-    +inf objective, is pending: counts 0 and surrogate +inf."""
-    return _pareto(domain, trials, objectives, engine)[1:]
+    +inf objective, is pending: counts 0 and surrogate +inf.  With
+    ``hypervolume`` the surrogate of a front trial is its place in the
+    hypervolume subset selection (``suggest``, ``hv_picks``); the selection's
+    sample seed is fixed, so the ranks are a function of the history alone."""
+    return _pareto(domain, trials, objectives, engine, hypervolume)[1:]
 
 
-def pareto_front(domain, trials, objectives, engine=None):
+def pareto_front(domain, trials, objectives, engine=None, hypervolume=False):
     """The trial documents on the Pareto front of ``result['objectives']``
-    -- complete trials no complete trial dominates -- in tid order."""
-    docs, _, by, _, s = _pareto(domain, trials, objectives, engine)
+    -- complete trials no complete trial dominates -- in tid order
+    (``hypervolume`` orders the front's rows in the split and leaves the front
+    as it is)."""
+    docs, _, by, _, s = _pareto(domain, trials, objectives, engine, hypervolume)
     return [docs[r] for r in np.flatnonzero((by == 0) & np.isfinite(s))]
+
+
+def hv_picks(domain, trials, objectives, hypervolume=True, engine=None):
+    """(tids, gains, alive) of the hypervolume subset selection inside the
+    Pareto front of ``trials`` (tpe_plan_hv_get), in pick order:
+    the tids picked, what each added to the hypervolume given the picks
+    before it -- the exact area with two objectives, the Monte-Carlo estimate
+    ``vol * alive / S`` with more -- and its alive samples (-1: exact).  At most
+    32 picks; fewer when the front inside the reference point is smaller;
+    none with ``objectives=1``, ``hypervolume=False`` or no complete trial."""
+    _, tids, _, _, _, (picks, keys, counts, R) = _pareto(domain, trials, objectives, engine,
+                                                       hypervolume, want_hv=True)
+    picks, keys, counts = picks[:R], keys[:R].copy(), counts[:R]
+    mc = counts >= 0
+    keys[mc] = keys[mc] / float(HV_N_SAMPLES)
+    return [tids[int(r)] for r in picks], keys, counts
 
 
 # --------------------------------------------------------------------------

@@ -566,6 +566,49 @@ int tpe_plan_pareto_get(tpe_plan_t p, int32_t *dominated_by, int32_t *dominates,
 int tpe_plan_pareto_shape(tpe_plan_t p, int64_t n, int32_t n_obj, int64_t force_splits,
                           int64_t *out);
 
+/* ---- hypervolume subset selection inside the Pareto front ----
+ * Off by default.  With mode 1 the next tpe_plan_set_objectives (and every
+ * later one, until mode 0) orders the nondominated rows by a greedy
+ * hypervolume subset selection against the reference point ref[n_obj] after
+ * the counts, and writes the loss column from it.  A row takes part when it is
+ * complete, has dominated_by = 0, is finite in every objective and has
+ * w[m] = ref[m] - y[m] > 0 for every m; vol = w[0] * ... * w[n_obj - 1].  In
+ * round t = 0 .. n_pick - 1 the row of largest key is pick t (ties to the
+ * lower row); a key that is not > 0 ends the selection with R = t picks.
+ *   exact (two objectives): key = (right - y[0]) * (top - y[1]), right the
+ *     smallest y_p[0] > y[0] over the picks p (ref[0] without one), top the
+ *     same in objective 1; 0 once a pick equals the row in both objectives.
+ *   Monte-Carlo: key = vol * alive, alive the number of the row's n_samples
+ *     samples z[m] = y[m] + u[s][m] * w[m] with no pick p below them
+ *     (y_p[m] <= z[m] for every m); u[s][m] is uniform m % 4 of the Philox
+ *     draw (seed, counter s, stream 0x60000000, block pair m / 4), the same
+ *     table for every row.  No division by n_samples.
+ * Picked rows and rows with a zero count have key 0.  The loss column becomes
+ *   s[i] = dominated_by[i] (n + 1) + sec[i]
+ * with sec = t for pick t, max(R, n - dominates[i]) for every other row with
+ * dominated_by = 0, n - dominates[i] elsewhere; +inf for a pending row.  sec
+ * stays in [0, n]: a dominates b still implies s[a] < s[b].  Every value is a
+ * function of (Y, ref, n_pick, n_samples, seed, method) alone: products and
+ * differences as written, no fused multiply-add, keys compared as integers.
+ * method: 0 exact with two objectives and Monte-Carlo with more, 1 exact,
+ * 2 Monte-Carlo.  With n_obj = 1 the setting is accepted and ignored (the
+ * ranking is total).  TPE_E_INVALID: a mode other than 0 / 1, a null or
+ * non-finite ref, n_obj outside [1, TPE_MAX_OBJ], n_pick outside [1, 256],
+ * n_samples not a multiple of 64 in [64, 4096], an unknown method, method 1
+ * with n_obj != 2; a tpe_plan_set_objectives with another n_obj fails with
+ * TPE_E_INVALID while the mode is on.  Mode 0 ignores the other arguments,
+ * adds no launch and allocates nothing.                                      */
+int tpe_plan_set_hv(tpe_plan_t p, int32_t mode, const double *ref, int32_t n_obj,
+                    int32_t n_pick, int32_t n_samples, uint64_t seed, int32_t method);
+
+/* Host copies of the last ranking's selection: the first min(cap, n_pick)
+ * entries of picks (row indices in pick order, -1 from round R on), keys (the
+ * key of each pick; 0 from round R on) and counts (the pick's alive samples;
+ * -1 on the exact path and from round R on), each may be NULL; *n_picked = R,
+ * 0 when that ranking ran no selection.  Waits for the device.              */
+int tpe_plan_hv_get(tpe_plan_t p, int32_t *picks, double *keys, int32_t *counts,
+                    int32_t *n_picked, int32_t cap);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,

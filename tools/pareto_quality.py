@@ -14,9 +14,17 @@ inside it):
         f2 = g (1 - (f1 / g)^2); the front is g = 1, f2 = 1 - f1^2.  Here any
         point with x0 near 0 is nondominated however large its g, so the rank
         alone does not push g down: the case hypervolume-based selection
-        inside the front (left out) exists for.
+        inside the front (``--hv``) exists for.
 The first problem's numbers are the README's.  Not a pass condition.
-usage: python tools/pareto_quality.py [--problems ff zdt2] [--seeds N] [--evals N] [--out FILE]
+
+``--hv`` adds the two arms of the hypervolume subset selection inside the
+front after the three above and writes to
+profiles/pareto_hv_quality.txt instead:
+  hv-auto  ``tpe.suggest(objectives=2, hypervolume=True)`` (the default
+           reference point, from the history),
+  hv-ref   ``tpe.suggest(objectives=2, hypervolume=(1.1, 1.1))``.
+usage: python tools/pareto_quality.py [--hv] [--problems ff zdt2] [--seeds N] [--evals N]
+                                      [--out FILE]
 """
 import argparse
 import functools
@@ -69,14 +77,22 @@ def main():
     ap.add_argument('--problems', nargs='+', default=['ff', 'zdt2'], choices=sorted(PROBLEMS))
     ap.add_argument('--seeds', type=int, default=5)
     ap.add_argument('--evals', type=int, default=200)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'pareto_quality.txt'))
+    ap.add_argument('--hv', action='store_true',
+                    help='also the two hypervolume= arms; to profiles/pareto_hv_quality.txt')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles',
+                                'pareto_hv_quality.txt' if args.hv else 'pareto_quality.txt')
     import numpy as np
     from hyperopt_amd import fmin, hp, rand, tpe, Trials
 
     algos = [('mo-tpe', functools.partial(tpe.suggest, objectives=2)),
              ('sum-tpe', tpe.suggest),
              ('random', rand.suggest)]
+    if args.hv:
+        algos += [('hv-auto', functools.partial(tpe.suggest, objectives=2, hypervolume=True)),
+                  ('hv-ref', functools.partial(tpe.suggest, objectives=2, hypervolume=REF))]
     out = open(args.out, 'w') if args.out else None
 
     def say(s):
