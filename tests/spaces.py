@@ -55,6 +55,18 @@ def cond_space(hp, n_branch=3):
     return {'top': hp.choice('top', branches), 'aa': hp.uniform('aa', 0, 1)}
 
 
+def fit_tiers_space(hp):
+    # cond_space's three sparse branches plus root hps of the fit paths they
+    # lack: a categorical past 64 bins (sorted, not counted), heavily tied
+    # quantized observations, and a pchoice (tests/fit_tier_cases.py)
+    s = cond_space(hp, 3)
+    s['r300'] = hp.randint('r300', 300)
+    s['qu'] = hp.quniform('qu', 0, 100, 1)
+    s['qn'] = hp.qnormal('qn', 0, 10, 2)
+    s['pk'] = hp.pchoice('pk', [(.1, 0), (.6, 1), (.3, 2)])
+    return s
+
+
 def cfg3_space(hp, n_branch=7):
     # config 3: exactly 50 hps: top + 7 x (3 loguniform + 3 qloguniform + 1 choice)
     branches = []

@@ -221,8 +221,9 @@ def test_mixtures_bit_exact(runs, name):
     sorted means must pair with the oracle's within one ulp of each -- the
     same observations on each side, in the same order, the prior at the same
     place and exact -- and the oracle's fit of the device's own logarithms
-    (taken from those means) must then equal the device's bit for bit."""
-    from oracle import tpe_oracle as O
+    (taken from those means) must then equal the device's bit for bit
+    (fit_oracle.assert_mixture_bit_exact)."""
+    from fit_oracle import assert_mixture_bit_exact
     s = TE.FIT_SETS[name]
     r = runs['three/' + name]
     for lab in LABELS:
@@ -232,24 +233,8 @@ def test_mixtures_bit_exact(runs, name):
             w, mu, sg = r['plan'].mixture(i, side)
             assert w.size == (s['K_below'], s['K_above'])[side], (name, lab, side, w.size)
             msg = '%s %s side %d ' % (name, lab, side)
-            if fk == 'lgmm':
-                with np.errstate(all='ignore'):
-                    _, mu_o, _, order, pos = O.parzen_fit(tobs[side], s['prior_weight'], pm, ps,
-                                                          lf=s['lf'], kind='stable',
-                                                          return_order=True)
-                off = np.abs(mu - mu_o)
-                assert (off <= np.spacing(np.abs(mu_o))).all(), msg + 'log(x) beyond an ulp'
-                assert mu[pos] == pm
-                print('%s: %d of %d means differ from numpy\'s log in the last bit'
-                      % (msg, int((off > 0).sum()), mu.size))
-                dev = np.array(tobs[side], dtype=np.float64)
-                if dev.size:
-                    dev[np.arange(dev.size) if order is None else order] = np.delete(mu, pos)
-                with np.errstate(all='ignore'):
-                    ref = O.parzen_fit(dev, s['prior_weight'], pm, ps, lf=s['lf'], kind='stable')
-            np.testing.assert_array_equal(mu, ref[1], err_msg=msg + 'mu')
-            np.testing.assert_array_equal(sg, ref[2], err_msg=msg + 'sigma')
-            np.testing.assert_array_equal(w, ref[0], err_msg=msg + 'w')
+            assert_mixture_bit_exact((w, mu, sg), tobs[side], s['prior_weight'], pm, ps, s['lf'],
+                                     fk == 'lgmm', msg, ref=ref)
 
 
 # ---- 2. the tables alone

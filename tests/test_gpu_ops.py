@@ -191,9 +191,12 @@ def test_categorical_sampler(eng):
     assert np.allclose(freq, p, atol=5e-3)
 
 
-# ---- fit tiers of tpe_fit.hip: tiny (<= 64, one wave), LDS radix sort
-# (<= 10240), global radix sort (> 10240); mixtures in LDS (K <= 4097) or HBM
-@pytest.mark.parametrize('n', [2, 63, 64, 65, 1000, 4096, 4097, 10240, 10241, 30000])
+# ---- fit tiers of tpe_fit.hip: tiny (<= 64, one wave), merge sort in the
+# all-LDS kernel (<= kMergeMax = 1024), LDS sorts (<= kSortCap = 10000), global
+# radix sort (> 10000); the gather prefetched (<= kPreN = 12288) or in chunks;
+# mixtures in LDS (K <= kMixLds = 4097) or HBM
+@pytest.mark.parametrize('n', [2, 63, 64, 65, 1000, 1024, 1025, 4096, 4097, 10000, 10001, 10240,
+                               10241, 12288, 12289, 30000])
 @pytest.mark.parametrize('ties', [False, True])
 def test_parzen_sort_tiers_bit_exact(eng, n, ties):
     rng = np.random.RandomState(n + ties)
@@ -230,7 +233,8 @@ def test_parzen_merge_sort_truncated_key_runs(eng, n, cluster):
 
 
 @pytest.mark.parametrize('n,gamma,cap', [(1000, 0.25, 25), (20000, 0.25, 25), (5000, 2.0, 1000),
-                                         (30000, 1.0, 1000), (50, 10.0, 1000)])
+                                         (30000, 1.0, 1000), (50, 10.0, 1000), (10000, 0.25, 25),
+                                         (10001, 0.25, 25), (12289, 100.0, 10001)])
 def test_split_rounds_and_sort_paths(eng, n, gamma, cap):
     rng = np.random.RandomState(n)
     losses = np.round(rng.rand(n), 3)                # ties
@@ -241,7 +245,9 @@ def test_split_rounds_and_sort_paths(eng, n, gamma, cap):
     assert set(np.where(mask)[0].tolist()) == good
 
 
-@pytest.mark.parametrize('n,upper', [(0, 3), (10, 3), (20000, 7), (5000, 300), (3000, 5000)])
+# (the counting fit: upper <= 64 bins and kMergeMax < n <= kSortCap observations)
+@pytest.mark.parametrize('n,upper', [(0, 3), (10, 3), (20000, 7), (5000, 300), (3000, 5000),
+                                     (1025, 64), (5000, 7), (10000, 64), (10001, 64), (5000, 65)])
 def test_categorical_posterior_sizes(eng, n, upper):
     rng = np.random.RandomState(upper)
     obs = rng.randint(0, min(upper, 40), n)

@@ -46,7 +46,7 @@ def _fixture(name):
     return meta, d, dom
 
 
-def _oracle_lliks(cs, losses, hist_vals, hist_active, vals, active):
+def _oracle_lliks(cs, losses, hist_vals, hist_active, vals, active, gamma=GAMMA, gamma_cap=25):
     """(llik_b, llik_a)[P, M] of the configurations' active values under the
     oracle's fit of the history (stable ties), NaN where inactive."""
     from oracle import tpe_oracle as O
@@ -59,8 +59,8 @@ def _oracle_lliks(cs, losses, hist_vals, hist_active, vals, active):
         on, at = hist_active[i] == 1, active[i] == 1
         if not at.any():
             continue
-        bo, ao = O.split_observations(tids[on], hist_vals[i][on], tids, losses, GAMMA,
-                                      kind='stable')
+        bo, ao = O.split_observations(tids[on], hist_vals[i][on], tids, losses, gamma,
+                                      gamma_cap, kind='stable')
         with np.errstate(all='ignore'):
             r = O.score_hp(hps[lab]['dist'], hps[lab]['args'], bo, ao, PRIOR_WEIGHT,
                            vals[i][at], kind='stable')
