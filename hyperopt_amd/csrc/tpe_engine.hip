@@ -824,6 +824,9 @@ StepShape step_shape(const tpe_plan *p, int64_t n_sug, int64_t n_cand, int64_t c
   s.prune_mode = p->prune_mode;
   s.lattice_on = p->lattice_on;
   s.screen_run = step_screen_run(switches());
+  s.screen_halves = step_screen_halves(switches());
+  s.screen_tail = (int32_t)switches().draw_screen_tail;
+  s.screen_pool = switches().draw_screen_pool;
   s.table_lean = switches().table_lean;
   return s;
 }
@@ -987,11 +990,11 @@ int run_level(tpe_engine *h, tpe_plan *p, int level, const StepShape &s, hipStre
           if (e == hipSuccess) e = launch_table_pilot(a, st);
           if (c.draw == Draw::SortedScreened) {
             if (e == hipSuccess)
-              e = launch_draw_zone(a, p->d_draw_zone, c.screen_tiles, kScreenMargin, c.screen_guide,
-                                   st);
+              e = launch_draw_zone(a, p->d_draw_zone, c.screen_tiles, c.screen_halves, c.screen_tail,
+                                   kScreenMargin, c.screen_guide, st);
             if (e == hipSuccess)
               e = launch_draw_screened(a, p->d_cpos, p->d_draw_zone, p->d_screen_stats,
-                                       c.screen_guide >= 0, c.screen_run, st);
+                                       c.screen_guide >= 0, c.screen_run, c.screen_pool, st);
           } else if (e == hipSuccess) {
             e = launch_draw_pruned(a, c.small_table, c.fast, p->d_cpos, st);
           }

@@ -587,18 +587,21 @@ struct __attribute__((aligned(16))) DrawZone {
   unsigned char tmode[kFuseTab];
 };
 // the zones of a launch's slots: after k_table_pilot, ahead of the screened draw
-// (tiles: pilot wave tiles of widening per side; margin: |x drawn - x true| / sigma covered;
-// guide_bits >= 0: the integer form too, and no zones for a slot whose guide is not valid)
-hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, double margin,
-                            int32_t guide_bits, hipStream_t st);
+// (halves >= 0: half tiles of 64 pilot positions of widening per side, else tiles: whole wave
+// tiles; tail: the tail zones' rank in the pilot's end tiles, 1 .. 128; margin: |x drawn - x
+// true| / sigma covered; guide_bits >= 0: the integer form too, and no zones for a slot whose
+// guide is not valid)
+hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, int32_t halves,
+                            int32_t tail, double margin, int32_t guide_bits, hipStream_t st);
 // launch_draw_pruned's fast small-table launch with the screen; stats: two
 // counters (blocks screened << 40 | elements inverted; blocks fallen back);
 // integer: the screen on integer uniforms (zones from a guide_bits >= 0 launch_draw_zone);
 // run >= 1 (with integer): k_draw_sorted_screen_run, a block per run of `run`
-// sort blocks (at most kScreenRunMax); 0: a block per sort block, as ever
+// sort blocks (at most kScreenRunMax); 0: a block per sort block, as ever;
+// pool (with run >= 1): the listed elements in dense rows across the block
 constexpr int kScreenRunMax = 16;
 hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
-                                unsigned long long *stats, bool integer, int32_t run,
+                                unsigned long long *stats, bool integer, int32_t run, bool pool,
                                 hipStream_t st);
 bool is_screen_draw_kernel_fn(const void *f);  // k_draw_sorted_screen's, all three (tpe_screen.hip)
 bool is_screen_run_kernel_fn(const void *f);   // ... the one with the run length as fifth parameter

@@ -195,6 +195,10 @@ struct StepShape {
   // the run length of the integer screened draw (step_screen_run of the
   // process switches): its grid depends on it
   int32_t screen_run = 0;
+  // the zones' rule and the pooled rows of the screened draw (step_screen_zone
+  // and Switches::draw_screen_pool): halves < 0 is the whole-tile rule
+  int32_t screen_halves = (int32_t)kDrawScreenHalves, screen_tail = (int32_t)kDrawScreenTail;
+  bool screen_pool = false;
   // the lean table path (Switches::table_lean): the build takes a node more
   // (k_table_terms)
   bool table_lean = true;
@@ -203,13 +207,20 @@ struct StepShape {
            n_total == o.n_total && below == o.below && fit == o.fit &&
            prune_mode == o.prune_mode && lattice_on == o.lattice_on &&
            capturing == o.capturing && publish == o.publish && screen_run == o.screen_run &&
-           table_lean == o.table_lean;
+           screen_halves == o.screen_halves && screen_tail == o.screen_tail &&
+           screen_pool == o.screen_pool && table_lean == o.table_lean;
   }
 };
 // StepShape::screen_run under the switches: TPE_DRAW_SCREEN_RUN for the integer
 // screen, 0 (a block per sort block) for the float one
 inline int32_t step_screen_run(const Switches &sw) {
   return sw.draw_screen && sw.draw_screen_int ? (int32_t)sw.draw_screen_run : 0;
+}
+
+// StepShape::screen_halves under the switches: -1 (the whole-tile rule, by
+// draw_screen_tiles) when TPE_DRAW_SCREEN_TILES is set
+inline int32_t step_screen_halves(const Switches &sw) {
+  return sw.draw_screen_whole ? -1 : (int32_t)sw.draw_screen_halves;
 }
 
 // Scoring grid of one launch: runs of equal-kind slots become groups of the
@@ -302,6 +313,9 @@ struct ChunkPlan {
   bool small_table = false;  // ... and the small one (kFuseTab)
   bool fast = false;         // the sorted draw without the out-of-line draws
   int32_t screen_tiles = 0;  // Draw::SortedScreened: the zones' widening
+  int32_t screen_halves = 0; // ... in half tiles; -1: in screen_tiles whole tiles
+  int32_t screen_tail = 128; // ... the tail zones' rank in the pilot's end tiles
+  bool screen_pool = false;  // ... k_draw_sorted_screen_run's rows dense across the block
   int32_t screen_guide = -1; // ... the integer screen's guide bits; -1: the float screen
   int32_t screen_run = 0;    // ... its sort blocks per block (k_draw_sorted_screen_run); 0: one, as ever
   bool bucket = false;       // k_bucket follows the draw
@@ -512,6 +526,9 @@ inline LevelPlan plan_level(const PlanShape &ps, const Switches &sw, const StepS
                           c.cn * n_sug * n_level >= sw.draw_screen_min;
       c.draw = screen ? Draw::SortedScreened : prune ? Draw::SortedPruned : Draw::Sorted;
       c.screen_tiles = (int32_t)sw.draw_screen_tiles;
+      c.screen_halves = s.screen_halves;
+      c.screen_tail = s.screen_tail;
+      c.screen_pool = s.screen_pool;
       c.screen_guide = sw.draw_screen_int ? (int32_t)sw.draw_screen_guide_bits : -1;
       c.screen_run = screen && c.screen_guide >= 0 ? s.screen_run : 0;
       if (prune) c.tab_pref = 2;

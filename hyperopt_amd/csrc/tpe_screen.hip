@@ -23,6 +23,7 @@
 #include "tpe_draw.hpp"
 #include "tpe_internal.hpp"
 #include "tpe_philox_row.hpp"
+#include "tpe_screen_pool.hpp"
 
 namespace tpe {
 
@@ -81,11 +82,28 @@ __device__ __forceinline__ bool zone_crossed(double u1, double b, double m, int 
 // and the guide of 2^gbits buckets), and no zones for a slot whose guide is
 // not valid: the draw's table not finite and nondecreasing with a positive
 // total, or two distinct pick boundaries inside one bucket.
+//
+// The zones are the hot intervals, each widened to where the tiles the draw
+// keeps can reach, and two tails that give a sort block's key range inverted
+// elements.  Both are heuristics of the fallback rate alone: the draw checks
+// per sort block that its key range comes from inverted elements and that no
+// live bucket lies in a gap's bucket range (screen_compose), so any zones that
+// contain the hot intervals are sound.
+//  - halves >= 0: a hot interval [a, b] reaches down to the minimum of the
+//    half tile (64 positions of the pilot's sorted block) `halves` before the
+//    first one whose maximum is at least a, and up likewise; halves < 0: the
+//    same rule in whole tiles, `tiles` of them.
+//  - tail: the low tail ends at the tail-th smallest value of the pilot's
+//    first wave tile, the high tail starts at the tail-th largest of its last
+//    (128: the tiles' maximum and minimum).
 __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZone *zones,
-                                                            int32_t tiles, double margin,
+                                                            int32_t tiles, int32_t halves,
+                                                            int32_t tail, double margin,
                                                             int32_t gbits) {
   __shared__ DrawTableT<kFuseTab> T;
   __shared__ double tmin[kPilotWaves], tmax[kPilotWaves];
+  __shared__ double hmin[2 * kPilotWaves], hmax[2 * kPilotWaves];
+  __shared__ double tail_s[2];
   __shared__ double zlo[kZoneCand], zhi[kZoneCand];
   __shared__ uint64_t pb[kFuseTab];
   __shared__ int nz_s, bad_s;
@@ -130,33 +148,68 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
       mx = fmax(mx, __shfl_xor(mx, o, 64));
     }
     if (lane == 0) { tmin[w] = mn; tmax[w] = mx; }
+    if (halves >= 0) {  // (block-uniform) ... and of its two half tiles
+      double an = a, ax = a, bn = b, bx = b;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        an = fmin(an, __shfl_xor(an, o, 64));
+        ax = fmax(ax, __shfl_xor(ax, o, 64));
+        bn = fmin(bn, __shfl_xor(bn, o, 64));
+        bx = fmax(bx, __shfl_xor(bx, o, 64));
+      }
+      if (lane == 0) { hmin[2 * w] = an; hmax[2 * w] = ax; hmin[2 * w + 1] = bn; hmax[2 * w + 1] = bx; }
+    }
+  }
+  __syncthreads();
+  // the tails' edges: wave 0 the tail-th smallest of tile 0, wave 1 the
+  // tail-th largest of tile 63, by counting each element's rank in its tile
+  // (equal values in index order; rank tail - 1 from its end is the edge)
+  static_assert(kZoneThreads >= 128, "a wave per tail");
+  if (wv < 2) {
+    const int w = wv == 0 ? 0 : kPilotWaves - 1;
+    if (lane == 0) tail_s[wv] = wv == 0 ? tmax[w] : tmin[w];
+    if (tail < 128) {
+      const double a = pc[w * 128 + lane], b = pc[w * 128 + 64 + lane];
+      int ra = 0, rb = 0;  // the elements ahead of a and of b in ascending order
+      for (int i = 0; i < 64; ++i) {
+        const double ua = __shfl(a, i, 64), ub = __shfl(b, i, 64);
+        ra += (ua < a || (ua == a && i < lane) ? 1 : 0) + (ub < a ? 1 : 0);
+        rb += (ua <= b ? 1 : 0) + (ub < b || (ub == b && i < lane) ? 1 : 0);
+      }
+      const int want = wv == 0 ? tail - 1 : 128 - tail;
+      if (ra == want) tail_s[wv] = a;
+      if (rb == want) tail_s[wv] = b;
+    }
   }
   __syncthreads();
   if (t == 0) {
     const double pm = H.prior_mu, y_lo = hot->y_lo, y_hi = hot->y_hi;
     int nz = 0;
     // the tails: the block's key range comes from inverted elements alone
-    zlo[nz] = -INFINITY; zhi[nz] = tmax[0]; ++nz;
-    zlo[nz] = tmin[kPilotWaves - 1]; zhi[nz] = INFINITY; ++nz;
+    zlo[nz] = -INFINITY; zhi[nz] = tail_s[0]; ++nz;
+    zlo[nz] = tail_s[1]; zhi[nz] = INFINITY; ++nz;
     for (int j = 0; j < nh; ++j) {
       // the values whose y' = x - prior_mu, clamped into [y_lo, y_hi], can
       // lie in the interval (a few ulp wider: the rounding of y')
       const double l = hot->lo[j], h = hot->hi[j];
       const double a = l <= y_lo ? -INFINITY : (l + pm) - 8.0 * DBL_EPSILON * (fabs(l) + fabs(pm));
       const double b = h >= y_hi ? INFINITY : (h + pm) + 8.0 * DBL_EPSILON * (fabs(h) + fabs(pm));
-      // ... widened by `tiles` pilot wave tiles on each side: the tiles the
-      // draw keeps reach that far beyond the interval
-      int tf = 0, tl = kPilotWaves - 1;
-      while (tf < kPilotWaves && !(tmax[tf] >= a)) ++tf;
-      while (tl >= 0 && !(tmin[tl] <= b)) --tl;
+      // ... widened by `tiles` pilot wave tiles (`halves` half tiles) on each
+      // side: the tiles the draw keeps reach that far beyond the interval
+      const int nt = halves >= 0 ? 2 * kPilotWaves : kPilotWaves;
+      const int wide = halves >= 0 ? halves : tiles;
+      const double *vmin = halves >= 0 ? hmin : tmin, *vmax = halves >= 0 ? hmax : tmax;
+      int tf = 0, tl = nt - 1;
+      while (tf < nt && !(vmax[tf] >= a)) ++tf;
+      while (tl >= 0 && !(vmin[tl] <= b)) --tl;
       double za = a, zb = b;
       if (a != -INFINITY) {
-        const int w = tf - tiles;
-        za = w < 0 ? -INFINITY : w < kPilotWaves ? fmin(a, tmin[w]) : a;
+        const int w = tf - wide;
+        za = w < 0 ? -INFINITY : w < nt ? fmin(a, vmin[w]) : a;
       }
       if (b != INFINITY) {
-        const int w = tl + tiles;
-        zb = w >= kPilotWaves ? INFINITY : w >= 0 ? fmax(b, tmax[w]) : b;
+        const int w = tl + wide;
+        zb = w >= nt ? INFINITY : w >= 0 ? fmax(b, vmax[w]) : b;
       }
       zlo[nz] = za; zhi[nz] = zb; ++nz;
     }
@@ -303,15 +356,15 @@ __global__ __launch_bounds__(kZoneThreads) void k_draw_zone(ScoreArgs A, DrawZon
   }
 }
 
-hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, double margin,
-                            int32_t guide_bits, hipStream_t st) {
+hipError_t launch_draw_zone(const ScoreArgs &a, DrawZone *zones, int32_t tiles, int32_t halves,
+                            int32_t tail, double margin, int32_t guide_bits, hipStream_t st) {
   const int64_t sbk = (int64_t)1 << a.sort_log2;
   if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
   if (sbk != kSortedBlock || sbk != kPilotWaves * 128 || !zones || !a.tab_hot || !a.tab_hdr ||
-      tiles < 0 || guide_bits > kGuideBitsMax)
+      tiles < 0 || tail < 1 || tail > 128 || guide_bits > kGuideBitsMax)
     return hipErrorInvalidValue;
   k_draw_zone<<<dim3((unsigned)a.slot_rows, a.n_suggest), kZoneThreads, 0, st>>>(
-      a, zones, tiles, margin, guide_bits < 0 ? -1 : guide_bits);
+      a, zones, tiles, halves < 0 ? -1 : halves, tail, margin, guide_bits < 0 ? -1 : guide_bits);
   return hipGetLastError();
 }
 
@@ -340,6 +393,8 @@ struct ScreenLds {
   // the integer screen's pick (DrawZone's)
   uint64_t pickB[kFuseTab];
   uint16_t guide[1 << kGuideBitsMax];
+  // the slot's hot intervals (k_draw_sorted_screen_run: once per run)
+  double hlo[kHotIv], hhi[kHotIv];
 };
 template <int CAP, int NT>
 union ScreenUnion {
@@ -362,7 +417,11 @@ __device__ __forceinline__ int screen_bucket(double key, double lo, double scale
 // in its list, [lo, hi] is the block's key range and (y_lo, y_hi, nh) the head
 // of the slot's hot intervals.  False: a live bucket may hold a cold element
 // (nothing is written).
-template <int NT>
+// HOTLDS: the hot intervals are in L.hlo, L.hhi (run_slot_lds).  POOL: phase 2
+// takes the block's lists as one sequence in rows of 64 dealt to the waves
+// (pool_slot); an element's count goes to its owner's row, so every count, byte
+// and flag is the per-wave loop's.
+template <int NT, bool POOL = false, bool HOTLDS = false>
 __device__ __forceinline__ bool screen_compose(const ScoreArgs &A, int s, int hp, int64_t base,
                                                int64_t off, int n, int nz, int ncl, double lo,
                                                double hi, double mu, const TabHot *hot,
@@ -379,20 +438,39 @@ __device__ __forceinline__ bool screen_compose(const ScoreArgs &A, int s, int hp
   // phase 2: buckets and the hot test of the inverted elements, as
   // sorted_block_prune_body's second pass
   const double scale = hi > lo ? (double)kSortBuckets / (hi - lo) : 0.0;
-#pragma unroll 1
-  for (int j0 = 0; j0 < ncl; j0 += 64) {
-    const int j = j0 + lane;
-    if (j < ncl) {
-      const double x = cx[j];
-      const int b = screen_bucket(x, lo, scale);
-      ci[j] = (ci[j] & 0xffffu) | ((uint32_t)b << 16);
-      __hip_atomic_fetch_add(&mine[b >> 1], 1u << ((b & 1) * 16), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-      const double y = x - mu;
-      const double yc = fmin(fmax(y, y_lo), y_hi);
-      bool hit = y != y;
+  // element e of the lists (cx and ci as one array each), counted in row
+  auto bucket_and_hot = [&](int e, uint32_t *row) {
+    const double x = (&L.cx[0][0])[e];
+    const int b = screen_bucket(x, lo, scale);
+    uint32_t *ce = &L.ci[0][0] + e;
+    *ce = (*ce & 0xffffu) | ((uint32_t)b << 16);
+    __hip_atomic_fetch_add(&row[b >> 1], 1u << ((b & 1) * 16), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    const double y = x - mu;
+    const double yc = fmin(fmax(y, y_lo), y_hi);
+    bool hit = y != y;
+    if constexpr (HOTLDS) {
+      for (int q = 0; q < nh; ++q) hit |= yc >= L.hlo[q] && yc <= L.hhi[q];
+    } else {
       for (int q = 0; q < nh; ++q) hit |= yc >= hot->lo[q] && yc <= hot->hi[q];
-      if (hit) L.hotb[b] = 1;
+    }
+    if (hit) L.hotb[b] = 1;
+  };
+  if constexpr (POOL) {
+    const int total = pool_total<NW>(L.ncl), rows = pool_rows(total);
+#pragma unroll 1
+    for (int r = wv; r < rows; r += NW) {
+      const int idx = r * 64 + lane;
+      if (idx < total) {
+        const PoolSlot o = pool_slot<NW>(L.ncl, idx);
+        bucket_and_hot(o.w * kScreenList + o.j, L.cnt + o.w * (kSortBuckets / 2));
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int j0 = 0; j0 < ncl; j0 += 64) {
+      const int j = j0 + lane;
+      if (j < ncl) bucket_and_hot(wv * kScreenList + j, mine);
     }
   }
   // a gap's cold elements: counted in the bucket of the zone edge below them
@@ -717,10 +795,10 @@ struct RunSlot {
 
 // The slot's state in LDS: the draw table from the DrawZone, the thresholds
 // and the pick boundaries in word form (the edges from E up: none), the guide.
-// The caller's barrier follows.
+// and the nh hot intervals.  The caller's barrier follows.
 template <int NT>
 __device__ __forceinline__ void run_slot_lds(const DrawZone *__restrict__ Z, int K, int nz, int G,
-                                             ScreenLds<NT> &L, int t) {
+                                             const TabHot *hot, int nh, ScreenLds<NT> &L, int t) {
   const int E = 2 * (nz - 1);
   if (t < K) {
     L.T.cdf[t] = Z->tcdf[t];
@@ -732,12 +810,15 @@ __device__ __forceinline__ void run_slot_lds(const DrawZone *__restrict__ Z, int
     L.thrI[idx] = u53_word_threshold(idx % kZoneEdges < E ? (&Z->thrI[0][0])[idx] : 1ull << 53);
   for (int idx = t; idx < (1 << G); idx += NT) L.guide[idx] = Z->guide[idx];
   if (t < kFuseTab) L.pickB[t] = u53_word_threshold(Z->pickB[t]);
+  if (t < nh) { L.hlo[t] = hot->lo[t]; L.hhi[t] = hot->hi[t]; }
 }
 
 // screened_block<CAP, NT, true> for one sort block of a run: the slot's LDS
 // state is in place (run_slot_lds) and hotb, keep and fail are reset, both
-// behind a barrier.  t: the thread's index in the block.
-template <int CAP, int NT>
+// behind a barrier.  t: the thread's index in the block.  POOL: the inversion
+// and phase 2 in rows of 64 across the block's lists (tpe_screen_pool.hpp), one
+// barrier more; the rank and store loop stays per wave, in list order.
+template <int CAP, int NT, bool POOL>
 __device__ __forceinline__ bool screened_block_run(const ScoreArgs &A, const RunSlot &R, int slot,
                                                    int s, int64_t base,
                                                    int32_t *__restrict__ pos_out,
@@ -819,20 +900,43 @@ __device__ __forceinline__ bool screened_block_run(const ScoreArgs &A, const Run
     for (int g = 0; g < kZoneMax - 1; ++g) L.gapc[wv][g] = gc[g];
     if (over) L.fail = 1;
   }
+  uint32_t *mine = L.cnt + wv * (kSortBuckets / 2);
   // the inversion of the listed elements, in dense rows
   double lo = INFINITY, hi = -INFINITY;
-#pragma unroll 1
-  for (int j0 = 0; j0 < ncl; j0 += 64) {
-    const int j = j0 + lane;
-    const bool v = j < ncl;
-    // (an idle lane inverts u1 = 0.5)
-    const double u1 = u53_word_value(v ? (uint64_t)__double_as_longlong(cx[j]) : 1ull << 58);
-    const int k = v ? (int)(ci[j] >> 16) : 0;
+  // element e of the lists (cx and ci as one array each; an idle lane inverts
+  // u1 = 0.5)
+  auto invert = [&](int e, bool v) {
+    double *xe = &L.cx[0][0] + e;
+    const double u1 = u53_word_value(v ? (uint64_t)__double_as_longlong(*xe) : 1ull << 58);
+    const int k = v ? (int)((&L.ci[0][0])[e] >> 16) : 0;
     const double x = draw_bounded_invert<CAP>(L.T, k, u1, R.bmu, R.bsg, R.low, R.high, R.high_prev,
                                               false, false, 0.0);
     if (v) {
-      cx[j] = x;
+      *xe = x;
       if (fabs(x) < INFINITY) { lo = fmin(lo, x); hi = fmax(hi, x); }
+    }
+  };
+  if constexpr (POOL) {
+    // the block's lists as one sequence, wave 0's first, in rows of 64 dealt
+    // to the waves: ceil(sum / 64) rows, not a wave's own ceil(ncl / 64).  The
+    // inversion is element by element and [lo, hi] a minimum and a maximum, so
+    // every bit is the per-wave loop's.  (The counts are zeroed ahead of the
+    // barrier: phase 2 adds to other waves' rows.)
+    for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
+    __syncthreads();
+    const int total = pool_total<NW>(L.ncl), rows = pool_rows(total);
+#pragma unroll 1
+    for (int r = wv; r < rows; r += NW) {
+      const int idx = r * 64 + lane;
+      const bool v = idx < total;
+      const PoolSlot o = pool_slot<NW>(L.ncl, v ? idx : 0);
+      invert(o.w * kScreenList + o.j, v);
+    }
+  } else {
+#pragma unroll 1
+    for (int j0 = 0; j0 < ncl; j0 += 64) {
+      const int j = j0 + lane;
+      invert(wv * kScreenList + j, j < ncl);
     }
   }
 #pragma unroll
@@ -841,8 +945,8 @@ __device__ __forceinline__ bool screened_block_run(const ScoreArgs &A, const Run
     hi = fmax(hi, __shfl_xor(hi, o, 64));
   }
   if (lane == 0) { L.red[0][wv] = lo; L.red[1][wv] = hi; }
-  uint32_t *mine = L.cnt + wv * (kSortBuckets / 2);
-  for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
+  if constexpr (!POOL)
+    for (int b = lane; b < kSortBuckets / 2; b += 64) mine[b] = 0u;
   __syncthreads();
   lo = INFINITY; hi = -INFINITY;
   nexact = 0;
@@ -853,8 +957,8 @@ __device__ __forceinline__ bool screened_block_run(const ScoreArgs &A, const Run
     nexact += L.ncl[w];
   }
   if (L.fail || !(lo <= R.gap_first) || !(hi >= R.gap_last)) return false;
-  return screen_compose<NT>(A, s, R.hp, base, off, n, nz, ncl, lo, hi, R.mu, R.hot, R.y_lo, R.y_hi,
-                            R.nh, Z, pos_out, L, t);
+  return screen_compose<NT, POOL, true>(A, s, R.hp, base, off, n, nz, ncl, lo, hi, R.mu, R.hot,
+                                        R.y_lo, R.y_hi, R.nh, Z, pos_out, L, t);
 }
 
 // Block x of the grid takes the sort blocks x run + 1 .. min(x run + run, the
@@ -862,7 +966,7 @@ __device__ __forceinline__ bool screened_block_run(const ScoreArgs &A, const Run
 // sorted_block_prune_body, which overwrites the union: those run behind the
 // run's last screened sort block, so the slot's LDS state is loaded once.  The
 // two counters get the run's totals.
-template <int CAP, bool FAST>
+template <int CAP, bool FAST, bool POOL>
 __device__ __forceinline__ void draw_sorted_screen_run_body(const ScoreArgs &A,
                                                             int32_t *__restrict__ pos_out,
                                                             const DrawZone *__restrict__ zones,
@@ -922,7 +1026,7 @@ __device__ __forceinline__ void draw_sorted_screen_run_body(const ScoreArgs &A,
   static_assert(kScreenRunMax <= 31, "a run's sort blocks: one mask");
   uint32_t todo = scr ? 0u : (1u << (j1 - j0)) - 1u;
   if (scr) {
-    run_slot_lds(Z, R.K, nz, 31 - R.gsh, U.S, (int)threadIdx.x);
+    run_slot_lds(Z, R.K, nz, 31 - R.gsh, R.hot, R.nh, U.S, (int)threadIdx.x);
 #pragma unroll 1
     for (int j = j0; j < j1; ++j) {
       // (the thread's index through an empty asm statement: what a sort block
@@ -936,7 +1040,7 @@ __device__ __forceinline__ void draw_sorted_screen_run_body(const ScoreArgs &A,
       if (t == 0) { U.S.keep = 0ull; U.S.fail = 0; }
       __syncthreads();
       int nexact = 0;
-      if (screened_block_run<CAP, kScreenThreads>(A, R, slot, s, (int64_t)(j + 1) << A.sort_log2,
+      if (screened_block_run<CAP, kScreenThreads, POOL>(A, R, slot, s, (int64_t)(j + 1) << A.sort_log2,
                                                   pos_out, Z, U.S, t, nexact))
         screened += (1ull << 40) | (unsigned long long)nexact;
       else
@@ -966,16 +1070,17 @@ __device__ __forceinline__ void draw_sorted_screen_run_body(const ScoreArgs &A,
     if (fallen) atomicAdd(stats + 1, (unsigned long long)fallen);
   }
 }
-template <int CAP, bool FAST>
+template <int CAP, bool FAST, bool POOL>
 __global__ __launch_bounds__(kScreenThreads) __attribute__((amdgpu_waves_per_eu(4)))
 void k_draw_sorted_screen_run(ScoreArgs A, int32_t *__restrict__ pos_out,
                               const DrawZone *__restrict__ zones, unsigned long long *stats,
                               int32_t run) {
-  draw_sorted_screen_run_body<CAP, FAST>(A, pos_out, zones, stats, run);
+  draw_sorted_screen_run_body<CAP, FAST, POOL>(A, pos_out, zones, stats, run);
 }
 
 bool is_screen_run_kernel_fn(const void *f) {
-  return f == reinterpret_cast<const void *>(&k_draw_sorted_screen_run<kFuseTab, true>);
+  return f == reinterpret_cast<const void *>(&k_draw_sorted_screen_run<kFuseTab, true, false>) ||
+         f == reinterpret_cast<const void *>(&k_draw_sorted_screen_run<kFuseTab, true, true>);
 }
 bool is_screen_draw_kernel_fn(const void *f) {
   return f == reinterpret_cast<const void *>(&k_draw_sorted_screen<kFuseTab, true>) ||
@@ -984,7 +1089,7 @@ bool is_screen_draw_kernel_fn(const void *f) {
 }
 
 hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const DrawZone *zones,
-                                unsigned long long *stats, bool integer, int32_t run,
+                                unsigned long long *stats, bool integer, int32_t run, bool pool,
                                 hipStream_t st) {
   const int64_t sbk = (int64_t)1 << a.sort_log2;
   if (a.n_slots <= 0 || a.n_suggest <= 0 || a.n_cand <= sbk) return hipSuccess;
@@ -994,8 +1099,12 @@ hipError_t launch_draw_screened(const ScoreArgs &a, int32_t *pos_out, const Draw
   const int64_t nsb = (a.n_cand + sbk - 1) / sbk - 1;
   if (integer && run >= 1) {
     const dim3 gr((unsigned)((nsb + run - 1) / run), (unsigned)a.slot_rows, a.n_suggest);
-    k_draw_sorted_screen_run<kFuseTab, true><<<gr, kScreenThreads, 0, st>>>(a, pos_out, zones, stats,
-                                                                            run);
+    if (pool)
+      k_draw_sorted_screen_run<kFuseTab, true, true><<<gr, kScreenThreads, 0, st>>>(a, pos_out, zones,
+                                                                                    stats, run);
+    else
+      k_draw_sorted_screen_run<kFuseTab, true, false><<<gr, kScreenThreads, 0, st>>>(
+          a, pos_out, zones, stats, run);
     return hipGetLastError();
   }
   const dim3 g((unsigned)nsb, (unsigned)a.slot_rows, a.n_suggest);

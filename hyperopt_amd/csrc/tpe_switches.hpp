@@ -55,6 +55,19 @@ struct Switches {
   // the screen's zones widen a hot interval by this many pilot wave tiles per
   // side (the sweep behind the default)
   int64_t draw_screen_tiles;
+  // TPE_DRAW_SCREEN_TILES is set: the whole-tile rule with that many tiles.
+  // Unset, the zones widen by draw_screen_halves half tiles of 64 positions
+  // per side (the sweep behind the defaults)
+  bool draw_screen_whole;
+  int64_t draw_screen_halves;
+  // the tail zones end at the r-th smallest value of the pilot's first wave
+  // tile and the r-th largest of its last; 128: the tiles' maximum and minimum
+  int64_t draw_screen_tail;
+  // k_draw_sorted_screen_run inverts and buckets the listed elements of a sort
+  // block in dense rows dealt to its waves: opt-in (the rows it saves
+  // cost less than its barrier and the owner lookup); default: every wave its
+  // own list
+  bool draw_screen_pool;
   // the smallest launch (candidates x suggestions x slots) the screen takes: it
   // saves ~1.4 us per 2^20 candidate-slots, k_draw_zone costs ~33 us
   int64_t draw_screen_min;
@@ -84,6 +97,8 @@ struct Switches {
 
 constexpr int64_t kDrawScreenMin = (int64_t)1 << 26;
 constexpr int64_t kDrawScreenRun = 4;
+constexpr int64_t kDrawScreenHalves = 4;
+constexpr int64_t kDrawScreenTail = 24;
 
 // how a variable's text becomes the switch
 enum class SwitchRule {
@@ -91,6 +106,7 @@ enum class SwitchRule {
   OffIfNonEmptyZero,  // off iff set, non-empty and atoi == 0
   OnIfNonZero,        // on iff set and atoi != 0
   OnIfSet,            // on iff set at all
+  OnIfNonEmpty,       // on iff set and non-empty
   ValueIfSet,         // atoll of the text if set, clamped to [lo, hi]
   ValueIfNonEmpty,    // ... if set and non-empty
 };
@@ -131,6 +147,12 @@ inline const SwitchDef *switch_table(int *n) {
       {"TPE_TABLE_TIE_LOG2", R::ValueIfSet, kTabTieLog2, nullptr, &S::table_tie_log2, -1074, 4096},
       {"TPE_DRAW_SCREEN_TILES", R::ValueIfNonEmpty, 2, nullptr, &S::draw_screen_tiles, 0,
        kPilotWaves},
+      {"TPE_DRAW_SCREEN_TILES", R::OnIfNonEmpty, 0, &S::draw_screen_whole, nullptr, 0, 0},
+      {"TPE_DRAW_SCREEN_HALVES", R::ValueIfNonEmpty, kDrawScreenHalves, nullptr,
+       &S::draw_screen_halves, 0, 2 * kPilotWaves},
+      {"TPE_DRAW_SCREEN_TAIL", R::ValueIfNonEmpty, kDrawScreenTail, nullptr, &S::draw_screen_tail, 1,
+       128},
+      {"TPE_DRAW_SCREEN_POOL", R::OnIfNonZero, 0, &S::draw_screen_pool, nullptr, 0, 0},
       {"TPE_DRAW_SCREEN_MIN", R::ValueIfNonEmpty, kDrawScreenMin, nullptr, &S::draw_screen_min, lo,
        hi},
       {"TPE_DRAW_SCREEN_GUIDE_BITS", R::ValueIfNonEmpty, 9, nullptr, &S::draw_screen_guide_bits, 0,
@@ -158,6 +180,7 @@ Switches read_switches(Get get) {
       case SwitchRule::OffIfNonEmptyZero: s.*d.flag = !(e && *e && std::atoi(e) == 0); break;
       case SwitchRule::OnIfNonZero: s.*d.flag = e && std::atoi(e) != 0; break;
       case SwitchRule::OnIfSet: s.*d.flag = e != nullptr; break;
+      case SwitchRule::OnIfNonEmpty: s.*d.flag = e && *e; break;
       case SwitchRule::ValueIfSet:
       case SwitchRule::ValueIfNonEmpty: {
         const bool set = e && (d.rule == SwitchRule::ValueIfSet || *e);

@@ -647,15 +647,23 @@ def _block_layout(key, hit, n):
     return cnt, base, keep, live
 
 
-def draw_zones(pilot, intervals, y_lo, y_hi, center, tiles, zone_max=6):
+def draw_zones(pilot, intervals, y_lo, y_hi, center, tiles, zone_max=6, tail=WAVE, halves=None):
     """k_draw_zone's value zones (zlo, zhi) from the pilot's sort block (draw
-    order) and the hot intervals in y'; None: the slot is not screened."""
+    order) and the hot intervals in y'; None: the slot is not screened.
+    tail: the low tail ends at the tail-th smallest value of the first wave
+    tile of the bucket-sorted pilot, the high tail starts at the tail-th
+    largest of its last (128: the tiles' maximum and minimum).  halves: the
+    widening in half tiles of 64 positions (the device's default rule);
+    None: in `tiles` whole tiles."""
     key = _block_bytes(pilot, pilot.min(), pilot.max())
     t = pilot[np.argsort(key, kind='stable')].reshape(-1, WAVE)
+    first, last = np.sort(t[0]), np.sort(t[-1])
+    z = [(-np.inf, first[tail - 1]), (last[WAVE - tail], np.inf)]
+    if halves is not None:
+        t, tiles = t.reshape(-1, WAVE // 2), halves
     tmin, tmax = t.min(axis=1), t.max(axis=1)
     nt = tmin.size
     eps = np.finfo(np.float64).eps
-    z = [(-np.inf, tmax[0]), (tmin[-1], np.inf)]
     for l, h in intervals:
         a = -np.inf if l <= y_lo else (l + center) - 8.0 * eps * (abs(l) + abs(center))
         b = np.inf if h >= y_hi else (h + center) + 8.0 * eps * (abs(h) + abs(center))
@@ -688,7 +696,7 @@ def draw_zones(pilot, intervals, y_lo, y_hi, center, tiles, zone_max=6):
 
 
 def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cells=CELLS,
-                integers=None, gbits=9):
+                integers=None, gbits=9, tail=WAVE, halves=None):
     """The screened draw on the draws (k, u1, x) of one launch (draw_picks),
     block by block behind the pilot's, beside the full computation on all
     elements: dict with `blocks`, `fallback` (blocks that would run the full
@@ -698,13 +706,16 @@ def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cell
     inverted elements differ from the full computation's (must be empty).
     integers = (U0, U1): the integer screen -- the component from the guide
     pick of U0 (k only draws x), the class from U1 against thrI; a slot whose
-    guide is not valid is not screened (`valid` False, no blocks)."""
+    guide is not valid is not screened (`valid` False, no blocks).
+    tail, halves: draw_zones'.  `lists`: per screened block, the inverted
+    elements of each of its eight waves (k_draw_sorted_screen_run's lists)."""
     w, mu, sigma = mix
     r = prefilter(tb, ta, x - center, tie, cells)
     y_lo = tb['y_lo']
     y_hi = y_lo + tb['width'] * tb['P']
-    out = dict(blocks=0, fallback=0, exact=0.0, mismatch=[])
-    zones = draw_zones(x[:SORT_BLOCK], r['intervals'], y_lo, y_hi, center, tiles)
+    out = dict(blocks=0, fallback=0, exact=0.0, mismatch=[], lists={})
+    zones = draw_zones(x[:SORT_BLOCK], r['intervals'], y_lo, y_hi, center, tiles, tail=tail,
+                       halves=halves)
     if zones is None:
         return out
     zlo, zhi = zones
@@ -750,6 +761,8 @@ def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cell
             continue
         nscr += xb.size
         nex += int(ex.sum())
+        per = -(-xb.size // (8 * 64)) * 64     # (bucket_bases' rows of a wave)
+        out['lists'][b0 // SORT_BLOCK] = [int(ex[v * per:(v + 1) * per].sum()) for v in range(8)]
         same = (lo == xb.min() and hi == xb.max() and (keep == full[2]).all() and
                 (live == full[3]).all() and (cnt[live] == full[0][live]).all() and
                 (bas[live] == full[1][live]).all() and
@@ -760,7 +773,8 @@ def draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles=2, tie=TIE, cell
     return out
 
 
-def report_drawscreen(losses, cols, specs, every=1, draws=1 << 18, only=None, tiles=2, **fit):
+def report_drawscreen(losses, cols, specs, every=1, draws=1 << 18, only=None, tiles=2, tail=WAVE,
+                      halves=None, **fit):
     """Per hp with two certified tables: blocks, fallback blocks and the share
     of inverted elements of the screened draw's emulation."""
     for i, (label, (dist, args)) in enumerate(specs.items()):
@@ -772,7 +786,7 @@ def report_drawscreen(losses, cols, specs, every=1, draws=1 << 18, only=None, ti
             continue
         tb, ta, mix, (low, high, center) = cp
         k, u1, x = draw_picks(*mix, low, high, draws, np.random.RandomState(1000 + i))
-        r = draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles)
+        r = draw_screen(tb, ta, mix, low, high, center, k, u1, x, tiles, tail=tail, halves=halves)
         print('%-6s blocks %4d fallback %4d inverted %.4f mismatches %d'
               % (label, r['blocks'], r['fallback'], r['exact'], len(r['mismatch'])))
 
@@ -1025,6 +1039,10 @@ def main():
     ap.add_argument('--fit-set', choices=sorted(FIT_SETS), help='the fit parameters of a named set')
     ap.add_argument('--drawscreen', action='store_true', help='report the screened-draw emulation')
     ap.add_argument('--tiles', type=int, default=2, help='--drawscreen: zone widening in pilot tiles')
+    ap.add_argument('--tail', type=int, default=WAVE,
+                    help="--drawscreen: the tail zones' rank in the pilot's end tiles (1 .. 128)")
+    ap.add_argument('--halves', type=int, default=None,
+                    help='--drawscreen: zone widening in half tiles (instead of --tiles)')
     ap.add_argument('--erfcinv', action='store_true',
                     help="only report erfcinv_fast's emulated error (the screened draw's margin)")
     a = ap.parse_args()
@@ -1049,7 +1067,8 @@ def main():
         losses, cols, specs = test_shape(a.n, gap)
     if a.drawscreen:
         only = None if a.only is None else {int(x) for x in a.only.split(',')}
-        report_drawscreen(losses, cols, specs, a.every, a.draws, only, a.tiles, **fit)
+        report_drawscreen(losses, cols, specs, a.every, a.draws, only, a.tiles, a.tail, a.halves,
+                          **fit)
         return
     if not (a.drawprune and a.only):
         run(losses, cols, specs, a.every, **fit)
