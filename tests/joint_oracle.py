@@ -32,8 +32,9 @@ def side_rows(losses, gamma, gamma_cap=O.DEFAULT_LF):
 
 
 def side_weights(n_s, prior_weight, lf=O.DEFAULT_LF):
-    """(w[K], S): w_0 the prior's weight, w_k the k-th row's."""
-    lw = O.lf_weights(n_s, lf) if lf < n_s else np.ones(n_s)
+    """(w[K], S): w_0 the prior's weight, w_k the k-th row's (lf = 0: no
+    forgetting, as ``parzen_fit`` reads it)."""
+    lw = O.lf_weights(n_s, lf) if lf and lf < n_s else np.ones(n_s)
     S = lw.sum() if n_s else 0.0
     return np.concatenate([[prior_weight], lw]) / (S + prior_weight), S
 
