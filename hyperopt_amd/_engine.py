@@ -54,10 +54,12 @@ EXPORTS = (
     'tpe_plan_group_batch_points',
     'tpe_plan_set_objectives', 'tpe_plan_pareto_get', 'tpe_plan_pareto_shape',
     'tpe_plan_set_hv', 'tpe_plan_hv_get',
+    'tpe_plan_set_constraints', 'tpe_plan_constraint_get',
 )
 
 BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
 MAX_OBJ = 8                 # include/tpe_engine.h TPE_MAX_OBJ
+MAX_CON = 16                # include/tpe_engine.h TPE_MAX_CON
 
 # include/tpe_engine.h TPE_SHARD_ALIGN: candidate splits at multiples of this
 # give byte-identical suggests (the large-draw value-bucketing block)
@@ -191,6 +193,8 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_pareto_shape': (C.c_int, [vp, i64, i32, i64, C.POINTER(i64)]),
             'tpe_plan_set_hv': (C.c_int, [vp, i32, vp, i32, i32, i32, C.c_uint64, i32]),
             'tpe_plan_hv_get': (C.c_int, [vp, vp, vp, vp, C.POINTER(i32), i32]),
+            'tpe_plan_set_constraints': (C.c_int, [vp, vp, i32, i64, i64, i64, i32, vp]),
+            'tpe_plan_constraint_get': (C.c_int, [vp, vp, i64]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -630,6 +634,54 @@ class Plan(object):
                                           counts.ctypes.data, C.byref(R), cap))
         k = int(np.count_nonzero(picks != -2))      # (entries the engine wrote)
         return picks[:k], keys[:k], counts[:k], int(R.value)
+
+    # ---- constrained TPE: the constraint matrix the next ranking reads
+    def set_constraints(self, G, n=None, con0=0, stream=None):
+        """The constraint matrix the next ``set_objectives`` ranks by
+        (tpe_plan_set_constraints): ``G`` float64 [C, ld] C-contiguous,
+        constraint c of row r at ``G[c, r]``, feasible when <= 0; rows
+        [con0, n) are copied (the rows below are the last call's).  ``G`` None
+        switches the mode off.  ``n`` (default ld) must be the history
+        length."""
+        e = self.engine
+        if G is None:
+            with e.lock:
+                e.check(e.lib.tpe_plan_set_constraints(self.p, None, 0, 0, 0, 0, 0, None))
+            self._con_on = False
+            return
+        G = np.asarray(G)
+        if G.ndim != 2 or G.dtype != np.float64 or not G.flags.c_contiguous:
+            raise ValueError('constraints must be a C-contiguous float64 [C, ld] array')
+        c, ld = G.shape
+        n = ld if n is None else int(n)
+        con0 = int(con0)
+        if c < 1 or n > ld or not 0 <= con0 <= n:
+            raise ValueError('need C >= 1 and 0 <= con0 <= n <= ld')
+        ptr = (G.ctypes.data + 8 * con0) if ld > 0 else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_set_constraints(self.p, ptr, int(c), n, int(ld), con0, 0,
+                                                   stream))
+        self._con_on = True
+
+    def set_constraints_device(self, g_ptr, n_con, n, ld, con0=0, stream=None):
+        """The same from device memory: ``g_ptr`` points at row con0 of
+        constraint 0, constraint c of row r at g_ptr[c * ld + (r - con0)].
+        Stream-ordered, no host synchronisation."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_set_constraints(self.p, g_ptr, int(n_con), int(n), int(ld),
+                                                   int(con0), 1, stream))
+        self._con_on = int(n_con) > 0
+
+    def constraint_get(self, n):
+        """violation float64[n] of the last ``set_objectives``, which ran with
+        constraints (tpe_plan_constraint_get)."""
+        e = self.engine
+        n = int(n)
+        v = np.empty(max(n, 0))
+        with e.lock:
+            e.check(e.lib.tpe_plan_constraint_get(self.p, v.ctypes.data, n))
+        return v
 
     def fit(self, gamma=0.25, prior_weight=1.0, lf=25, gamma_cap=25, stream=None):
         e = self.engine

@@ -253,6 +253,13 @@ struct tpe_plan : PlanShape {
   int32_t hv_u_S = 0, hv_u_M = 0;
   int32_t hv_last_pick = 0;     // n_pick of the last ranking's selection (0: it ran none)
   bool hv_last_exact = false;
+  // constrained dominance (tpe_plan_set_constraints, tpe_constraint.hip):
+  // nothing allocated or launched while con_C is 0
+  int32_t con_C = 0;            // constraints: read by the next tpe_plan_set_objectives (0: off)
+  int64_t con_n = 0;            // rows of d_con held
+  double *d_con = nullptr;      // [TPE_MAX_CON][ncap] the constraint matrix
+  double *d_viol = nullptr;     // [ncap] the violations of the last constrained ranking
+  int64_t viol_n = -1;          // ... and their number (-1: that ranking had none)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -325,7 +332,7 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_gsides, p->d_gjoint, p->d_bt_ja, p->d_bt_score, p->d_bt_gain,
                   p->d_bt_trace, p->d_bt_gact, p->d_bt_state, p->d_bt_slot, p->d_bt_rec,
                   p->d_bt_idx, p->d_obj, p->d_pcount, p->d_hv_i32, p->d_hv_f64, p->d_hv_alive,
-                  p->d_hv_u};
+                  p->d_hv_u, p->d_con, p->d_viol};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -1678,14 +1685,19 @@ int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_
                 "set_objectives: the rows below obj0 are not on the device with this n_obj");
   if (p->hv_mode && p->hv_M != n_obj)
     return fail(h, TPE_E_INVALID, "set_objectives: n_obj is not that of tpe_plan_set_hv");
+  const int32_t C = p->con_C;
+  if (C && n > p->con_n)
+    return fail(h, TPE_E_INVALID,
+                "set_objectives: more rows than tpe_plan_set_constraints holds");
   if (n == 0) {  // an empty history: nothing to rank
     p->obj_M = n_obj;
     p->obj_n = 0;
     p->pareto_n = 0;
     p->hv_last_pick = 0;
+    p->viol_n = C ? 0 : -1;
     return TPE_OK;
   }
-  const ParetoPlan pp = pareto_plan(n, n_obj, p->pareto_force);
+  const ParetoPlan pp = pareto_plan(n, n_obj, p->pareto_force, C ? 1 : 0);
   if (!pp.ok) return fail(h, TPE_E_INVALID, "set_objectives: need (n + 1)^2 < 2^53");
   CKH(hipSetDevice(h->device));
   hipStream_t st = pick_stream(h, stream);
@@ -1706,8 +1718,15 @@ int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_
   p->obj_n = n;
   int32_t *by = p->d_pcount, *of = p->d_pcount + p->ncap;
   p->pareto_n = -1;
+  p->viol_n = -1;
   CKH(hipMemsetAsync(p->d_pcount, 0, 2 * (size_t)p->ncap * sizeof(int32_t), st));
-  CKH(launch_pareto_count(p->d_obj, p->ncap, n, n_obj, pp.per_split, pp.splits, by, of, st));
+  if (C) {  // constrained dominance in the place of dominance
+    CKH(launch_violation(p->d_con, p->ncap, n, C, p->d_viol, st));
+    CKH(launch_cdom_count(p->d_obj, p->d_viol, p->ncap, n, n_obj, pp.per_split, pp.splits, by,
+                          of, st));
+  } else {
+    CKH(launch_pareto_count(p->d_obj, p->ncap, n, n_obj, pp.per_split, pp.splits, by, of, st));
+  }
   p->hv_last_pick = 0;
   if (p->hv_mode && n_obj >= 2) {
     const int rc = hv_rank(h, p, n, n_obj, by, of, st);
@@ -1716,12 +1735,69 @@ int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_
     CKH(launch_pareto_loss(p->d_obj, p->ncap, n, n_obj, by, of, p->d_losses, st));
   }
   p->pareto_n = n;
+  if (C) p->viol_n = n;
   // a new loss column: nothing fitted on the old one stands
   p->last_nb = -1;
   p->tab_built = false;
   p->joint_ok = false;
   p->group_ok = false;
   if (!on_device) CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+// ---- constrained TPE: the constraint matrix the next ranking reads
+int tpe_plan_set_constraints(tpe_plan_t p, const double *G, int32_t n_con, int64_t n, int64_t ld,
+                             int64_t con0, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (n_con == 0) {  // off: nothing else is read
+    p->con_C = 0;
+    p->con_n = 0;
+    return TPE_OK;
+  }
+  if (n_con < 0 || n_con > TPE_MAX_CON)
+    return fail(h, TPE_E_INVALID, "set_constraints: need 0 <= n_con <= TPE_MAX_CON");
+  if (n != p->n) return fail(h, TPE_E_INVALID, "set_constraints: n is not the history length");
+  if (!G) return fail(h, TPE_E_INVALID, "set_constraints: G must not be null");
+  if (con0 < 0 || con0 > n) return fail(h, TPE_E_INVALID, "set_constraints: need 0 <= con0 <= n");
+  if (ld < n - con0) return fail(h, TPE_E_INVALID, "set_constraints: ld < n - con0");
+  if (con0 > 0 && (p->con_C != n_con || con0 > p->con_n))
+    return fail(h, TPE_E_INVALID,
+                "set_constraints: the rows below con0 are not on the device with this n_con");
+  if (n == 0) {
+    p->con_C = n_con;
+    p->con_n = 0;
+    return TPE_OK;
+  }
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  if (!p->d_con) {
+    CKH(dalloc(&p->d_con, (size_t)TPE_MAX_CON * (size_t)p->ncap));
+    CKH(dalloc(&p->d_viol, (size_t)p->ncap));
+  }
+  p->con_C = 0;  // (not a consistent matrix until the copy is enqueued)
+  p->con_n = 0;
+  if (con0 < n)
+    CKH(hipMemcpy2DAsync(p->d_con + con0, (size_t)p->ncap * 8, G, (size_t)ld * 8,
+                         (size_t)(n - con0) * 8, (size_t)n_con,
+                         on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  p->con_C = n_con;
+  p->con_n = n;
+  if (!on_device) CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+static_assert(kConstraintMax == TPE_MAX_CON, "tpe_pareto_plan.hpp's constant is the header's");
+
+int tpe_plan_constraint_get(tpe_plan_t p, double *violation, int64_t n) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->viol_n < 0 || n != p->viol_n)
+    return fail(h, TPE_E_INVALID,
+                "constraint_get: n is not that of the last constrained tpe_plan_set_objectives");
+  if (n == 0 || !violation) return TPE_OK;
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  CKH(hipMemcpy(violation, p->d_viol, (size_t)n * 8, hipMemcpyDeviceToHost));
   return TPE_OK;
 }
 

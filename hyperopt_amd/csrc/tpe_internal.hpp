@@ -1013,6 +1013,17 @@ hipError_t launch_pareto_loss(const double *Y, int64_t ld, int64_t n, int32_t M,
                               const int32_t *dominated_by, const int32_t *dominates,
                               double *losses, hipStream_t st);
 
+// Constrained dominance (tpe_constraint.hip; tpe_plan_set_constraints; DESIGN
+// 5.19).  launch_violation: v[r] of rows [0, n) from the constraint matrix
+// G[C][ld].  launch_cdom_count: launch_pareto_count's counts under constrained
+// dominance, from Y[M][ld] and v (same grid, same zeroed counters); the
+// surrogate column follows from launch_pareto_loss / launch_hv_select.
+hipError_t launch_violation(const double *G, int64_t ld, int64_t n, int32_t C, double *v,
+                            hipStream_t st);
+hipError_t launch_cdom_count(const double *Y, const double *v, int64_t ld, int64_t n, int32_t M,
+                             int64_t per_split, int64_t splits, int32_t *dominated_by,
+                             int32_t *dominates, hipStream_t st);
+
 // Greedy hypervolume subset selection inside the Pareto front and the
 // surrogate column that follows from it (tpe_hv.hip; tpe_plan_set_hv; DESIGN
 // 5.18), after launch_pareto_count on the same stream: k_hv_init, per round

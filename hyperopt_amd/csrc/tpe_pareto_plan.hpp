@@ -13,6 +13,7 @@ namespace tpe {
 
 constexpr int kParetoTile = 256;     // rows per tile: one row per lane of a block
 constexpr int kParetoMaxObj = 8;     // TPE_MAX_OBJ
+constexpr int kConstraintMax = 16;   // TPE_MAX_CON
 // the largest history: s = dominated_by (n + 1) + (n - dominates) is an exact
 // integer in a double while (n + 1)^2 < 2^53
 constexpr int64_t kParetoMaxN = 94906264;
@@ -29,7 +30,7 @@ struct ParetoPlan {
   int64_t tiles = 0;      // ceil(n / tile): tiles of rows i (grid.x) and of rows j
   int64_t per_split = 0;  // j tiles a block walks
   int64_t splits = 0;     // grid.y: ceil(tiles / per_split), none empty
-  size_t lds_bytes = 0;   // the staged j tile, [M][tile] doubles
+  size_t lds_bytes = 0;   // the staged j tile, [M + extra_rows][tile] doubles
 
   // rows [begin, end) of tile t
   int64_t tile_begin(int64_t t) const { return t * kParetoTile; }
@@ -41,10 +42,14 @@ struct ParetoPlan {
 
 // force_splits > 0: that many j-splits where the history has the tiles for it
 // (tests); 0: enough to fill the machine.  Whatever is asked for, the result
-// has no empty split: splits = ceil(tiles / per_split).
-inline ParetoPlan pareto_plan(int64_t n, int32_t M, int64_t force_splits = 0) {
+// has no empty split: splits = ceil(tiles / per_split).  extra_rows: rows a
+// block stages beside the M objectives -- 1 under constraints, the violation
+// of k_cdom_count (tpe_constraint.hip), 0 otherwise.
+inline ParetoPlan pareto_plan(int64_t n, int32_t M, int64_t force_splits = 0,
+                              int32_t extra_rows = 0) {
   ParetoPlan p;
   if (n < 1 || n > kParetoMaxN || M < 1 || M > kParetoMaxObj) return p;
+  if (extra_rows < 0 || extra_rows > 1) return p;
   p.n = n;
   p.M = M;
   p.tiles = (n + kParetoTile - 1) / kParetoTile;
@@ -52,7 +57,7 @@ inline ParetoPlan pareto_plan(int64_t n, int32_t M, int64_t force_splits = 0) {
   want = std::max<int64_t>(1, std::min<int64_t>(want, std::min<int64_t>(p.tiles, kParetoMaxSplits)));
   p.per_split = (p.tiles + want - 1) / want;
   p.splits = (p.tiles + p.per_split - 1) / p.per_split;
-  p.lds_bytes = (size_t)M * kParetoTile * sizeof(double);
+  p.lds_bytes = (size_t)(M + extra_rows) * kParetoTile * sizeof(double);
   p.ok = p.lds_bytes <= kParetoLdsLimit;
   return p;
 }

@@ -25,6 +25,12 @@ is kept beside the losses, from ``result['objectives']`` of the ok trials, and
 (``tpe_plan_set_objectives``) instead of sending the losses.  With
 ``hypervolume=`` the nondominated rows are ordered by a greedy hypervolume
 subset selection against a reference point (``tpe_plan_set_hv``).
+
+With ``constraints=C`` (constrained TPE) a constraint store
+``G[C][cap]`` is kept too, from ``result['constraints']`` of the ok trials, and
+``push`` sends it (``tpe_plan_set_constraints``) ahead of the objectives: the
+device then ranks by constrained dominance.  Without ``objectives`` the
+objective store is the single row of the losses.
 """
 from __future__ import annotations
 
@@ -37,6 +43,7 @@ import numpy as np
 from .status import STATUS_OK
 
 MAX_OBJ = 8                     # include/tpe_engine.h TPE_MAX_OBJ
+MAX_CON = 16                    # include/tpe_engine.h TPE_MAX_CON
 
 
 def _loss_of(domain, doc):
@@ -54,6 +61,19 @@ def check_objectives(objectives):
         raise ValueError('objectives must be None or an int in [1, %d], got %r'
                          % (MAX_OBJ, objectives))
     return int(objectives)
+
+
+def check_constraints(constraints):
+    """``constraints=`` checked: None (unconstrained) or the number C in
+    [1, 16] of constraints every ok trial reports in ``result['constraints']``
+    (feasible when every one is <= 0)."""
+    if constraints is None:
+        return None
+    if isinstance(constraints, bool) or not isinstance(constraints, numbers.Integral) \
+            or not 1 <= constraints <= MAX_CON:
+        raise ValueError('constraints must be None or an int in [1, %d], got %r'
+                         % (MAX_CON, constraints))
+    return int(constraints)
 
 
 def check_hypervolume(hypervolume, objectives):
@@ -107,20 +127,20 @@ def default_reference(Y):
 HV_N_PICK, HV_N_SAMPLES, HV_SEED, HV_METHOD = 32, 1024, 0, 0
 
 
-def _objectives_of(doc, M, tid):
-    """The M objectives of a row's document: those of an ok trial, NaN (a
-    pending row) for any other."""
+def _objectives_of(doc, M, tid, key='objectives'):
+    """The M objectives (``key='constraints'``: constraints) of a row's
+    document: those of an ok trial, NaN (a pending row) for any other."""
     res = doc['result']
     if res.get('status') != STATUS_OK:
         return np.full(M, np.nan)
-    y = res.get('objectives')
+    y = res.get(key)
     try:
         ok = y is not None and len(y) == M
     except TypeError:
         ok = False
     if not ok:
-        raise ValueError("trial %r: result['objectives'] must be a sequence of %d numbers, got %r"
-                         % (tid, M, y))
+        raise ValueError("trial %r: result[%r] must be a sequence of %d numbers, got %r"
+                         % (tid, key, M, y))
     return np.array([float(v) for v in y])
 
 
@@ -140,6 +160,8 @@ class TrialHistory(object):
         self.M = None           # objectives of the last sync (None: the scalar loss)
         self.Y = None           # [M][cap] objective store beside losses (NaN: pending)
         self.hv = False         # hypervolume= of the last sync: False, True or the reference point
+        self.C = None           # constraints of the last sync (None: unconstrained)
+        self.G = None           # [C][cap] constraint store (NaN: not an ok trial)
         self._alloc(64)
         self._forget()
 
@@ -165,6 +187,10 @@ class TrialHistory(object):
             y = self.Y
             self.Y = np.full((y.shape[0], cap), np.nan)
             self.Y[:, :self.n] = y[:, :self.n]
+        if self.G is not None:
+            g = self.G
+            self.G = np.full((g.shape[0], cap), np.nan)
+            self.G[:, :self.n] = g[:, :self.n]
 
     def _forget(self):
         """Drop all rows: the next sync rebuilds from the documents."""
@@ -184,8 +210,12 @@ class TrialHistory(object):
         self._obj_ok = False    # Y holds the objectives of every row not in _touched
         self._touched = set()   # rows whose document was (re)read since Y was
         self._obj_dirty = 0     # rows of Y >= this differ from the device copy
+        self._obj_loss = False  # Y is the row of the losses (constraints without objectives)
+        self._con_ok = False    # the same three for G
+        self._con_dirty = 0
         # what the device loss column holds: None the losses, M a ranking, (M, hv) a
-        # ranking with the hypervolume order inside the front
+        # ranking with the hypervolume order inside the front, (M or 'loss', hv, C)
+        # a constrained ranking
         self._dev_mode = None
         self._dev = None        # weakref to the plan holding the device copy
         self._plain = True      # rows == visible documents, integer tids ascending
@@ -227,14 +257,19 @@ class TrialHistory(object):
         self._touched.add(r)
 
     # -- sync ----------------------------------------------------------------
-    def sync(self, trials, objectives=None, hypervolume=False):
+    def sync(self, trials, objectives=None, hypervolume=False, constraints=None):
         """Bring the columns up to date with ``trials.trials``.  ``objectives``
         = M: also the objective store ``Y[M][cap]``, from every ok trial's
         ``result['objectives']`` (ValueError naming the tid where an ok trial
         has none, or not M of them); ``push`` then ranks the device history by
         Pareto dominance instead of by the loss.  ``hypervolume``: the front
-        is ordered by hypervolume subset selection (``check_hypervolume``)."""
+        is ordered by hypervolume subset selection (``check_hypervolume``).
+        ``constraints`` = C: also the constraint store ``G[C][cap]``, from every
+        ok trial's ``result['constraints']`` under the same rules (NaN for any
+        other trial); ``push`` then ranks by constrained dominance, over the
+        objectives or, without them, over the single row of the losses."""
         objectives = check_objectives(objectives)
+        constraints = check_constraints(constraints)
         self.hv = check_hypervolume(hypervolume, objectives)
         view = trials.trials
         store = getattr(trials, '_store', None)
@@ -261,27 +296,47 @@ class TrialHistory(object):
         self._jgen = jgen
         self._jpos = jlen if fresh else 0
         self._seen = len(view)
-        self._sync_objectives(objectives)
+        self._sync_objectives(objectives, constraints)
         return self
 
-    def _sync_objectives(self, M):
+    def _sync_objectives(self, M, C=None):
         """The objective store after the columns: the rows read since the last
         sync when that one kept a store of M objectives too, every row
         otherwise (a rebuild, a first call, another M, a call without
-        objectives in between)."""
+        objectives in between).  The constraint store by the same rule; with C
+        and no M the objective store is the row of the losses."""
         self.M = M
-        if M is None:
+        self.C = C
+        if C is None:
+            self._con_ok = False
+        if M is None and C is None:
             self._obj_ok = False
             self._touched.clear()
             return
-        full = not self._obj_ok or self.Y is None or self.Y.shape != (M, self.cap)
+        touched = sorted(r for r in self._touched if r < self.n)
+        from_loss = M is None
+        Me = 1 if from_loss else M
+        full = (not self._obj_ok or self.Y is None or self.Y.shape != (Me, self.cap) or
+                self._obj_loss != from_loss)
         if full:
-            self.Y = np.full((M, self.cap), np.nan)
-        rows = range(self.n) if full else sorted(r for r in self._touched if r < self.n)
+            self.Y = np.full((Me, self.cap), np.nan)
+        rows = range(self.n) if full else touched
         self._obj_ok = False        # (until every row is read: an error leaves a full re-read)
+        self._obj_loss = from_loss
         for r in rows:
-            self.Y[:, r] = _objectives_of(self.docs[r], M, self.tids[r])
+            self.Y[:, r] = (self.losses[r] if from_loss else
+                            _objectives_of(self.docs[r], M, self.tids[r]))
         self._obj_dirty = 0 if full else min([self._obj_dirty] + list(rows))
+        if C is not None:
+            full = not self._con_ok or self.G is None or self.G.shape != (C, self.cap)
+            if full:
+                self.G = np.full((C, self.cap), np.nan)
+            rows = range(self.n) if full else touched
+            self._con_ok = False
+            for r in rows:
+                self.G[:, r] = _objectives_of(self.docs[r], C, self.tids[r], 'constraints')
+            self._con_dirty = 0 if full else min([self._con_dirty] + list(rows))
+            self._con_ok = True
         self._touched.clear()
         self._obj_ok = True
 
@@ -407,10 +462,11 @@ class TrialHistory(object):
         ``plan``'s device history."""
         if self._dev is None or self._dev() is not plan or \
                 getattr(plan, '_history_owner', None) is not self:
-            self._vals_dirty = self._loss_dirty = self._obj_dirty = 0
+            self._vals_dirty = self._loss_dirty = self._obj_dirty = self._con_dirty = 0
             self._dev_mode = None
         r0 = min(self._vals_dirty, self.n)
-        if self.M is None:
+        mode = None
+        if self.M is None and self.C is None:
             if self._dev_mode is not None:
                 self._loss_dirty = 0        # the column holds a ranking: every loss goes again
             l0 = min(self._loss_dirty, r0, self.n)
@@ -422,7 +478,10 @@ class TrialHistory(object):
             plan.update_history(self.n, r0, self.vals, self.active, self.cap, self.n,
                                 self.losses)
             mode = self.M if self.hv is False else (self.M, self.hv)
-            o0 = min(self._obj_dirty, self.n) if self._dev_mode == mode else 0
+            if self.C is not None:
+                mode = ('loss' if self.M is None else self.M, self.hv, self.C)
+            same = self._dev_mode == mode
+            o0 = min(self._obj_dirty, self.n) if same else 0
             # the setting goes before the ranking that reads it; a plan that
             # never saw one is off (Plan._hv_on), and is not told so again
             ref = self.reference()
@@ -430,9 +489,16 @@ class TrialHistory(object):
                 plan.set_hv(ref, self.M, HV_N_PICK, HV_N_SAMPLES, HV_SEED, HV_METHOD)
             elif getattr(plan, '_hv_on', False):
                 plan.set_hv(None)
+            # the constraints go before the ranking that reads them too
+            if self.C is not None:
+                plan.set_constraints(self.G, n=self.n,
+                                     con0=min(self._con_dirty, self.n) if same else 0)
+                self._con_dirty = self.n
+            elif getattr(plan, '_con_on', False):
+                plan.set_constraints(None)
             plan.set_objectives(self.Y, n=self.n, obj0=o0)
             self._obj_dirty = self.n
-        self._dev_mode = self.M if self.M is None or self.hv is False else (self.M, self.hv)
+        self._dev_mode = mode
         plan._history_owner = self
         self._dev = weakref.ref(plan)
         self._vals_dirty = self.n

@@ -37,7 +37,8 @@ import numpy as np
 
 from . import _engine as E
 from . import rand, rstream
-from .history import TrialHistory, check_objectives, check_hypervolume, HV_N_SAMPLES
+from .history import (TrialHistory, check_objectives, check_hypervolume, check_constraints,
+                      HV_N_SAMPLES)
 
 logger = logging.getLogger(__name__)
 
@@ -150,7 +151,7 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             rng_stream='philox', startup_stream='numpy', engine=None, objectives=None,
-            hypervolume=False):
+            hypervolume=False, constraints=None):
     """hyperopt/tpe.py:804-897 on the GPU, one document per id in
     ``new_ids``.  ``linear_forgetting`` is accepted and, as in the reference
     (tpe.py:809), not used: LF is fixed at 25.  The first ``n_startup_jobs``
@@ -178,9 +179,22 @@ def suggest(new_ids, domain, trials, seed,
     they are all equal); a sequence of M finite floats: that reference point;
     ``False`` (default): the order of DESIGN 5.17.  Anything else, or
     ``hypervolume`` without ``objectives``, is a ValueError.  With M = 1 the
-    setting is ignored."""
+    setting is ignored.
+
+    ``constraints=C`` (constrained TPE): every ok trial also
+    reports ``result['constraints']``, a sequence of C numbers known only after
+    it ran, feasible when every one is <= 0 (an ok trial without it, or with
+    another length, is a ValueError naming the tid).  The split then ranks the
+    history by constrained dominance (``constraint_ranks``): feasible trials
+    first, in the order they have without constraints -- by the loss, or with
+    ``objectives=M`` by Pareto dominance --, then infeasible trials by their
+    total violation ``sum of max(g, 0)`` whatever their loss, then pending
+    ones.  With every trial feasible the suggestions are those of
+    ``constraints=None``.  Calls with and without ``constraints`` may alternate
+    on one domain and one trials object."""
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    constraints = check_constraints(constraints)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -189,7 +203,7 @@ def suggest(new_ids, domain, trials, seed,
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
         startup = hist.n < n_startup_jobs
     if startup:
         # the reference's RandomState prior stream (numpy), or device prior
@@ -197,8 +211,9 @@ def suggest(new_ids, domain, trials, seed,
         return rand.suggest(new_ids, domain, trials, seed, rng_stream=startup_stream)
     with st.lock:
         engine = engine or E.default_engine()
-        if hist.M != objectives or hist.hv != hypervolume:    # (another thread's call in between)
-            hist.sync(trials, objectives, hypervolume)
+        if hist.M != objectives or hist.hv != hypervolume or hist.C != constraints:
+            # (another thread's call in between)
+            hist.sync(trials, objectives, hypervolume, constraints)
         plan = st.plan_for(domain, hist.n, engine)
         hist.push(plan)
         seeds = batch_seeds(seed, len(new_ids))
@@ -391,7 +406,7 @@ def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate
 
 def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
                   gamma=_default_gamma, engine=None, return_terms=False, multivariate=False,
-                  objectives=None, hypervolume=False):
+                  objectives=None, hypervolume=False, constraints=None):
     """What the fitted TPE model thinks of configurations the caller holds.
 
     The history of ``trials`` is synced, pushed and fitted as ``suggest``
@@ -424,16 +439,19 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
 
     ``objectives=M``: the model is fitted on the Pareto ranking of the
     trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
-    hypervolume order inside the front (``suggest``)."""
+    hypervolume order inside the front (``suggest``).  ``constraints=C``: the
+    history is ranked by constrained dominance over the trials'
+    ``result['constraints']`` (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    constraints = check_constraints(constraints)
     cs = domain.space
     as_dicts = not isinstance(configs, np.ndarray)
     vals, present = config_columns(cs, configs)
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
         if hist.n == 0:
             raise ValueError('score_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
@@ -526,7 +544,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
                       prior_weight=_default_prior_weight,
                       n_startup_jobs=_default_n_startup_jobs,
                       gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False,
-                      objectives=None, hypervolume=False):
+                      objectives=None, hypervolume=False, constraints=None):
     """``algo=`` for a constrained or discrete search: the next trials are the
     ``len(new_ids)`` configurations of ``pool`` the fitted model scores
     highest (``score_configs``' EI), distinct, ties to the lower pool index,
@@ -541,10 +559,13 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     (True or 'groups'): the pool is ranked by ``score_configs`` with that
     argument.  ``objectives=M``: the model is fitted on the Pareto ranking of
     the trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with
-    the hypervolume order inside the front (``suggest``)."""
+    the hypervolume order inside the front (``suggest``).  ``constraints=C``: the
+    history is ranked by constrained dominance over the trials'
+    ``result['constraints']`` (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    constraints = check_constraints(constraints)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -555,7 +576,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     k = len(new_ids)
     with st.lock:
         pl = _pool_for(st, cs, pool)
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
         if hist.n < n_startup_jobs:
             if pl.m < k:
                 raise ValueError('the pool holds %d configurations, %d asked for' % (pl.m, k))
@@ -584,7 +605,7 @@ STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
 
 def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
                    gamma=_default_gamma, engine=None, begin=0, as_dicts=False,
-                   multivariate=False, objectives=None, hypervolume=False):
+                   multivariate=False, objectives=None, hypervolume=False, constraints=None):
     """``n`` whole configurations drawn from the fitted model's *below*
     mixtures, each with its joint EI (``score_configs``' total of it).
 
@@ -608,14 +629,17 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     ``score_configs(..., multivariate='groups')``'s
     (tpe_plan_group_sample_points).  ``objectives=M``: the model is fitted on
     the Pareto ranking of the trials' ``result['objectives']`` (``suggest``);
-    ``hypervolume``: with the hypervolume order inside the front (``suggest``)."""
+    ``hypervolume``: with the hypervolume order inside the front (``suggest``).
+    ``constraints=C``: the history is ranked by constrained dominance over the
+    trials' ``result['constraints']`` (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    constraints = check_constraints(constraints)
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
@@ -756,7 +780,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
                   startup_stream='numpy', engine=None, multivariate=False, batch='topk',
-                  objectives=None, hypervolume=False):
+                  objectives=None, hypervolume=False, constraints=None):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -803,10 +827,13 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
 
     ``objectives=M``: the model is fitted on the Pareto ranking of the
     trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
-    hypervolume order inside the front (``suggest``)."""
+    hypervolume order inside the front (``suggest``).  ``constraints=C``: the
+    history is ranked by constrained dominance over the trials'
+    ``result['constraints']`` (``suggest``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    constraints = check_constraints(constraints)
     if batch not in ('topk', 'pending'):
         raise ValueError("batch must be 'topk' or 'pending', got %r" % (batch,))
     if batch == 'pending' and multivariate != 'groups':
@@ -821,7 +848,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     k = len(new_ids)
     n = int(n_configs)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
         startup = hist.n < n_startup_jobs
     if startup:
         if feasible is None:
@@ -831,8 +858,9 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
     P = len(cs.labels)
     with st.lock:
-        if hist.M != objectives or hist.hv != hypervolume:    # (another thread's call in between)
-            hist.sync(trials, objectives, hypervolume)
+        if hist.M != objectives or hist.hv != hypervolume or hist.C != constraints:
+            # (another thread's call in between)
+            hist.sync(trials, objectives, hypervolume, constraints)
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
         draw = (plan.group_sample_points_device if multivariate == 'groups' else
@@ -875,27 +903,33 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
 # --------------------------------------------------------------------------
 # multi-objective TPE: the Pareto ranking the split reads
 # --------------------------------------------------------------------------
-def _pareto(domain, trials, objectives, engine, hypervolume=False, want_hv=False):
+def _pareto(domain, trials, objectives, engine, hypervolume=False, want_hv=False,
+            constraints=None, want_v=False):
     """(docs, tids, dominated_by, dominates, surrogate) of the synced history,
-    ranked on the device; ``want_hv``: and ``Plan.hv_get``'s tuple."""
+    ranked on the device; ``want_hv``: and ``Plan.hv_get``'s tuple; ``want_v``:
+    and the violations (``Plan.constraint_get``)."""
     objectives = check_objectives(objectives)
-    if objectives is None:
-        raise ValueError('the Pareto ranking needs objectives=M')
+    constraints = check_constraints(constraints)
+    if objectives is None and constraints is None:
+        raise ValueError('the Pareto ranking needs objectives=M or constraints=C')
     hypervolume = check_hypervolume(hypervolume, objectives)
     st = _state(domain)
     none = (np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0, dtype=np.int32), 0)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
         if hist.n == 0:
             out = [], [], np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
-            return out + (none,) if want_hv else out
+            out = out + (none,) if want_hv else out
+            return out + (np.zeros(0),) if want_v else out
         plan = st.plan_for(domain, hist.n, engine or E.default_engine())
         hist.push(plan)
         out = (list(hist.docs), list(hist.tids)) + plan.pareto_get(hist.n)
-        return out + (plan.hv_get(),) if want_hv else out
+        out = out + (plan.hv_get(),) if want_hv else out
+        return out + (plan.constraint_get(hist.n),) if want_v else out
 
 
-def pareto_ranks(domain, trials, objectives, engine=None, hypervolume=False):
+def pareto_ranks(domain, trials, objectives=None, engine=None, hypervolume=False,
+                 constraints=None):
     """(tids, dominated_by, dominates, surrogate) of the history of
     ``trials`` under ``objectives=M``, read back from the device
     (tpe_plan_pareto_get): per trial in tid order the number of complete
@@ -905,33 +939,63 @@ def pareto_ranks(domain, trials, objectives, engine=None, hypervolume=False):
     +inf objective, is pending: counts 0 and surrogate +inf.  With
     ``hypervolume`` the surrogate of a front trial is its place in the
     hypervolume subset selection (``suggest``, ``hv_picks``); the selection's
-    sample seed is fixed, so the ranks are a function of the history alone."""
-    return _pareto(domain, trials, objectives, engine, hypervolume)[1:]
+    sample seed is fixed, so the ranks are a function of the history alone.
+    With ``constraints=C`` the counts and the surrogate are those of
+    constrained dominance (``constraint_ranks``; ``objectives`` may then be
+    None: the single objective is the loss)."""
+    return _pareto(domain, trials, objectives, engine, hypervolume, constraints=constraints)[1:]
 
 
-def pareto_front(domain, trials, objectives, engine=None, hypervolume=False):
+def pareto_front(domain, trials, objectives=None, engine=None, hypervolume=False,
+                 constraints=None):
     """The trial documents on the Pareto front of ``result['objectives']``
     -- complete trials no complete trial dominates -- in tid order
     (``hypervolume`` orders the front's rows in the split and leaves the front
-    as it is)."""
-    docs, _, by, _, s = _pareto(domain, trials, objectives, engine, hypervolume)
-    return [docs[r] for r in np.flatnonzero((by == 0) & np.isfinite(s))]
+    as it is).  With ``constraints=C``: the feasible trials no feasible trial
+    dominates; none when no trial is feasible."""
+    out = _pareto(domain, trials, objectives, engine, hypervolume, constraints=constraints,
+                  want_v=constraints is not None)
+    docs, by, s = out[0], out[2], out[4]
+    keep = (by == 0) & np.isfinite(s)
+    if constraints is not None:
+        keep &= out[5] == 0
+    return [docs[r] for r in np.flatnonzero(keep)]
 
 
-def hv_picks(domain, trials, objectives, hypervolume=True, engine=None):
+def hv_picks(domain, trials, objectives=None, hypervolume=True, engine=None, constraints=None):
     """(tids, gains, alive) of the hypervolume subset selection inside the
     Pareto front of ``trials`` (tpe_plan_hv_get), in pick order:
     the tids picked, what each added to the hypervolume given the picks
     before it -- the exact area with two objectives, the Monte-Carlo estimate
     ``vol * alive / S`` with more -- and its alive samples (-1: exact).  At most
     32 picks; fewer when the front inside the reference point is smaller;
-    none with ``objectives=1``, ``hypervolume=False`` or no complete trial."""
+    none with ``objectives=1``, ``hypervolume=False`` or no complete trial.
+    With ``constraints=C`` the front is that of constrained dominance: the
+    feasible front, or without a feasible trial the trials of least violation."""
     _, tids, _, _, _, (picks, keys, counts, R) = _pareto(domain, trials, objectives, engine,
-                                                       hypervolume, want_hv=True)
+                                                       hypervolume, want_hv=True,
+                                                       constraints=constraints)
     picks, keys, counts = picks[:R], keys[:R].copy(), counts[:R]
     mc = counts >= 0
     keys[mc] = keys[mc] / float(HV_N_SAMPLES)
     return [tids[int(r)] for r in picks], keys, counts
+
+
+def constraint_ranks(domain, trials, constraints, objectives=None, engine=None):
+    """(tids, violation, feasible, dominated_by, dominates, s) of the history of
+    ``trials`` under ``constraints=C``, read back from the device
+    (tpe_plan_constraint_get, tpe_plan_pareto_get), per trial in tid order:
+    the total violation ``sum of max(g, 0)`` over ``result['constraints']``
+    (+inf with a NaN constraint or for a trial that is not ok), whether it is
+    0, the complete trials that c-dominate it, those it c-dominates, and the
+    surrogate loss the split ranks by.  j c-dominates i when it violates less,
+    or when both are feasible and j dominates i -- by ``result['objectives']``
+    with ``objectives=M``, by the loss without."""
+    if check_constraints(constraints) is None:
+        raise ValueError('constraint_ranks needs constraints=C')
+    _, tids, by, of, s, v = _pareto(domain, trials, objectives, engine, constraints=constraints,
+                                    want_v=True)
+    return tids, v, v == 0, by, of, s
 
 
 # --------------------------------------------------------------------------

@@ -609,6 +609,42 @@ int tpe_plan_set_hv(tpe_plan_t p, int32_t mode, const double *ref, int32_t n_obj
 int tpe_plan_hv_get(tpe_plan_t p, int32_t *picks, double *keys, int32_t *counts,
                     int32_t *n_picked, int32_t cap);
 
+/* ---- constrained TPE: the history ranked by constrained dominance ----------
+ * (DESIGN 5.19).  Beside the objective matrix stands a constraint matrix
+ * G[n_con][n], known only after a trial has run; row i is feasible when every
+ * G[c][i] <= 0.  Its violation is
+ *   v[i] = ((0.0 + max0(G[0][i])) + max0(G[1][i])) + ...,  max0(g) = g > 0 ? g : 0.0
+ * added in ascending c in plain fp64 (-inf and -0.0 add 0; a +inf constraint
+ * or an overflowing sum gives +inf), and +inf when any G[c][i] is NaN.  v = 0
+ * is feasible.  Completeness is 5.17's and reads Y alone.  For complete rows,
+ * j c-dominates i when v[j] < v[i], or when v[j] = v[i] = 0 and j dominates i
+ * by 5.17's rule.  dominated_by, dominates and s are 5.17's with c-dominance in
+ * the place of dominance: feasible rows first in 5.17's order, then infeasible
+ * rows by ascending violation whatever their objectives, then pending rows.
+ * With every row feasible the counts and the column are 5.17's bit for bit.
+ *
+ * tpe_plan_set_constraints copies rows [con0, n) of every constraint from G
+ * (row r of constraint c at G[c * ld + (r - con0)]) into the plan's constraint
+ * matrix (allocated by the first call with n_con > 0, at the plan's trial
+ * capacity; rows below con0 are those of the last call, which must have had
+ * the same n_con and at least con0 rows).  It ranks nothing itself: the next
+ * tpe_plan_set_objectives (and every later one, until n_con = 0) computes v
+ * and counts by c-dominance in the place of dominance; tpe_plan_set_hv's
+ * selection then runs on those counts.  n_con = 0 switches the mode off: no
+ * other argument is read, nothing is launched, nothing is allocated.
+ * TPE_E_INVALID: n_con outside [0, TPE_MAX_CON], n other than the history
+ * length, con0 outside [0, n] or above the rows held, ld < n - con0, a null G;
+ * and, while the mode is on, a tpe_plan_set_objectives over more rows than the
+ * constraint matrix holds (the loss column then stays what it was).         */
+#define TPE_MAX_CON 16
+int tpe_plan_set_constraints(tpe_plan_t p, const double *G, int32_t n_con, int64_t n,
+                             int64_t ld, int64_t con0, int32_t on_device, void *stream);
+
+/* Host copy of v[n] of the last tpe_plan_set_objectives, which must have run
+ * with constraints over n rows (TPE_E_INVALID otherwise).  tpe_plan_pareto_get
+ * returns that ranking's c-dominance counts and column.  Waits for the device. */
+int tpe_plan_constraint_get(tpe_plan_t p, double *violation, int64_t n);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
