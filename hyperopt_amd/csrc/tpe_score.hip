@@ -35,6 +35,7 @@
 #include "tpe_draw.hpp"
 #include "tpe_lpdf.hpp"
 #include "tpe_switches.hpp"
+#include "tpe_tie_plan.hpp"
 
 namespace tpe {
 
@@ -2679,6 +2680,297 @@ void k_score_wave_tie(ScoreArgs A) {
                                                                                 nblk, true);
   }
 }
+
+// The lean form of k_score_wave_tie (Switches::tie_lean): the same gathered
+// blocks, list entries, records, tickets and merge, compiled for what the
+// launch fixes -- prune mode 3 on the 16-wide moment tables, bucketed
+// candidates with their positions, the score alone (no lpdf outputs), no L2
+// warm-up (tie_lean_form: launch_class takes this kernel only then) -- with
+// the slot's state worked out once per persistent block instead of once per
+// gathered block.  What the block's waves need of the slot waits in LDS
+// (TieSlot) and each phase reads its own part there, so nothing of it stays
+// live across the component loops; the small mixtures' coefficients
+// (lse_small) are staged once, and the block's arrival counter counts on from
+// one gathered block to the next instead of being cleared behind a second
+// barrier.  The sums are score_tile's: the same helpers on the same operands.
+struct TieSlot {
+  double prior_mu;
+  int32_t K[2], probe[2];
+  float cmax[2], amin[2];
+  int32_t cnt;
+};
+struct TieSmem {
+  double2 wpart[2][kWaves][2][64];  // per-wave sums (below, above)
+  double xs[kWaves][2][64];         // each wave's candidates, till its finalize
+  double best_s[kWaves], best_v[kWaves];
+  int64_t best_i[kWaves];
+  uint32_t arrive;
+  double small[2][4][kSmallMix];
+  double small_m[2];
+  TieSlot slot;
+};
+// a word of the staged slot state as a scalar, read where it is needed (never
+// kept from an earlier read)
+__device__ __forceinline__ int32_t lds_s32(const int32_t &v) {
+  return __builtin_amdgcn_readfirstlane(*(const volatile int32_t *)&v);
+}
+__device__ __forceinline__ float lds_sf32(const float &v) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int32_t, *(const volatile float *)&v)));
+}
+
+// The two logarithms of a tile, out of line (as box_muller_ool): inlined, their
+// fp64 polynomial constants -- 17 register pairs -- are formed ahead of the
+// persistent loop and held, or spilled to scratch, across every component loop
+__device__ __attribute__((noinline)) double tie_log_ool(double x) { return fast_log(x); }
+__device__ __attribute__((noinline)) double tie_log2_ratio_ool(double num, double den) {
+  return fast_log2(num / den);
+}
+
+// gathered block `tile` of the slot's `ntiles`, the persistent block's `it`-th
+template <bool LOGN, bool CENSUS>
+__device__ __forceinline__ void tie_tile_lean(const ScoreArgs &A, TieSmem &sm, int slot, int hp,
+                                              int s, int tile, int ntiles, uint32_t it) {
+  constexpr int KR = 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wvs = __builtin_amdgcn_readfirstlane(wave);
+  const int64_t sh = (int64_t)s * A.n_hp + hp;
+  const int64_t sb = 2 * (int64_t)hp, sa = sb + 1;
+  const int64_t coff = (int64_t)s * A.cand_sstride + (int64_t)(A.cand_slot0 + slot) * A.n_cand;
+  // the wave's list entry (a wave past the list's end takes no candidates)
+  const int e = tile * kWaves + wvs;
+  bool valid[KR];
+  double y[KR];
+  {
+    const bool cold = e >= lds_s32(sm.slot.cnt);
+    const int64_t wt0 = cold ? 0 : (int64_t)A.tie_list[sh * A.pstride * kWaves + e] * (64 * KR);
+    const double mu = sm.slot.prior_mu;
+#pragma unroll
+    for (int r = 0; r < KR; ++r) {
+      const int64_t li = wt0 + r * 64 + lane;
+      valid[r] = li < A.n_cand && !cold;
+      const double x = valid[r] ? (A.cand + coff)[li] : (LOGN ? 1.0 : 0.0);
+      sm.xs[wave][r][lane] = x;
+      y[r] = (LOGN ? tie_log_ool(x) : x) - mu;
+    }
+  }
+  int nvalid = 0;
+#pragma unroll
+  for (int r = 0; r < KR; ++r) nvalid += valid[r] ? 1 : 0;
+  LseCensus lcen{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  const LseRange rg = lse_range<KR>(y, valid);
+#pragma unroll
+  for (int mix = 0; mix < 2; ++mix) {
+    LseAcc acc[KR];
+#pragma unroll
+    for (int r = 0; r < KR; ++r) acc[r] = LseAcc{-INFINITY, 0.0};
+    const int K = lds_s32(sm.slot.K[mix]);
+    if (!rg.any) {
+      // (nothing to sum: the empty sums, never read)
+    } else if (K <= kSmallMix) {
+      lse_small<KR>(sm.small[mix], K, y, acc, sm.small_m[mix]);
+      if constexpr (CENSUS) {
+        lcen.total += (uint32_t)(K * nvalid);
+        lcen.exec += (uint32_t)(K * nvalid);
+      }
+    } else {
+      const int64_t ms = mix ? sa : sb;
+      const Coef *__restrict__ cm = A.coef + ms * A.kcap;
+      const int probe = lds_s32(sm.slot.probe[mix]);
+      const LseWindow win = lse_window<KR>(uniform_ptr(cm), probe, K, y, valid, rg);
+      Stage stv{};
+      stv.genv = A.coefe ? A.coefe + ms * (A.kcap / kCoefBlock) : nullptr;
+      stv.tight = A.lse_tight && K >= kRangeMinK;
+      bool shifted = false;
+      if (K >= A.lse_shift_min && win.thr > -INFINITY) {
+        const CoefM *mt16 = A.coefm + ms * mom_stride(A.kcap);
+        const CoefM8 *mth = A.lse_momh ? A.coefmh + ms * mom_stride(A.kcap) : nullptr;
+        shifted = lse_chunks_shifted<KR, CENSUS, 1, true, false, 16>(
+            uniform_ptr(cm), cm, 0, K, y, valid, acc, win, nvalid, lcen,
+            uniform_ptr32(A.coef32 + ms * (A.kcap / kCoefBlock)), mt16, nullptr, stv,
+            lds_sf32(sm.slot.cmax[mix]), lds_sf32(sm.slot.amin[mix]), probe, mth);
+      }
+      if (!shifted)
+        lse_chunks<KR, CENSUS, 1, true>(uniform_ptr(cm), cm, 0, K, y, acc, true, win, nvalid, lcen,
+                                        uniform_ptr32(A.coef32 + ms * (A.kcap / kCoefBlock)), stv);
+    }
+#pragma unroll
+    for (int r = 0; r < KR; ++r) sm.wpart[mix][wave][r][lane] = make_double2(acc[r].m, acc[r].s);
+  }
+  if constexpr (CENSUS) {
+    unsigned long long c2[9] = {lcen.total, lcen.exec, lcen.shift, lcen.f32, lcen.retry,
+                                lcen.wide, lcen.mom, lcen.mom8, lcen.momh};
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c2[q] += __shfl_xor(c2[q], o, 64);
+    }
+    if (lane == 0) {
+      atomicAdd(A.census + 3, c2[0]);
+      atomicAdd(A.census + 4, c2[2]);
+      atomicAdd(A.census + 5, c2[1]);
+      atomicAdd(A.census + 6, c2[3]);
+      atomicAdd(A.census + 7, c2[4]);
+      atomicAdd(A.census + 8, c2[5]);
+      atomicAdd(A.census + 9, c2[6]);
+      atomicAdd(A.census + 10, c2[7]);
+      atomicAdd(A.census + 11, c2[8]);
+    }
+  }
+
+  // ---- finalize (score_tile's: EI, argmax, numpy semantics): the wave's slots
+  // again from its list entry, its candidates and sums back from LDS
+  double best_s = NAN, best_v = NAN;
+  int64_t best_i = -1;
+  {
+    asm volatile("" ::: "memory");  // (reloads, not the registers above)
+    const bool cold = e >= lds_s32(sm.slot.cnt);
+    const int64_t wt0 = cold ? 0 : (int64_t)A.tie_list[sh * A.pstride * kWaves + e] * (64 * KR);
+    const int32_t *__restrict__ cpos = A.cand_pos + coff;
+#pragma unroll
+    for (int r = 0; r < KR; ++r) {
+      const int64_t li = wt0 + r * 64 + lane;
+      if (!(li < A.n_cand && !cold)) continue;
+      const double x = sm.xs[wave][r][lane];
+      const double LN2 = 0.6931471805599453;
+      const double2 b = sm.wpart[0][wave][r][lane];
+      const double2 a = sm.wpart[1][wave][r][lane];
+      const double sc = (b.x == -INFINITY || a.x == -INFINITY)
+                            ? NAN
+                            : ((b.x - a.x) + tie_log2_ratio_ool(b.y, a.y)) * LN2;
+      take_better(best_s, best_v, best_i, sc, x, A.cand_begin + (int64_t)cpos[li]);
+    }
+  }
+  wave_best(best_s, best_v, best_i);
+  // the block's argmax over its waves, without a barrier (score_tile).  The
+  // counter is never cleared: the last arrival of the block's it-th gathered
+  // block is its 8 (it + 1)-th
+  if (lane == 0) {
+    sm.best_s[wave] = best_s;
+    sm.best_v[wave] = best_v;
+    sm.best_i[wave] = best_i;
+  }
+  int last = 0;
+  if (lane == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    last = __hip_atomic_fetch_add(&sm.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ==
+           (it + 1u) * (uint32_t)kWaves - 1u;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  if (!__shfl(last, 0, 64)) return;
+  const int w = lane < kWaves ? lane : 0;
+  best_s = sm.best_s[w];
+  best_v = sm.best_v[w];
+  best_i = lane < kWaves ? sm.best_i[w] : -1;
+  wave_best(best_s, best_v, best_i);
+  Partial *pbase = A.partial + sh * A.pstride;
+  int is_last = 0;
+  if (lane == 0) {
+    // (the tile records' protocol of score_tile: sc1 stores, drain, ticket)
+    gu64 *rec = (gu64 *)(uintptr_t)(pbase + tile);
+    __hip_atomic_store(rec + 0, dbits(best_s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(rec + 1, dbits(best_v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(rec + 2, (uint64_t)best_i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    gu32 *tk = (gu32 *)(uintptr_t)(A.ticket + sh);
+    const uint32_t t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = (t == (uint32_t)ntiles - 1) ? 1 : 0;
+    if (is_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  is_last = __shfl(is_last, 0, 64);
+  if (!is_last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // keeps the loads below the ticket
+  double fs = NAN, fv = NAN;
+  int64_t fi = -1;
+  for (int i = lane; i < ntiles; i += 64) {
+    gu64 *rec = (gu64 *)(uintptr_t)(pbase + i);
+    const double qs = bitsd(__hip_atomic_load(rec + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const double qv = bitsd(__hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const int64_t qi = (int64_t)__hip_atomic_load(rec + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    take_better(fs, fv, fi, qs, qv, qi);
+  }
+  wave_best(fs, fv, fi);
+  if (lane == 0) {
+    Partial *rr = A.results + sh;
+    if (!(A.accumulate && better(rr->score, rr->index, fs, fi))) *rr = Partial{fs, fv, fi, 1, 0};
+  }
+}
+
+// 4 waves per SIMD: an 8-wave block takes 2 waves of each SIMD, so a cap of 5
+// holds the same two blocks per CU as 4 with 96 registers instead of 127; at 4
+// the <false> form has no scratch, at 5 and 6 it spills 69 and 106 VGPRs
+// 
+#ifndef TPE_TIE_LEAN_EU
+#define TPE_TIE_LEAN_EU 4
+#endif
+template <bool CENSUS>
+__global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu(TPE_TIE_LEAN_EU)))
+void k_score_wave_tie_lean(ScoreArgs A) {
+  __shared__ TieSmem sm;
+  const int s = blockIdx.z;
+  int row = blockIdx.y;
+  const int g = row_group(A, row);
+  int slot = A.grp_slot0[g] + row;
+  if (A.compact) {
+    slot = active_slot(A, s, A.grp_slot0[g], A.grp_slots[g], row);
+    if (slot < 0) return;
+  }
+  const int hp = A.level_hps[slot];
+  const int cnt = A.tie_cnt[(int64_t)s * A.n_hp + hp];
+  const int nblk = (cnt + kWaves - 1) / kWaves;
+  if ((int)blockIdx.x >= nblk) return;  // (block-uniform; an inactive hp has no entries)
+  const bool lw = A.grp_kind[g] == KIND_LSE_LW;
+  // the slot's state, once: wave 0 stages the small mixtures (score_tile's
+  // staging, the same values), thread 64 the scalars
+  if (threadIdx.x < 2 * kSmallMix) {
+    const int q = threadIdx.x / kSmallMix, k = threadIdx.x % kSmallMix;
+    const int Kq = A.info[2 * (int64_t)hp + q].K;
+    const bool cp = Kq <= kSmallMix && k < Kq;
+    double ca = 0.0, cb = 0.0, cg = 0.0, pk = -INFINITY;
+    if (cp) {
+      const double *t = reinterpret_cast<const double *>(A.coef + (2 * (int64_t)hp + q) * A.kcap);
+      ca = t[coef_off(k, 0)];
+      cb = t[coef_off(k, 1)];
+      cg = t[coef_off(k, 2)];
+      pk = ca - cb * cb / (4.0 * cg);
+    }
+#pragma unroll
+    for (int o = kSmallMix / 2; o > 0; o >>= 1) pk = fmax(pk, __shfl_xor(pk, o, 64));
+    const double mt = ceil(pk);
+    if (cp) {
+      sm.small[q][0][k] = ca;
+      sm.small[q][1][k] = cb;
+      sm.small[q][2][k] = cg;
+      sm.small[q][3][k] = ca - mt;
+    }
+    if (k == 0) sm.small_m[q] = mt;
+  } else if (threadIdx.x == 64) {
+    sm.arrive = 0u;
+    sm.slot.prior_mu = A.hps[hp].prior_mu;
+    sm.slot.cnt = cnt;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const MixInfo mi = A.info[2 * (int64_t)hp + q];
+      sm.slot.K[q] = mi.K;
+      sm.slot.probe[q] = mi.probe;
+      sm.slot.cmax[q] = mi.env_cmax;
+      sm.slot.amin[q] = mi.env_amin;
+    }
+  }
+  // (a loop per kind: each keeps one tile body's registers)
+  uint32_t it = 0;
+  if (lw) {
+    for (int j = blockIdx.x; j < nblk; j += gridDim.x, ++it) {
+      __syncthreads();  // the staged state; the last gathered block's LDS records have been read
+      tie_tile_lean<true, CENSUS>(A, sm, slot, hp, s, j, nblk, it);
+    }
+  } else {
+    for (int j = blockIdx.x; j < nblk; j += gridDim.x, ++it) {
+      __syncthreads();
+      tie_tile_lean<false, CENSUS>(A, sm, slot, hp, s, j, nblk, it);
+    }
+  }
+}
 // the same tiles of the slots scored from their Chebyshev tables (tab_on 2:
 // the operator form; MAP, tab_on 1: a suggest's per-wave map, score_tile TMAP)
 // (SCL: the operator form on the scalar-panel tab_eval, the default; the
@@ -3636,10 +3928,7 @@ static ScoreArgs select_groups(const ScoreArgs &a, int cls) {
   return b;
 }
 
-// k_score_wave_tie's persistent blocks per CU.  Config 4, ms per step at
-// 4 / 6 / 8 / 12 / 16 / 32: 26.86 / 26.52 / 26.44 / 26.33 / 26.29 / 26.29, two
-// rounds within 0.07 ms of each other (profiles/tiegather_blocks_sweep.txt)
-constexpr int kTieBlocksPerCu = 16;
+// (the direct pass's grid and its choice of kernel: tpe_tie_plan.hpp)
 
 // The table kernels' form (Switches::table_scalar, A/B): the scalar-panel
 // tab_eval -- k_table_map and k_score_table<., false, true> -- unless off, which
@@ -3720,15 +4009,16 @@ static hipError_t launch_class(const ScoreArgs &a, int cls, bool has_erf, hipStr
         k_tie_gather_lean<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
       else
         k_tie_gather<<<dim3((unsigned)rows, a.n_suggest), kGatherThreads, 0, st>>>(a);
-      // persistent blocks per slot: ~kTieBlocksPerCu blocks per CU over
-      // the launch's (row, suggestion) pairs, so that a single all-hot slot
-      // still fills the chip; never more than the slot has tiles
-      const int64_t per = ((int64_t)kTieBlocksPerCu * kNumCUs + (int64_t)rows * a.n_suggest - 1) /
-                          ((int64_t)rows * a.n_suggest);
-      const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntmax, per));
-      const dim3 gt(G, (unsigned)rows, a.n_suggest);
-      if (a.census) k_score_wave_tie<true><<<gt, kWaves * 64, 0, st>>>(a);
-      else k_score_wave_tie<false><<<gt, kWaves * 64, 0, st>>>(a);
+      // (Switches::tie_lean, A/B: off keeps k_score_wave_tie for every launch)
+      const bool lean = tie_lean_form(switches().tie_lean, a);
+      const dim3 gt(tie_grid(lean, rows, a.n_suggest, ntmax), (unsigned)rows, a.n_suggest);
+      if (lean) {
+        if (a.census) k_score_wave_tie_lean<true><<<gt, kWaves * 64, 0, st>>>(a);
+        else k_score_wave_tie_lean<false><<<gt, kWaves * 64, 0, st>>>(a);
+      } else {
+        if (a.census) k_score_wave_tie<true><<<gt, kWaves * 64, 0, st>>>(a);
+        else k_score_wave_tie<false><<<gt, kWaves * 64, 0, st>>>(a);
+      }
       return hipGetLastError();
     }
     if (m8) {
