@@ -55,6 +55,8 @@ EXPORTS = (
     'tpe_plan_set_objectives', 'tpe_plan_pareto_get', 'tpe_plan_pareto_shape',
     'tpe_plan_set_hv', 'tpe_plan_hv_get',
     'tpe_plan_set_constraints', 'tpe_plan_constraint_get',
+    'tpe_plan_ctpe_fit', 'tpe_plan_ctpe_score_points', 'tpe_plan_ctpe_sample_points',
+    'tpe_plan_ctpe_get_mixture', 'tpe_plan_ctpe_info',
 )
 
 BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
@@ -195,6 +197,13 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_hv_get': (C.c_int, [vp, vp, vp, vp, C.POINTER(i32), i32]),
             'tpe_plan_set_constraints': (C.c_int, [vp, vp, i32, i64, i64, i64, i32, vp]),
             'tpe_plan_constraint_get': (C.c_int, [vp, vp, i64]),
+            'tpe_plan_ctpe_fit': (C.c_int, [vp, vp, i32, i64, i64, i32, vp, vp, dbl, i32, vp]),
+            'tpe_plan_ctpe_score_points': (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp]),
+            'tpe_plan_ctpe_sample_points': (C.c_int, [vp, u64, i64, i64, i64, vp, vp, vp, vp, i32,
+                                                      vp]),
+            'tpe_plan_ctpe_get_mixture': (C.c_int, [vp, i32, i32, i32, _D, _D, _D, i64,
+                                                    C.POINTER(i64)]),
+            'tpe_plan_ctpe_info': (C.c_int, [vp, vp, vp, C.POINTER(i32)]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -682,6 +691,114 @@ class Plan(object):
         with e.lock:
             e.check(e.lib.tpe_plan_constraint_get(self.p, v.ctypes.data, n))
         return v
+
+    # ---- c-TPE: one pair of Parzen models per constraint (tpe_plan_ctpe_*)
+    def ctpe_fit(self, G, nb, ghat, n=None, prior_weight=1.0, lf=25, stream=None):
+        """Fit the objective's model with ``nb[0]`` good rows and one model per
+        constraint m with ``ghat[m] < 1`` on its key column (tpe_plan_ctpe_fit):
+        ``G`` float64 [C, ld] C-contiguous, ``nb`` / ``ghat`` of C + 1 entries,
+        ``n`` (default ld) the history length."""
+        e = self.engine
+        G = np.asarray(G)
+        if G.ndim != 2 or G.dtype != np.float64 or not G.flags.c_contiguous:
+            raise ValueError('constraints must be a C-contiguous float64 [C, ld] array')
+        c, ld = G.shape
+        nb = np.ascontiguousarray(nb, dtype=np.int32)
+        ghat = _f64(ghat)
+        if nb.shape != (c + 1,) or ghat.shape != (c + 1,):
+            raise ValueError('nb and ghat must hold C + 1 = %d entries' % (c + 1))
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_fit(self.p, G.ctypes.data, int(c),
+                                            ld if n is None else int(n), int(ld), 0,
+                                            nb.ctypes.data, ghat.ctypes.data,
+                                            float(prior_weight), int(lf), stream))
+
+    def ctpe_info(self):
+        """(live models in ascending order, the device's count of rows on each
+        one's feasible side) of the c-TPE fit (tpe_plan_ctpe_info)."""
+        e = self.engine
+        live = np.zeros(MAX_CON + 1, dtype=np.int32)
+        feas = np.zeros(MAX_CON + 1, dtype=np.int32)
+        k = C.c_int32(0)
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_info(self.p, live.ctypes.data, feas.ctypes.data,
+                                             C.byref(k)))
+        return live[:k.value].copy(), feas[:k.value].copy()
+
+    def ctpe_mixture(self, model, hp, side=0):
+        """``mixture`` of live model ``model`` (tpe_plan_ctpe_get_mixture)."""
+        e = self.engine
+        cap = max(self.max_trials + 1, 1 << 16)
+        w, mu, sg = np.empty(cap), np.empty(cap), np.empty(cap)
+        k = C.c_int64(0)
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_get_mixture(self.p, int(model), int(hp), int(side),
+                                                    _dp(w), _dp(mu), _dp(sg), cap, C.byref(k)))
+        k = k.value
+        return w[:k].copy(), mu[:k].copy(), sg[:k].copy()
+
+    def ctpe_score_points(self, vals, want_T=False, want_active=False, stream=None):
+        """acq[M] of M whole configurations under the c-TPE fit
+        (tpe_plan_ctpe_score_points), ``vals`` as ``score_points`` takes them;
+        with the ``want_`` flags also T[n_live, M] -- each live model's total --
+        and active[n_hp, M] uint8."""
+        e = self.engine
+        vals = _f64(vals)
+        if vals.ndim != 2 or vals.shape[0] != self.n_hp:
+            raise ValueError('configurations must be a [n_hp, M] array')
+        m = vals.shape[1]
+        acq = np.empty(m)
+        T = np.empty((MAX_CON + 1, m)) if want_T else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_score_points(
+                self.p, vals.ctypes.data, m, m, acq.ctypes.data,
+                T.ctypes.data if want_T else None,
+                active.ctypes.data if want_active else None, 0, stream))
+            if want_T:
+                T = T[:len(self.ctpe_info()[0])] if m else T[:0]
+        out = (acq,) + ((T,) if want_T else ()) + ((active,) if want_active else ())
+        return out[0] if len(out) == 1 else out
+
+    def ctpe_score_points_device(self, vals_ptr, m, ld, acq_ptr, T_ptr=0, active_ptr=0,
+                                 stream=None):
+        """The same on device memory: vals[n_hp][ld], acq[m], optional
+        T[n_live][ld] and active[n_hp][ld].  Stream-ordered."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_score_points(
+                self.p, vals_ptr, int(m), int(ld), acq_ptr, T_ptr or None, active_ptr or None, 1,
+                stream))
+
+    def ctpe_sample_points(self, seed, m, begin=0, want_T=False, want_active=False, stream=None):
+        """``m`` whole configurations drawn from the live models' below
+        mixtures in turn, with their acquisition (tpe_plan_ctpe_sample_points):
+        (vals[n_hp, m], acq[m][, T[n_live, m]][, active[n_hp, m]])."""
+        e = self.engine
+        m = int(m)
+        if m < 0:
+            raise ValueError('the number of configurations must not be negative')
+        vals = np.empty((self.n_hp, m))
+        acq = np.empty(m)
+        T = np.empty((MAX_CON + 1, m)) if want_T else None
+        active = np.empty((self.n_hp, m), dtype=np.uint8) if want_active else None
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), m, m, vals.ctypes.data,
+                acq.ctypes.data, T.ctypes.data if want_T else None,
+                active.ctypes.data if want_active else None, 0, stream))
+            if want_T:
+                T = T[:len(self.ctpe_info()[0])] if m else T[:0]
+        return (vals, acq) + ((T,) if want_T else ()) + ((active,) if want_active else ())
+
+    def ctpe_sample_points_device(self, seed, begin, m, ld, vals_ptr, acq_ptr, T_ptr=0,
+                                  active_ptr=0, stream=None):
+        """The same into device memory.  Stream-ordered."""
+        e = self.engine
+        with e.lock:
+            e.check(e.lib.tpe_plan_ctpe_sample_points(
+                self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
+                acq_ptr, T_ptr or None, active_ptr or None, 1, stream))
 
     def fit(self, gamma=0.25, prior_weight=1.0, lf=25, gamma_cap=25, stream=None):
         e = self.engine

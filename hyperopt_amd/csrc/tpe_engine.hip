@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "tpe_anneal.hpp"
+#include "tpe_ctpe.hpp"
 #include "tpe_group_plan.hpp"
 #include "tpe_internal.hpp"
 #include "tpe_level_plan.hpp"
@@ -260,6 +261,28 @@ struct tpe_plan : PlanShape {
   double *d_con = nullptr;      // [TPE_MAX_CON][ncap] the constraint matrix
   double *d_viol = nullptr;     // [ncap] the violations of the last constrained ranking
   int64_t viol_n = -1;          // ... and their number (-1: that ranking had none)
+  // c-TPE (tpe_plan_ctpe_*, tpe_ctpe.hip): nothing allocated before
+  // the first tpe_plan_ctpe_fit.  ct_ok: the bank is that of the current fit
+  // epoch (fit_args clears it).  Live position 0 is the plan's own fit; position
+  // l >= 1 lives at bank index l - 1
+  bool ct_ok = false;
+  int32_t ct_nlive = 0;
+  int32_t ct_live[kCtpeModels] = {};   // model of each live position
+  double ct_ghat[kCtpeModels] = {};    // ... and its ghat
+  int32_t ct_bank_cap = 0;             // models the bank holds
+  int64_t ct_kb_max = 0;               // bound on the live models' below components / options
+  double *d_ct_G = nullptr;            // [TPE_MAX_CON][ncap] the constraint matrix of the fit
+  double *d_ct_keys = nullptr;         // [bank][ncap] key columns
+  double *d_ct_mw = nullptr, *d_ct_mmu = nullptr, *d_ct_msig = nullptr;  // [bank][2P][kcap]
+  MixInfo *d_ct_info = nullptr;        // [bank][2P]
+  Coef *d_ct_coef = nullptr;           // [bank][2P][kcap]
+  int32_t *d_ct_feas = nullptr;        // [kCtpeModels] rows on the feasible side, by live position
+  double *d_ct_terms = nullptr;        // [n_live][P][chunk] terms of a scoring chunk
+  size_t ct_terms_cap = 0;
+  double *d_ct_T = nullptr;            // [n_live][m] host-mode staging of T
+  size_t ct_T_cap = 0;
+  void *d_ct_tab = nullptr;            // [n_live][P] draw tables
+  int32_t ct_tab_cap = 0;              // ... of this many models
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -332,7 +355,9 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_gsides, p->d_gjoint, p->d_bt_ja, p->d_bt_score, p->d_bt_gain,
                   p->d_bt_trace, p->d_bt_gact, p->d_bt_state, p->d_bt_slot, p->d_bt_rec,
                   p->d_bt_idx, p->d_obj, p->d_pcount, p->d_hv_i32, p->d_hv_f64, p->d_hv_alive,
-                  p->d_hv_u, p->d_con, p->d_viol};
+                  p->d_hv_u, p->d_con, p->d_viol, p->d_ct_G, p->d_ct_keys, p->d_ct_mw,
+                  p->d_ct_mmu, p->d_ct_msig, p->d_ct_info, p->d_ct_coef, p->d_ct_feas,
+                  p->d_ct_terms, p->d_ct_T, p->d_ct_tab};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -732,6 +757,7 @@ FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf,
   p->tab_built = false;  // a new fit epoch
   p->joint_ok = false;
   p->group_ok = false;
+  p->ct_ok = false;
   p->fit_pw = prior_weight;
   p->fit_lf = lf;
   FitArgs a{};
@@ -1741,6 +1767,7 @@ int tpe_plan_set_objectives(tpe_plan_t p, const double *Y, int32_t n_obj, int64_
   p->tab_built = false;
   p->joint_ok = false;
   p->group_ok = false;
+  p->ct_ok = false;
   if (!on_device) CKH(hipStreamSynchronize(st));
   return TPE_OK;
 }
@@ -2063,6 +2090,7 @@ int launch_step(tpe_engine *h, tpe_plan *p, int32_t nb, const uint64_t *seeds, i
   p->tab_built = p->graph_tab;
   p->joint_ok = false;  // (a new fit epoch, fitted with the captured node's arguments)
   p->group_ok = false;
+  p->ct_ok = false;
   p->fit_pw = p->fit_args0[0].prior_weight;
   p->fit_lf = p->fit_args0[0].lf;
   return TPE_OK;
@@ -2478,6 +2506,297 @@ JointScoreArgs joint_score_args(tpe_plan *p, const PointsArgs &a, double *joint)
 }
 
 }  // namespace
+
+// ---- c-TPE: one pair of Parzen models per constraint (tpe_ctpe.hip) ----
+namespace {
+
+// the bank for n_bank models (grown, never shrunk), the counters, the matrix
+int ensure_ctpe_bank(tpe_engine *h, tpe_plan *p, int32_t n_bank, hipStream_t st) {
+  if (!p->d_ct_G) {
+    CKH(dalloc(&p->d_ct_G, (size_t)TPE_MAX_CON * (size_t)p->ncap));
+    CKH(dalloc(&p->d_ct_feas, (size_t)kCtpeModels));
+  }
+  if (n_bank <= p->ct_bank_cap) return TPE_OK;
+  CKH(hipStreamSynchronize(st));  // (an earlier call may still read the old bank)
+  dfree(p->d_ct_keys); dfree(p->d_ct_mw); dfree(p->d_ct_mmu); dfree(p->d_ct_msig);
+  dfree(p->d_ct_info); dfree(p->d_ct_coef);
+  p->d_ct_keys = p->d_ct_mw = p->d_ct_mmu = p->d_ct_msig = nullptr;
+  p->d_ct_info = nullptr;
+  p->d_ct_coef = nullptr;
+  p->ct_bank_cap = 0;
+  const size_t nbk = (size_t)n_bank, slots = 2 * (size_t)p->P, kc = (size_t)p->kcap;
+  CKH(dalloc(&p->d_ct_keys, nbk * (size_t)p->ncap));
+  CKH(dalloc(&p->d_ct_mw, nbk * slots * kc));
+  CKH(dalloc(&p->d_ct_mmu, nbk * slots * kc));
+  CKH(dalloc(&p->d_ct_msig, nbk * slots * kc));
+  CKH(dalloc(&p->d_ct_info, nbk * slots));
+  CKH(dalloc(&p->d_ct_coef, nbk * slots * kc));
+  p->ct_bank_cap = n_bank;
+  return TPE_OK;
+}
+
+// configurations per scoring chunk: all m when their terms fit the scratch
+// budget (TPE_CHUNK_MB), else as many whole blocks of 256 as do, at least one
+int64_t ctpe_chunk(const tpe_plan *p, int64_t m) {
+  const int64_t per = (int64_t)p->ct_nlive * p->P;
+  const int64_t fit = std::max<int64_t>(switches().chunk_budget(), 0) / per;
+  return fit >= m ? m : std::max<int64_t>(256, fit / 256 * 256);
+}
+
+// score (sample: draw first) m configurations in chunks: V[P][ld], ACT[P][act_ld],
+// ACQ[m], T[n_live][t_ld] or null -- device pointers
+int ctpe_run(tpe_engine *h, tpe_plan *p, bool sample, uint64_t seed, int64_t begin, double *V,
+             int64_t ld, int64_t m, double *ACQ, double *T, int64_t t_ld, uint8_t *ACT,
+             int64_t act_ld, hipStream_t st) {
+  const int64_t chunk = ctpe_chunk(p, m);
+  const size_t need = (size_t)p->ct_nlive * p->P * (size_t)chunk;
+  if (need > p->ct_terms_cap) {
+    CKH(hipStreamSynchronize(st));
+    dfree(p->d_ct_terms);
+    p->d_ct_terms = nullptr;
+    p->ct_terms_cap = 0;
+    CKH(dalloc(&p->d_ct_terms, need));
+    p->ct_terms_cap = need;
+  }
+  CtpeSampleArgs s{};
+  CtpeArgs &c = s.C;
+  c.P = points_args(p, 0);
+  c.P.terms = p->d_ct_terms;
+  c.P.term_ld = chunk;
+  c.P.ld = ld;
+  c.P.act_ld = act_ld;
+  c.bk_info = p->d_ct_info;
+  c.bk_coef = p->d_ct_coef;
+  c.n_live = p->ct_nlive;
+  for (int l = 0; l < p->ct_nlive; ++l) c.ghat[l] = p->ct_ghat[l];
+  c.t_ld = t_ld;
+  s.mw = p->d_mw; s.mmu = p->d_mmu; s.msig = p->d_msig;
+  s.bk_mw = p->d_ct_mw; s.bk_mmu = p->d_ct_mmu; s.bk_msig = p->d_ct_msig;
+  s.tab = static_cast<DrawTableT<kTabCap> *>(p->d_ct_tab);
+  s.seed = seed;
+  for (int64_t c0 = 0; c0 < m; c0 += chunk) {
+    c.P.m = std::min(chunk, m - c0);
+    c.P.vals = V + c0;
+    c.P.active = ACT + c0;
+    c.acq = ACQ + c0;
+    c.T = T ? T + c0 : nullptr;
+    s.out = V + c0;
+    s.begin = begin + c0;
+    CKH(hipMemsetAsync(p->d_pt_count, 0, (size_t)p->P * sizeof(uint32_t), st));
+    if (sample) CKH(launch_ctpe_sample(s, p->ct_kb_max > kTabCap, st));
+    else CKH(launch_points_active(c.P, st));
+    CKH(launch_ctpe_score(c, st));
+  }
+  return TPE_OK;
+}
+
+// the shared front of the two point calls: checks, scratch, staging.  Host
+// mode stages through the plan's points scratch and d_ct_T
+int ctpe_points(tpe_plan *p, const char *who, bool sample, uint64_t seed, int64_t begin,
+                const double *vals_in, double *vals, int64_t m, int64_t ld, double *acq, double *T,
+                uint8_t *active, int32_t on_device, void *stream) {
+  tpe_engine *h = p->eng;
+  const std::string w(who);
+  if (m < 0 || ld < m) return fail(h, TPE_E_INVALID, w + ": need 0 <= m <= ld");
+  if (begin < 0) return fail(h, TPE_E_INVALID, w + ": begin must not be negative");
+  if (m > 0 && (!vals || !acq))
+    return fail(h, TPE_E_INVALID, w + ": vals and acq must not be null");
+  if (m > (int64_t)INT32_MAX) return fail(h, TPE_E_INVALID, w + ": too many configurations");
+  if (m == 0) return TPE_OK;
+  if (!p->ct_ok || p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, w + ": the plan has no c-TPE fit (tpe_plan_ctpe_fit first)");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  {
+    const int rc = ensure_points(h, p, (size_t)m);
+    if (rc) return rc;
+  }
+  if (sample) {
+    if (p->ct_tab_cap < p->ct_nlive) {
+      CKH(hipStreamSynchronize(st));
+      dfree(p->d_ct_tab);
+      p->d_ct_tab = nullptr;
+      p->ct_tab_cap = 0;
+      CKH(hipMalloc(&p->d_ct_tab, (size_t)p->ct_nlive * sample_tables_bytes(p->P)));
+      p->ct_tab_cap = p->ct_nlive;
+    }
+    // the draw tables of every live model's below mixtures, [live][P]
+    for (int l = 0; l < p->ct_nlive; ++l) {
+      SampleArgs t{};
+      t.P = points_args(p, 0);
+      const size_t off = (size_t)std::max(l - 1, 0) * 2 * (size_t)p->P;
+      t.P.info = l ? p->d_ct_info + off : p->d_info;
+      t.mw = l ? p->d_ct_mw + off * p->kcap : p->d_mw;
+      t.mmu = l ? p->d_ct_mmu + off * p->kcap : p->d_mmu;
+      t.msig = l ? p->d_ct_msig + off * p->kcap : p->d_msig;
+      t.tab = reinterpret_cast<DrawTableT<kTabCap> *>(static_cast<char *>(p->d_ct_tab) +
+                                                      (size_t)l * sample_tables_bytes(p->P));
+      CKH(launch_sample_tables(t, st));
+    }
+  }
+  if (on_device)
+    return ctpe_run(h, p, sample, seed, begin, vals, ld, m, acq, T, ld,
+                    active ? active : p->d_pt_act, active ? ld : m, st);
+  if (T && (size_t)p->ct_nlive * (size_t)m > p->ct_T_cap) {
+    CKH(hipStreamSynchronize(st));
+    dfree(p->d_ct_T);
+    p->d_ct_T = nullptr;
+    p->ct_T_cap = 0;
+    CKH(dalloc(&p->d_ct_T, (size_t)p->ct_nlive * (size_t)m));
+    p->ct_T_cap = (size_t)p->ct_nlive * (size_t)m;
+  }
+  if (!sample)
+    CKH(hipMemcpy2DAsync(p->d_pt_vals, (size_t)m * 8, vals_in, (size_t)ld * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyHostToDevice, st));
+  {
+    const int rc = ctpe_run(h, p, sample, seed, begin, p->d_pt_vals, m, m, p->d_pt_total,
+                            T ? p->d_ct_T : nullptr, m, p->d_pt_act, m, st);
+    if (rc) return rc;
+  }
+  if (sample)
+    CKH(hipMemcpy2DAsync(vals, (size_t)ld * 8, p->d_pt_vals, (size_t)m * 8, (size_t)m * 8,
+                         (size_t)p->P, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(acq, p->d_pt_total, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (T)
+    CKH(hipMemcpy2DAsync(T, (size_t)ld * 8, p->d_ct_T, (size_t)m * 8, (size_t)m * 8,
+                         (size_t)p->ct_nlive, hipMemcpyDeviceToHost, st));
+  if (active)
+    CKH(hipMemcpy2DAsync(active, (size_t)ld, p->d_pt_act, (size_t)m, (size_t)m, (size_t)p->P,
+                         hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+}  // namespace
+
+int tpe_plan_ctpe_fit(tpe_plan_t p, const double *G, int32_t n_con, int64_t n, int64_t ld,
+                      int32_t on_device, const int32_t *nb, const double *ghat,
+                      double prior_weight, int32_t lf, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (n_con < 1 || n_con > TPE_MAX_CON)
+    return fail(h, TPE_E_INVALID, "ctpe_fit: need 1 <= n_con <= TPE_MAX_CON");
+  if (n != p->n || n < 1)
+    return fail(h, TPE_E_INVALID, "ctpe_fit: n is not the (non-empty) history length");
+  if (!G || !nb || !ghat || ld < n)
+    return fail(h, TPE_E_INVALID, "ctpe_fit: G, nb, ghat must not be null, ld >= n");
+  for (int m = 0; m <= n_con; ++m)
+    if (nb[m] < 0 || nb[m] > n || !(ghat[m] > 0.0 && ghat[m] <= 1.0))
+      return fail(h, TPE_E_INVALID, "ctpe_fit: need 0 <= nb[m] <= n and 0 < ghat[m] <= 1");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  // the live models: the objective, and every constraint whose good side is
+  // not the whole history
+  int32_t live[kCtpeModels], n_live = 0;
+  for (int m = 0; m <= n_con; ++m)
+    if (m == 0 || ghat[m] < 1.0) live[n_live++] = m;
+  p->ct_ok = false;
+  {
+    int rc = ensure_ctpe_bank(h, p, n_live - 1, st);
+    if (!rc) rc = flush_patch(h, p, st);  // (the keys read the loss column)
+    if (rc) return rc;
+  }
+  CKH(hipMemcpy2DAsync(p->d_ct_G, (size_t)p->ncap * 8, G, (size_t)ld * 8, (size_t)n * 8,
+                       (size_t)n_con, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                       st));
+  CKH(hipMemsetAsync(p->d_ct_feas, 0, kCtpeModels * sizeof(int32_t), st));
+  CtpeKeyArgs k{};
+  k.G = p->d_ct_G; k.losses = p->d_losses; k.n = n; k.ld = p->ncap; k.n_live = n_live;
+  for (int l = 1; l < n_live; ++l) k.con[l] = live[l] - 1;
+  k.keys = p->d_ct_keys; k.feas = p->d_ct_feas;
+  CKH(launch_ctpe_keys(k, st));
+  // the constraint models through tpe_plan_fit's own path, one after another
+  // (they share the sort and observation scratch), each on its key column and
+  // into its bank slot; the tables the points path never reads go to the
+  // plan's own (model 0's fit, last, writes them again) or nowhere
+  const FitArgs f0 = fit_args(p, nb[0], prior_weight, lf, plan_fit_variant(p, true));
+  for (int l = 1; l < n_live; ++l) {
+    const size_t off = (size_t)(l - 1) * 2 * (size_t)p->P;
+    FitArgs f = f0;
+    f.losses = p->d_ct_keys + (size_t)(l - 1) * (size_t)p->ncap;
+    f.n_below = nb[live[l]];
+    f.mw = p->d_ct_mw + off * p->kcap;
+    f.mmu = p->d_ct_mmu + off * p->kcap;
+    f.msig = p->d_ct_msig + off * p->kcap;
+    f.info = p->d_ct_info + off;
+    f.coef = p->d_ct_coef + off * p->kcap;
+    f.coefm = nullptr; f.coefm8 = nullptr; f.coefmh = nullptr;
+    CKH(launch_fit(f, p->P, st));
+  }
+  {
+    const int rc = fit_launch(h, p, f0, p->P, st);
+    if (rc) return rc;
+  }
+  p->last_nb = nb[0];
+  p->ct_nlive = n_live;
+  p->ct_kb_max = 0;
+  for (int i = 0; i < p->P; ++i)
+    if (p->hps[i].family == TPE_CAT) p->ct_kb_max = std::max<int64_t>(p->ct_kb_max, p->hps[i].upper);
+  for (int l = 0; l < n_live; ++l) {
+    p->ct_live[l] = live[l];
+    p->ct_ghat[l] = ghat[live[l]];
+    p->ct_kb_max = std::max<int64_t>(p->ct_kb_max, (int64_t)nb[live[l]] + 1);
+  }
+  p->ct_ok = true;
+  if (!on_device) CKH(hipStreamSynchronize(st));
+  return TPE_OK;
+}
+
+int tpe_plan_ctpe_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld, double *acq,
+                               double *T, uint8_t *active, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  return ctpe_points(p, "ctpe_score_points", false, 0, 0, vals, const_cast<double *>(vals), m, ld,
+                     acq, T, active, on_device, stream);
+}
+
+int tpe_plan_ctpe_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m, int64_t ld,
+                                double *vals, double *acq, double *T, uint8_t *active,
+                                int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  return ctpe_points(p, "ctpe_sample_points", true, seed, begin, nullptr, vals, m, ld, acq, T,
+                     active, on_device, stream);
+}
+
+int tpe_plan_ctpe_get_mixture(tpe_plan_t p, int32_t model, int32_t hp, int32_t side, double *w,
+                              double *mu, double *sigma, int64_t cap, int64_t *k) {
+  if (!p || !k) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!p->ct_ok || p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, "ctpe_get_mixture: the plan has no c-TPE fit");
+  int l = -1;
+  for (int i = 0; i < p->ct_nlive; ++i)
+    if (p->ct_live[i] == model) l = i;
+  if (l < 0) return fail(h, TPE_E_INVALID, "ctpe_get_mixture: not a live model");
+  if (l == 0) return tpe_plan_get_mixture(p, hp, side, w, mu, sigma, cap, k);
+  if (hp < 0 || hp >= p->P || side < 0 || side > 1) return fail(h, TPE_E_INVALID, "bad hp/side");
+  CKH(hipSetDevice(h->device));
+  CKH(hipDeviceSynchronize());
+  const size_t slot = (size_t)(l - 1) * 2 * (size_t)p->P + 2 * (size_t)hp + (size_t)side;
+  MixInfo mi;
+  CKH(hipMemcpy(&mi, p->d_ct_info + slot, sizeof(mi), hipMemcpyDeviceToHost));
+  *k = mi.K;
+  if (mi.K > cap) return fail(h, TPE_E_INVALID, "capacity too small");
+  if (w) CKH(hipMemcpy(w, p->d_ct_mw + slot * p->kcap, mi.K * 8, hipMemcpyDeviceToHost));
+  if (mu) CKH(hipMemcpy(mu, p->d_ct_mmu + slot * p->kcap, mi.K * 8, hipMemcpyDeviceToHost));
+  if (sigma) CKH(hipMemcpy(sigma, p->d_ct_msig + slot * p->kcap, mi.K * 8, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+int tpe_plan_ctpe_info(tpe_plan_t p, int32_t *live, int32_t *feasible_count, int32_t *n_live) {
+  if (!p || !n_live) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!p->ct_ok || p->last_nb < 0)
+    return fail(h, TPE_E_INVALID, "ctpe_info: the plan has no c-TPE fit");
+  *n_live = p->ct_nlive;
+  if (live) std::copy(p->ct_live, p->ct_live + p->ct_nlive, live);
+  if (feasible_count) {
+    CKH(hipSetDevice(h->device));
+    CKH(hipDeviceSynchronize());
+    CKH(hipMemcpy(feasible_count, p->d_ct_feas, (size_t)p->ct_nlive * sizeof(int32_t),
+                  hipMemcpyDeviceToHost));
+  }
+  return TPE_OK;
+}
 
 int tpe_plan_joint_fit(tpe_plan_t p, void *stream) {
   if (!p) return TPE_E_INVALID;

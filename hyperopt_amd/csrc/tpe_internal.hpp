@@ -709,6 +709,8 @@ struct PointsArgs {
 hipError_t launch_points(const PointsArgs &a, hipStream_t st);
 // k_score_points, k_points_sum alone (the caller's launch wrote the lists)
 hipError_t launch_points_score(const PointsArgs &a, hipStream_t st);
+// k_points_active alone (the caller scores)
+hipError_t launch_points_active(const PointsArgs &a, hipStream_t st);
 
 // Whole configurations drawn from the fitted below mixtures and scored
 // (tpe_sample_points.hip, tpe_plan_sample_points): P.vals == out
@@ -724,6 +726,8 @@ struct SampleArgs {
 size_t sample_tables_bytes(int32_t n_hp);
 // k_sample_tables, k_sample_points, then launch_points_score
 hipError_t launch_sample_points(const SampleArgs &s, hipStream_t st);
+// k_sample_tables alone, into s.tab
+hipError_t launch_sample_tables(const SampleArgs &s, hipStream_t st);
 
 // The joint Parzen model over the root (unconditional) hps (tpe_joint.hip;
 // tpe_plan_joint_*).  Side s has K_s = n_s + 1 components --

@@ -92,6 +92,13 @@ __global__ __launch_bounds__(kSpThreads) void k_sample_points(SampleArgs S) {
 
 size_t sample_tables_bytes(int32_t n_hp) { return (size_t)n_hp * sizeof(DrawTable); }
 
+// k_sample_tables alone: the draw tables of s.P.info / s.mw / s.mmu / s.msig
+// into s.tab (one model of tpe_ctpe.hip's bank per call)
+hipError_t launch_sample_tables(const SampleArgs &s, hipStream_t st) {
+  k_sample_tables<<<dim3((unsigned)s.P.n_hp), dim3(kSpThreads), 0, st>>>(s);
+  return hipGetLastError();
+}
+
 hipError_t launch_sample_points(const SampleArgs &s, hipStream_t st) {
   const unsigned gx = (unsigned)((s.P.m + kSpThreads - 1) / kSpThreads);
   k_sample_tables<<<dim3((unsigned)s.P.n_hp), dim3(kSpThreads), 0, st>>>(s);

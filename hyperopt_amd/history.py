@@ -30,7 +30,9 @@ With ``constraints=C`` (constrained TPE) a constraint store
 ``G[C][cap]`` is kept too, from ``result['constraints']`` of the ok trials, and
 ``push`` sends it (``tpe_plan_set_constraints``) ahead of the objectives: the
 device then ranks by constrained dominance.  Without ``objectives`` the
-objective store is the single row of the losses.
+objective store is the single row of the losses.  With
+``constraint_model='ctpe'`` (c-TPE) the store is kept the same way
+but ``push`` ranks without it: the caller hands ``G`` to the c-TPE fit instead.
 """
 from __future__ import annotations
 
@@ -74,6 +76,17 @@ def check_constraints(constraints):
         raise ValueError('constraints must be None or an int in [1, %d], got %r'
                          % (MAX_CON, constraints))
     return int(constraints)
+
+
+def check_constraint_model(constraint_model, constraints):
+    """``constraint_model=`` checked against the checked ``constraints``: 'rank'
+    (constrained dominance in the split; the default) or 'ctpe'
+    (one Parzen model per constraint), which needs constraints."""
+    if constraint_model not in ('rank', 'ctpe'):
+        raise ValueError("constraint_model must be 'rank' or 'ctpe', got %r" % (constraint_model,))
+    if constraint_model == 'ctpe' and constraints is None:
+        raise ValueError("constraint_model='ctpe' needs constraints=C")
+    return constraint_model
 
 
 def check_hypervolume(hypervolume, objectives):
@@ -162,6 +175,7 @@ class TrialHistory(object):
         self.hv = False         # hypervolume= of the last sync: False, True or the reference point
         self.C = None           # constraints of the last sync (None: unconstrained)
         self.G = None           # [C][cap] constraint store (NaN: not an ok trial)
+        self.cmodel = 'rank'    # constraint_model of the last sync
         self._alloc(64)
         self._forget()
 
@@ -257,7 +271,8 @@ class TrialHistory(object):
         self._touched.add(r)
 
     # -- sync ----------------------------------------------------------------
-    def sync(self, trials, objectives=None, hypervolume=False, constraints=None):
+    def sync(self, trials, objectives=None, hypervolume=False, constraints=None,
+             constraint_model='rank'):
         """Bring the columns up to date with ``trials.trials``.  ``objectives``
         = M: also the objective store ``Y[M][cap]``, from every ok trial's
         ``result['objectives']`` (ValueError naming the tid where an ok trial
@@ -267,9 +282,12 @@ class TrialHistory(object):
         ``constraints`` = C: also the constraint store ``G[C][cap]``, from every
         ok trial's ``result['constraints']`` under the same rules (NaN for any
         other trial); ``push`` then ranks by constrained dominance, over the
-        objectives or, without them, over the single row of the losses."""
+        objectives or, without them, over the single row of the losses.
+        ``constraint_model`` 'ctpe': the store is kept, and ``push`` ranks as
+        without constraints."""
         objectives = check_objectives(objectives)
         constraints = check_constraints(constraints)
+        self.cmodel = check_constraint_model(constraint_model, constraints)
         self.hv = check_hypervolume(hypervolume, objectives)
         view = trials.trials
         store = getattr(trials, '_store', None)
@@ -466,7 +484,8 @@ class TrialHistory(object):
             self._dev_mode = None
         r0 = min(self._vals_dirty, self.n)
         mode = None
-        if self.M is None and self.C is None:
+        C = self.C if self.cmodel == 'rank' else None   # the constraints the ranking reads
+        if self.M is None and C is None:
             if self._dev_mode is not None:
                 self._loss_dirty = 0        # the column holds a ranking: every loss goes again
             l0 = min(self._loss_dirty, r0, self.n)
@@ -478,8 +497,8 @@ class TrialHistory(object):
             plan.update_history(self.n, r0, self.vals, self.active, self.cap, self.n,
                                 self.losses)
             mode = self.M if self.hv is False else (self.M, self.hv)
-            if self.C is not None:
-                mode = ('loss' if self.M is None else self.M, self.hv, self.C)
+            if C is not None:
+                mode = ('loss' if self.M is None else self.M, self.hv, C)
             same = self._dev_mode == mode
             o0 = min(self._obj_dirty, self.n) if same else 0
             # the setting goes before the ranking that reads it; a plan that
@@ -490,7 +509,7 @@ class TrialHistory(object):
             elif getattr(plan, '_hv_on', False):
                 plan.set_hv(None)
             # the constraints go before the ranking that reads them too
-            if self.C is not None:
+            if C is not None:
                 plan.set_constraints(self.G, n=self.n,
                                      con0=min(self._con_dirty, self.n) if same else 0)
                 self._con_dirty = self.n

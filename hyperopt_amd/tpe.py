@@ -38,7 +38,7 @@ import numpy as np
 from . import _engine as E
 from . import rand, rstream
 from .history import (TrialHistory, check_objectives, check_hypervolume, check_constraints,
-                      HV_N_SAMPLES)
+                      check_constraint_model, HV_N_SAMPLES)
 
 logger = logging.getLogger(__name__)
 
@@ -151,7 +151,7 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             rng_stream='philox', startup_stream='numpy', engine=None, objectives=None,
-            hypervolume=False, constraints=None):
+            hypervolume=False, constraints=None, constraint_model='rank'):
     """hyperopt/tpe.py:804-897 on the GPU, one document per id in
     ``new_ids``.  ``linear_forgetting`` is accepted and, as in the reference
     (tpe.py:809), not used: LF is fixed at 25.  The first ``n_startup_jobs``
@@ -191,10 +191,15 @@ def suggest(new_ids, domain, trials, seed,
     total violation ``sum of max(g, 0)`` whatever their loss, then pending
     ones.  With every trial feasible the suggestions are those of
     ``constraints=None``.  Calls with and without ``constraints`` may alternate
-    on one domain and one trials object."""
+    on one domain and one trials object.  ``constraint_model`` must be 'rank'
+    here: c-TPE's acquisition is joint over a configuration, which
+    this per-hp argmax cannot use -- ``suggest_joint`` takes 'ctpe'."""
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
     constraints = check_constraints(constraints)
+    if check_constraint_model(constraint_model, constraints) == 'ctpe':
+        raise ValueError("tpe.suggest picks every hp by its own argmax and cannot rank a joint "
+                         "acquisition: use suggest_joint(constraint_model='ctpe')")
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -363,8 +368,52 @@ def _mode(multivariate):
     raise ValueError("multivariate must be False, True or 'groups', got %r" % (multivariate,))
 
 
-def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate=False):
+def _cmodel(constraint_model, constraints, multivariate, batch='topk'):
+    """``constraint_model=`` checked against the other settings of a call:
+    'ctpe' needs ``constraints``, the marginal model and ``batch='topk'``."""
+    cm = check_constraint_model(constraint_model, constraints)
+    if cm == 'ctpe' and multivariate is not False:
+        raise ValueError("constraint_model='ctpe' needs multivariate=False: the constraint "
+                         "models are marginal, got multivariate=%r" % (multivariate,))
+    if cm == 'ctpe' and batch == 'pending':
+        raise ValueError("constraint_model='ctpe' is incompatible with batch='pending'")
+    return cm
+
+
+def ctpe_counts(losses, G, gamma=_default_gamma, gamma_cap=DEFAULT_LF):
+    """(nb int32[C + 1], ghat[C + 1]) of c-TPE's models over a history with loss
+    column ``losses[n]`` and constraints ``G[C, n]``: per model
+    the rows on its good side and their share of the complete (finite-loss)
+    rows.  Model 0, the objective: the plain ``min(ceil(gamma sqrt(n)),
+    gamma_cap)``, raised to the 1-based rank of the best feasible row in the
+    stable loss order where a row is feasible under every constraint, so the
+    good side holds a feasible trial.  Model m, constraint m - 1: its feasible
+    complete rows, at least the plain count, at most the complete rows.
+    ValueError without a complete row."""
+    losses = np.asarray(losses, dtype=np.float64)
+    G = np.asarray(G, dtype=np.float64)
+    n = losses.size
+    complete = np.isfinite(losses)
+    n_c = int(complete.sum())
+    if n_c == 0:
+        raise ValueError('c-TPE needs a complete trial: no loss of the history is finite')
+    plain = int(max(0.0, min(math.ceil(gamma * math.sqrt(n)), gamma_cap)))
+    with np.errstate(invalid='ignore'):
+        ok = complete & (G <= 0)                    # [C, n]; NaN is not feasible
+    nb = np.empty(G.shape[0] + 1, dtype=np.int32)
+    nb[0] = plain
+    feasible = ok.all(axis=0)
+    if feasible.any():
+        order = np.argsort(losses, kind='stable')
+        nb[0] = max(plain, 1 + int(np.flatnonzero(feasible[order])[0]))
+    nb[1:] = np.minimum(np.maximum(ok.sum(axis=1), plain), n_c)
+    return nb, np.minimum(nb, n_c) / float(n_c)
+
+
+def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate=False,
+             constraint_model='rank'):
     """Push the history and fit, exactly as ``suggest`` does (st.lock held).
+    ``constraint_model`` 'ctpe': the c-TPE fit in the place of the plain one.
     ``multivariate``: also the joint model over the unconditional hps, which
     every history row must hold (ValueError otherwise); 'groups': the joint
     model of every ``hp_groups`` group, whose hps must be active in exactly
@@ -373,6 +422,13 @@ def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate
     engine = engine or E.default_engine()
     plan = st.plan_for(domain, hist.n, engine)
     hist.push(plan)
+    if constraint_model == 'ctpe':
+        # the ranking ran without constraints (TrialHistory.push); G goes to the bank fit
+        n = hist.n
+        column = hist.losses[:n] if hist.M is None else plan.pareto_get(n)[2]
+        nb, ghat = ctpe_counts(column, hist.G[:, :n], gamma)
+        plan.ctpe_fit(hist.G, nb, ghat, n=n, prior_weight=prior_weight, lf=DEFAULT_LF)
+        return plan
     plan.fit(gamma=gamma, prior_weight=prior_weight, lf=DEFAULT_LF)
     if multivariate == 'groups':
         cs = domain.space
@@ -406,7 +462,7 @@ def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate
 
 def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
                   gamma=_default_gamma, engine=None, return_terms=False, multivariate=False,
-                  objectives=None, hypervolume=False, constraints=None):
+                  objectives=None, hypervolume=False, constraints=None, constraint_model='rank'):
     """What the fitted TPE model thinks of configurations the caller holds.
 
     The history of ``trials`` is synced, pushed and fitted as ``suggest``
@@ -441,22 +497,38 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
     hypervolume order inside the front (``suggest``).  ``constraints=C``: the
     history is ranked by constrained dominance over the trials'
-    ``result['constraints']`` (``suggest``)."""
+    ``result['constraints']`` (``suggest``).
+
+    ``constraint_model='ctpe'`` (with ``constraints``, ``multivariate=False``;
+    DESIGN 5.20): c-TPE.  The split ranks without the constraints; beside the
+    objective's model stands one pair of Parzen models per constraint, split at
+    its feasibility threshold, and the score is the acquisition ``acq(c) = -sum
+    over the live models of log(ghat_m + (1 - ghat_m) exp(-T_m(c)))`` with
+    ``T_m`` the EI above under model m and ``ghat_m`` the share of the history
+    on its good side (``ctpe_counts``); a constraint every trial satisfies is
+    dead and changes nothing.  With ``return_terms`` the result is (acq,
+    T[n_live, M], active, live) with ``live`` the live models (0: the
+    objective, m: constraint m - 1).  ValueError for any other value, for
+    'ctpe' without ``constraints`` or with ``multivariate``."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
     constraints = check_constraints(constraints)
+    cm = _cmodel(constraint_model, constraints, multivariate)
     cs = domain.space
     as_dicts = not isinstance(configs, np.ndarray)
     vals, present = config_columns(cs, configs)
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
         if hist.n == 0:
             raise ValueError('score_configs needs a history: trials holds no usable trial')
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate, cm)
         joint = None
-        if multivariate == 'groups':
+        if cm == 'ctpe':
+            total, terms, active = plan.ctpe_score_points(vals, want_T=True, want_active=True)
+            live = plan.ctpe_info()[0]
+        elif multivariate == 'groups':
             total, active, joint = plan.group_score_points(vals, want_active=True,
                                                            want_joint=True)
             terms = np.zeros(vals.shape)
@@ -469,6 +541,9 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
         _check_consistent(cs, present, active)
     if not return_terms:
         return total
+    if cm == 'ctpe':
+        return (total, terms, {lab: active[i].astype(bool) for i, lab in enumerate(cs.labels)},
+                live)
     out = (total, {lab: terms[i] for i, lab in enumerate(cs.labels)},
            {lab: active[i].astype(bool) for i, lab in enumerate(cs.labels)})
     return out + (joint,) if multivariate else out
@@ -486,11 +561,13 @@ class _Pool(object):
         self.m = self.vals.shape[1]
         self._dev = None            # (engine, values, totals) device buffers of an array pool
 
-    def totals(self, plan, multivariate=False):
-        """EI of every pool configuration under ``plan``'s fit."""
+    def totals(self, plan, multivariate=False, ctpe=False):
+        """EI (``ctpe``: the c-TPE acquisition) of every pool configuration
+        under ``plan``'s fit."""
         groups = multivariate == 'groups'
         if not isinstance(self.source, np.ndarray) or self.m == 0:
-            return (plan.group_score_points if groups else plan.joint_score_points
+            return (plan.ctpe_score_points if ctpe else
+                    plan.group_score_points if groups else plan.joint_score_points
                     if multivariate else plan.score_points)(self.vals)
         # an array pool lives on the device: uploaded once, scored in place
         eng = plan.engine
@@ -498,7 +575,8 @@ class _Pool(object):
             self._dev = (eng, E.DeviceBuffer(eng, self.vals.nbytes).upload(self.vals),
                          E.DeviceBuffer(eng, 8 * self.m))
         _, v, out = self._dev
-        score = (plan.group_score_points_device if groups else plan.joint_score_points_device
+        score = (plan.ctpe_score_points_device if ctpe else
+                 plan.group_score_points_device if groups else plan.joint_score_points_device
                  if multivariate else plan.score_points_device)
         score(v.ptr, self.m, self.m, out.ptr)
         return out.download(np.empty(self.m))
@@ -544,7 +622,8 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
                       prior_weight=_default_prior_weight,
                       n_startup_jobs=_default_n_startup_jobs,
                       gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False,
-                      objectives=None, hypervolume=False, constraints=None):
+                      objectives=None, hypervolume=False, constraints=None,
+                      constraint_model='rank'):
     """``algo=`` for a constrained or discrete search: the next trials are the
     ``len(new_ids)`` configurations of ``pool`` the fitted model scores
     highest (``score_configs``' EI), distinct, ties to the lower pool index,
@@ -561,11 +640,13 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     the trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with
     the hypervolume order inside the front (``suggest``).  ``constraints=C``: the
     history is ranked by constrained dominance over the trials'
-    ``result['constraints']`` (``suggest``)."""
+    ``result['constraints']`` (``suggest``); ``constraint_model='ctpe'``: the pool
+    is ranked by c-TPE's acquisition instead (``score_configs``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
     constraints = check_constraints(constraints)
+    cm = _cmodel(constraint_model, constraints, multivariate)
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -576,7 +657,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     k = len(new_ids)
     with st.lock:
         pl = _pool_for(st, cs, pool)
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
         if hist.n < n_startup_jobs:
             if pl.m < k:
                 raise ValueError('the pool holds %d configurations, %d asked for' % (pl.m, k))
@@ -589,8 +670,9 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
             if int(eligible.sum()) < k:
                 raise ValueError('%d eligible pool configurations remain, %d asked for'
                                  % (int(eligible.sum()), k))
-            plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
-            picks = rank_pool(pl.totals(plan, multivariate), eligible, k)
+            plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate,
+                            cm)
+            picks = rank_pool(pl.totals(plan, multivariate, cm == 'ctpe'), eligible, k)
     chosen = columns_to_configs(cs, pl.vals[:, picks], pl.active[:, picks])
     return [_new_doc(domain, trials, cs, i, c) for i, c in zip(new_ids, chosen)]
 
@@ -605,7 +687,8 @@ STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
 
 def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
                    gamma=_default_gamma, engine=None, begin=0, as_dicts=False,
-                   multivariate=False, objectives=None, hypervolume=False, constraints=None):
+                   multivariate=False, objectives=None, hypervolume=False, constraints=None,
+                   constraint_model='rank'):
     """``n`` whole configurations drawn from the fitted model's *below*
     mixtures, each with its joint EI (``score_configs``' total of it).
 
@@ -631,19 +714,27 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     the Pareto ranking of the trials' ``result['objectives']`` (``suggest``);
     ``hypervolume``: with the hypervolume order inside the front (``suggest``).
     ``constraints=C``: the history is ranked by constrained dominance over the
-    trials' ``result['constraints']`` (``suggest``)."""
+    trials' ``result['constraints']`` (``suggest``).  ``constraint_model='ctpe'``
+    (``score_configs``): configuration ``begin + j`` is drawn from the below
+    mixtures of live model ``(begin + j) % n_live`` -- the objective's and every
+    live constraint's good side in turn -- and the second result is c-TPE's
+    acquisition (tpe_plan_ctpe_sample_points).  A constraint's good side is as
+    large as its feasible trials are many: past 2047 of them the draw takes the
+    engine's rejection sampler in the place of its tables, with the same values."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
     constraints = check_constraints(constraints)
+    cm = _cmodel(constraint_model, constraints, multivariate)
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
-        draw = (plan.group_sample_points if multivariate == 'groups' else
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate, cm)
+        draw = (plan.ctpe_sample_points if cm == 'ctpe' else
+                plan.group_sample_points if multivariate == 'groups' else
                 plan.joint_sample_points if multivariate else plan.sample_points)
         vals, total = draw(batch_seeds(seed, 1)[0], int(n), begin=int(begin))
     if as_dicts:
@@ -780,7 +871,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
                   startup_stream='numpy', engine=None, multivariate=False, batch='topk',
-                  objectives=None, hypervolume=False, constraints=None):
+                  objectives=None, hypervolume=False, constraints=None, constraint_model='rank'):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -829,13 +920,16 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
     hypervolume order inside the front (``suggest``).  ``constraints=C``: the
     history is ranked by constrained dominance over the trials'
-    ``result['constraints']`` (``suggest``)."""
+    ``result['constraints']`` (``suggest``).  ``constraint_model='ctpe'``: the
+    draw and its ranking are ``sample_configs``' with that argument (c-TPE,
+    DESIGN 5.20); ValueError with ``multivariate`` or ``batch='pending'``."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
     constraints = check_constraints(constraints)
     if batch not in ('topk', 'pending'):
         raise ValueError("batch must be 'topk' or 'pending', got %r" % (batch,))
+    cm = _cmodel(constraint_model, constraints, multivariate, batch)
     if batch == 'pending' and multivariate != 'groups':
         raise ValueError("batch='pending' needs multivariate='groups': only the group models "
                          "hold an above density per configuration that a pending trial can "
@@ -848,7 +942,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     k = len(new_ids)
     n = int(n_configs)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
         startup = hist.n < n_startup_jobs
     if startup:
         if feasible is None:
@@ -858,12 +952,14 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
     P = len(cs.labels)
     with st.lock:
-        if hist.M != objectives or hist.hv != hypervolume or hist.C != constraints:
+        if hist.M != objectives or hist.hv != hypervolume or hist.C != constraints or \
+                hist.cmodel != cm:
             # (another thread's call in between)
-            hist.sync(trials, objectives, hypervolume, constraints)
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate)
+            hist.sync(trials, objectives, hypervolume, constraints, cm)
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate, cm)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
-        draw = (plan.group_sample_points_device if multivariate == 'groups' else
+        draw = (plan.ctpe_sample_points_device if cm == 'ctpe' else
+                plan.group_sample_points_device if multivariate == 'groups' else
                 plan.joint_sample_points_device if multivariate else plan.sample_points_device)
         draw(batch_seeds(seed, 1)[0], 0, n, n, d_vals.ptr, d_total.ptr)
         vals = eligible = None

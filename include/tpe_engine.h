@@ -645,6 +645,69 @@ int tpe_plan_set_constraints(tpe_plan_t p, const double *G, int32_t n_con, int64
  * returns that ranking's c-dominance counts and column.  Waits for the device. */
 int tpe_plan_constraint_get(tpe_plan_t p, double *violation, int64_t n);
 
+/* ---- c-TPE: one pair of Parzen models per constraint ---------
+ * Models are m = 0 (the objective, split on the plan's loss column) and
+ * m = 1 .. n_con (constraint m - 1, split on its key column: G[m - 1][i], or
+ * +inf where row i's loss is not finite or the value is NaN).  Model m's good
+ * side holds the nb[m] rows of smallest (key, row) and ghat[m] is the share of
+ * complete rows that stands for; the caller computes both.  A model with
+ * ghat[m] == 1 is dead: it is not fitted and adds exactly 0.0.  Model 0 is
+ * always live.  With T_m(c) the total tpe_plan_score_points computes under
+ * model m's mixtures,
+ *   L_m = log(ghat_m + (1 - ghat_m) exp(-T_m))
+ *       = hi + log1p(exp(lo - hi)),  u = log(ghat_m),  v = log1p(-ghat_m) - T_m,
+ *         (hi, lo) = u > v ? (u, v) : (v, u),
+ * in plain fp64 (T = +inf gives u, T = -inf gives +inf, NaN gives NaN), and
+ *   acq(c) = ((0.0 - L_m0) - L_m1) - ...   over the live models in ascending m.
+ *
+ * tpe_plan_ctpe_fit copies G (row r of constraint c at G[c * ld + r]; rows
+ * [0, n)), writes the key columns and fits every live model with
+ * tpe_plan_fit's kernel: model 0 into the plan's own fit storage with
+ * n_below = nb[0] (tpe_plan_score_points and the other readers of a fit serve
+ * it afterwards), the others into a plan-owned bank that grows with the live
+ * count.  on_device != 0: G is a device pointer, stream-ordered, no host
+ * synchronisation (nb and ghat are always host arrays of n_con + 1 entries).
+ * TPE_E_INVALID: n_con outside [1, TPE_MAX_CON], n other than the (non-empty)
+ * history length, ld < n, a null G / nb / ghat, nb[m] outside [0, n], ghat[m]
+ * outside (0, 1].  A later tpe_plan_fit or tpe_plan_set_objectives drops the
+ * c-TPE fit.                                                                */
+int tpe_plan_ctpe_fit(tpe_plan_t p, const double *G, int32_t n_con, int64_t n, int64_t ld,
+                      int32_t on_device, const int32_t *nb, const double *ghat,
+                      double prior_weight, int32_t lf, void *stream);
+/* acq[m] of m whole configurations vals[n_hp][ld] under the c-TPE fit, and
+ * optional T[n_live][ld] (T_m of live model l at T[l * ld + c]) and
+ * active[n_hp][ld].  Activity, layouts, on_device, the NULL outputs and
+ * m == 0 are tpe_plan_score_points'; T_0 is its total bit for bit.  When the
+ * terms of all m configurations exceed the scratch budget (TPE_CHUNK_MB) the
+ * call walks them in chunks, which changes no number.  TPE_E_INVALID: m < 0,
+ * ld < m, null vals / acq with m > 0, or a plan without a c-TPE fit.         */
+int tpe_plan_ctpe_score_points(tpe_plan_t p, const double *vals, int64_t m, int64_t ld,
+                               double *acq, double *T, uint8_t *active, int32_t on_device,
+                               void *stream);
+/* tpe_plan_sample_points under the c-TPE fit: configuration g = begin + j is
+ * drawn from the below mixtures of live model g % n_live -- an active hp
+ * takes, bit for bit, the value tpe_sample returns for that model's below
+ * mixture with key `seed`, stream = the hp's index and offset g -- and acq, T
+ * and active are what tpe_plan_ctpe_score_points returns for the drawn vals,
+ * bit for bit.  Any split of a range into calls gives the same numbers.  A
+ * below mixture of more than 2048 components (a good side of more than 2047
+ * rows) is drawn by tpe_sample's rejection sampler, as tpe_sample draws it.
+ * TPE_E_INVALID as tpe_plan_sample_points, or without a c-TPE fit.          */
+int tpe_plan_ctpe_sample_points(tpe_plan_t p, uint64_t seed, int64_t begin, int64_t m,
+                                int64_t ld, double *vals, double *acq, double *T,
+                                uint8_t *active, int32_t on_device, void *stream);
+/* tpe_plan_get_mixture of model `model` of the c-TPE fit.  TPE_E_INVALID for
+ * a dead model or without a c-TPE fit.  Synchronizes the device.            */
+int tpe_plan_ctpe_get_mixture(tpe_plan_t p, int32_t model, int32_t hp, int32_t side,
+                              double *w, double *mu, double *sigma, int64_t cap, int64_t *k);
+/* The live models in ascending order (live[*n_live], at most TPE_MAX_CON + 1
+ * entries) and, per live model, the rows the device counted on its feasible
+ * side: the complete rows for model 0, the complete rows with G <= 0 for a
+ * constraint model -- a cross-check of the caller's nb.  live and
+ * feasible_count may be NULL.  TPE_E_INVALID without a c-TPE fit.  Waits for
+ * the device.                                                               */
+int tpe_plan_ctpe_info(tpe_plan_t p, int32_t *live, int32_t *feasible_count, int32_t *n_live);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,

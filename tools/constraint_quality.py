@@ -18,7 +18,11 @@ random search: 200 evaluations, mean and range over 5 seeds.
 
 Methods: ``tpe.suggest(constraints=2)``; ``tpe.suggest`` on the loss (every
 objective) plus a fixed penalty for an infeasible trial; ``rand.suggest``.
-usage: python tools/constraint_quality.py [--evals 200] [--seeds 5] [--out FILE]
+``--model ctpe`` adds c-TPE: ``tpe.suggest_joint(constraints=2,
+constraint_model='ctpe')``, and beside it ``suggest_joint(constraints=2)`` -- the
+ranking through the same whole-configuration draw -- and writes to
+profiles/ctpe_quality.txt.
+usage: python tools/constraint_quality.py [--evals 200] [--seeds 5] [--model ctpe] [--out FILE]
 """
 import argparse
 import functools
@@ -54,8 +58,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--evals', type=int, default=200)
     ap.add_argument('--seeds', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'constraint_quality.txt'))
+    ap.add_argument('--model', choices=['rank', 'ctpe'], default='rank')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'ctpe_quality.txt' if args.model == 'ctpe'
+                                else 'constraint_quality.txt')
     import numpy as np
     from hyperopt_amd import fmin, hp, rand, tpe, Trials
     import hv_oracle as HO
@@ -94,6 +102,12 @@ def main():
         methods = [('tpe constraints=2', functools.partial(tpe.suggest, constraints=2, **obj), 0.0),
                    ('tpe + penalty', functools.partial(tpe.suggest, **obj), PENALTY[name]),
                    ('rand', rand.suggest, 0.0)]
+        if args.model == 'ctpe':
+            methods[1:1] = [
+                ('joint constraints=2', functools.partial(tpe.suggest_joint, constraints=2, **obj),
+                 0.0),
+                ('joint c-TPE', functools.partial(tpe.suggest_joint, constraints=2,
+                                                  constraint_model='ctpe', **obj), 0.0)]
         for label, algo, penalty in methods:
             vals = []
             for seed in range(args.seeds):
@@ -101,7 +115,7 @@ def main():
                 fmin(objective(f, penalty), space(), algo=algo, max_evals=args.evals, trials=t,
                      rstate=np.random.RandomState(100 + seed))
                 vals.append(figure(name, t))
-            say('%-5s %-18s %s %10.4f [%.4f, %.4f]'
+            say('%-5s %-19s %s %10.4f [%.4f, %.4f]'
                 % (name, label, FIGURE[name], np.mean(vals), min(vals), max(vals)))
 
 
