@@ -57,6 +57,7 @@ EXPORTS = (
     'tpe_plan_set_constraints', 'tpe_plan_constraint_get',
     'tpe_plan_ctpe_fit', 'tpe_plan_ctpe_score_points', 'tpe_plan_ctpe_sample_points',
     'tpe_plan_ctpe_get_mixture', 'tpe_plan_ctpe_info',
+    'tpe_plan_importance',
 )
 
 BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
@@ -204,6 +205,7 @@ def load_library(path: str = LIB_PATH):
             'tpe_plan_ctpe_get_mixture': (C.c_int, [vp, i32, i32, i32, _D, _D, _D, i64,
                                                     C.POINTER(i64)]),
             'tpe_plan_ctpe_info': (C.c_int, [vp, vp, vp, C.POINTER(i32)]),
+            'tpe_plan_importance': (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -707,6 +709,9 @@ class Plan(object):
         ghat = _f64(ghat)
         if nb.shape != (c + 1,) or ghat.shape != (c + 1,):
             raise ValueError('nb and ghat must hold C + 1 = %d entries' % (c + 1))
+        live = np.arange(c + 1) == 0
+        live[1:] = ghat[1:] < 1.0
+        self._fit_ghat, self._fit_gamma = ghat[live].copy(), None
         with e.lock:
             e.check(e.lib.tpe_plan_ctpe_fit(self.p, G.ctypes.data, int(c),
                                             ld if n is None else int(n), int(ld), 0,
@@ -800,8 +805,69 @@ class Plan(object):
                 self.p, int(seed) & (2 ** 64 - 1), int(begin), int(m), int(ld), vals_ptr,
                 acq_ptr, T_ptr or None, active_ptr or None, 1, stream))
 
+    # ---- importances from the fitted models (tpe_plan_importance)
+    def importance(self, n_nodes=1024, ghat=None, want_curves=False, stream=None):
+        """(D, norm, mass)[n_live, n_hp] of the last fit: per live model and hp
+        the Pearson divergence between the good trials' density and the
+        model's density of all trials, its share of the model's sum, and the
+        mass the nodes covered (1 when they cover the density).  After
+        ``ctpe_fit`` the live models are ``ctpe_info``'s, after ``fit`` model 0
+        alone.  ``ghat``: each live model's good-side share, in (0, 1];
+        ``None``: what the last ``ctpe_fit`` was given, or after ``fit`` its
+        good-side count over the history length (every row taken as
+        complete).  ``want_curves``: also (x, lb, la)[n_live, n_hp, n_nodes],
+        the nodes and the two log densities, NaN past an hp's last node.
+        ValueError before a fit, for ``n_nodes`` not a multiple of 64 in
+        [64, 65536], or a ``ghat`` outside (0, 1]."""
+        e = self.engine
+        if ghat is None:
+            ghat = self._fit_ghat
+            if ghat is None and self._fit_gamma is not None:
+                gamma, cap = self._fit_gamma
+                nb = max(0, min(int(np.ceil(gamma * np.sqrt(self.n))), cap))
+                ghat = [min(nb, self.n) / float(max(self.n, 1))]
+            if ghat is None:
+                raise ValueError('importance: no fit was made through this plan object; '
+                                 'pass ghat')
+        ghat = self._live_ghat(ghat)
+        n_live = ghat.size
+        g = int(n_nodes)
+        D, norm, mass = (np.empty((n_live, self.n_hp)) for _ in range(3))
+        curves = [np.empty((n_live, self.n_hp, max(g, 0))) for _ in range(3)] if want_curves else []
+        ptr = [c.ctypes.data for c in curves] or [None] * 3
+        with e.lock:
+            e.check(e.lib.tpe_plan_importance(self.p, g, ghat.ctypes.data, D.ctypes.data,
+                                              norm.ctypes.data, mass.ctypes.data, ptr[0], ptr[1],
+                                              ptr[2], 0, stream))
+        return (D, norm, mass) + tuple(curves)
+
+    def importance_device(self, n_nodes, ghat, D_ptr, norm_ptr, mass_ptr, x_ptr=0, lb_ptr=0,
+                          la_ptr=0, stream=None):
+        """The same into device memory (``ghat`` a host array).  Stream-ordered."""
+        e = self.engine
+        ghat = self._live_ghat(ghat)
+        with e.lock:
+            e.check(e.lib.tpe_plan_importance(self.p, int(n_nodes), ghat.ctypes.data, D_ptr,
+                                              norm_ptr, mass_ptr, x_ptr or None, lb_ptr or None,
+                                              la_ptr or None, 1, stream))
+
+    def _live_ghat(self, ghat):
+        """``ghat`` as float64 with one entry per live model of the last fit."""
+        try:
+            n_live = len(self.ctpe_info()[0])
+        except ValueError:               # (no c-TPE fit: the plan's own model alone)
+            n_live = 1
+        ghat = _f64(np.atleast_1d(ghat))
+        if ghat.shape != (n_live,):
+            raise ValueError('ghat must hold one entry per live model (%d)' % n_live)
+        return ghat
+
+    _fit_ghat = None     # the live models' ghat of the last fit, when it was a ctpe_fit
+    _fit_gamma = None    # (gamma, gamma_cap) of the last fit, when it was a plain one
+
     def fit(self, gamma=0.25, prior_weight=1.0, lf=25, gamma_cap=25, stream=None):
         e = self.engine
+        self._fit_ghat, self._fit_gamma = None, (float(gamma), int(gamma_cap))
         with e.lock:
             e.check(e.lib.tpe_plan_fit(self.p, float(gamma), int(gamma_cap), float(prior_weight),
                                        int(lf), stream))

@@ -16,6 +16,7 @@
 
 #include "tpe_anneal.hpp"
 #include "tpe_ctpe.hpp"
+#include "tpe_importance.hpp"
 #include "tpe_group_plan.hpp"
 #include "tpe_internal.hpp"
 #include "tpe_level_plan.hpp"
@@ -283,6 +284,13 @@ struct tpe_plan : PlanShape {
   size_t ct_T_cap = 0;
   void *d_ct_tab = nullptr;            // [n_live][P] draw tables
   int32_t ct_tab_cap = 0;              // ... of this many models
+  // importances (tpe_plan_importance, tpe_importance.hip): nothing
+  // allocated before the first call
+  double *d_im_part = nullptr;         // [n_live][P][tiles][2] tile sums
+  size_t im_part_cap = 0;
+  double *d_im_out = nullptr;          // [3][kCtpeModels][P] host-mode staging of D, norm, mass
+  double *d_im_curves = nullptr;       // [3][n_live][P][G] host-mode staging of x, lb, la
+  size_t im_curves_cap = 0;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -357,7 +365,8 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_bt_idx, p->d_obj, p->d_pcount, p->d_hv_i32, p->d_hv_f64, p->d_hv_alive,
                   p->d_hv_u, p->d_con, p->d_viol, p->d_ct_G, p->d_ct_keys, p->d_ct_mw,
                   p->d_ct_mmu, p->d_ct_msig, p->d_ct_info, p->d_ct_coef, p->d_ct_feas,
-                  p->d_ct_terms, p->d_ct_T, p->d_ct_tab};
+                  p->d_ct_terms, p->d_ct_T, p->d_ct_tab, p->d_im_part, p->d_im_out,
+                  p->d_im_curves};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -2795,6 +2804,85 @@ int tpe_plan_ctpe_info(tpe_plan_t p, int32_t *live, int32_t *feasible_count, int
     CKH(hipMemcpy(feasible_count, p->d_ct_feas, (size_t)p->ct_nlive * sizeof(int32_t),
                   hipMemcpyDeviceToHost));
   }
+  return TPE_OK;
+}
+
+// ---- importances from the fitted models (tpe_importance.hip) ----
+// Reads the fitted tables and mixtures only, as tpe_plan_score_points does.
+// Device mode enqueues two launches and returns; host mode stages through the
+// plan's scratch and waits for its own stream only.
+int tpe_plan_importance(tpe_plan_t p, int32_t n_nodes, const double *ghat, double *D, double *norm,
+                        double *mass, double *x, double *lb, double *la, int32_t on_device,
+                        void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (p->last_nb < 0)
+    return fail(h, TPE_E_INVALID,
+                "importance: the plan has not been fitted (tpe_plan_fit or tpe_plan_ctpe_fit first)");
+  if (n_nodes < kImpMinNodes || n_nodes > kImpMaxNodes || n_nodes % 64 != 0)
+    return fail(h, TPE_E_INVALID, "importance: n_nodes must be a multiple of 64 in [64, 65536]");
+  if (!ghat || !D || !norm || !mass)
+    return fail(h, TPE_E_INVALID, "importance: ghat, D, norm and mass must not be null");
+  const int32_t n_live = p->ct_ok ? p->ct_nlive : 1;
+  for (int l = 0; l < n_live; ++l)
+    if (!(ghat[l] > 0.0 && ghat[l] <= 1.0))
+      return fail(h, TPE_E_INVALID, "importance: need 0 < ghat[m] <= 1 for every live model");
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  const bool dev = on_device != 0;
+  const size_t P = (size_t)p->P, G = (size_t)n_nodes;
+  ImportanceArgs a{};
+  a.P = points_args(p, 0);
+  a.bk_info = p->d_ct_info;
+  a.bk_coef = p->d_ct_coef;
+  a.mmu = p->d_mmu;
+  a.bk_mmu = p->d_ct_mmu;
+  a.n_live = n_live;
+  a.G = n_nodes;
+  a.tiles = (n_nodes + kImpThreads - 1) / kImpThreads;
+  for (int l = 0; l < n_live; ++l) a.ghat[l] = ghat[l];
+  const size_t part = (size_t)n_live * P * (size_t)a.tiles * 2;
+  const bool curves = x || lb || la;
+  const size_t layer = (size_t)n_live * P * G;
+  if (part > p->im_part_cap || (!dev && curves && 3 * layer > p->im_curves_cap)) {
+    CKH(hipStreamSynchronize(st));  // (an earlier call may still use the old scratch)
+    if (part > p->im_part_cap) {
+      dfree(p->d_im_part);
+      p->d_im_part = nullptr;
+      p->im_part_cap = 0;
+      CKH(dalloc(&p->d_im_part, part));
+      p->im_part_cap = part;
+    }
+    if (!dev && curves && 3 * layer > p->im_curves_cap) {
+      dfree(p->d_im_curves);
+      p->d_im_curves = nullptr;
+      p->im_curves_cap = 0;
+      CKH(dalloc(&p->d_im_curves, 3 * layer));
+      p->im_curves_cap = 3 * layer;
+    }
+  }
+  a.part = p->d_im_part;
+  if (dev) {
+    a.D = D; a.norm = norm; a.mass = mass;
+    a.x = x; a.lb = lb; a.la = la;
+    CKH(launch_importance(a, st));
+    return TPE_OK;
+  }
+  const size_t out = (size_t)kCtpeModels * P;
+  if (!p->d_im_out) CKH(dalloc(&p->d_im_out, 3 * out));
+  a.D = p->d_im_out; a.norm = p->d_im_out + out; a.mass = p->d_im_out + 2 * out;
+  a.x = x ? p->d_im_curves : nullptr;
+  a.lb = lb ? p->d_im_curves + layer : nullptr;
+  a.la = la ? p->d_im_curves + 2 * layer : nullptr;
+  CKH(launch_importance(a, st));
+  const size_t nb = (size_t)n_live * P * 8;
+  CKH(hipMemcpyAsync(D, a.D, nb, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(norm, a.norm, nb, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(mass, a.mass, nb, hipMemcpyDeviceToHost, st));
+  if (x) CKH(hipMemcpyAsync(x, a.x, layer * 8, hipMemcpyDeviceToHost, st));
+  if (lb) CKH(hipMemcpyAsync(lb, a.lb, layer * 8, hipMemcpyDeviceToHost, st));
+  if (la) CKH(hipMemcpyAsync(la, a.la, layer * 8, hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
   return TPE_OK;
 }
 

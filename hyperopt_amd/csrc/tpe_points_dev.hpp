@@ -97,4 +97,66 @@ __device__ __forceinline__ double points_cat(const PointsArgs &A, int hp, double
   return lpb - lpa;
 }
 
+// ---- the same terms with the two lpdfs handed back separately (lb below, la
+// above) for k_importance (tpe_importance.hip): the arithmetic, statement for
+// statement, of the three functions above, which stay as they are so that the
+// kernels built on them keep their code
+template <bool LOGN>
+__device__ __forceinline__ void points_lse_pair(const PointsArgs &A, const tpe_hp &H, int hp,
+                                                double x, double &lb, double &la) {
+  const double y[1] = {(LOGN ? fast_log(x) : x) - H.prior_mu};
+  const double y2[1] = {y[0] * y[0]};
+  double lp[2];
+#pragma unroll
+  for (int mix = 0; mix < 2; ++mix) {
+    const int64_t slot = 2 * (int64_t)hp + mix;
+    lp[mix] = points_lse_mix<LOGN>(uniform_ptr(A.coef + slot * A.kcap), A.info[slot].K, x, y, y2);
+  }
+  lb = lp[0];
+  la = lp[1];
+}
+
+template <bool LOGN>
+__device__ __forceinline__ void points_erf_pair(const PointsArgs &A, const tpe_hp &H, int hp,
+                                                double x, bool act, double &lb, double &la) {
+#pragma clang fp contract(off)
+  double ub, lo;
+  quant_bounds<LOGN>(H, x, ub, lo);
+  double lp[2];
+#pragma unroll
+  for (int mix = 0; mix < 2; ++mix) {
+    const int64_t slot = 2 * (int64_t)hp + mix;
+    KDbl *cs = uniform_ptr(A.coef + slot * A.kcap);
+    const int K = A.info[slot].K;
+    double prob = 0.0;
+    for (int k0 = 0; k0 < K; k0 += 16) {
+      const int k1 = min(K, k0 + 16);
+      double pc = 0.0;
+      for (int k = k0; k < k1; ++k) {
+        const double cx = cs[coef_off(k, 0)], cy = cs[coef_off(k, 1)];
+        const double zu = (ub - cx) * cy, zl = (lo - cx) * cy;
+        if (__all(!act || erf_dead(zu, zl))) continue;
+        pc += erf_term<LOGN>(zu, zl, cs[coef_off(k, 2)]);
+      }
+      prob += pc;
+    }
+    lp[mix] = log(prob) - A.info[slot].log_pacc;
+  }
+  lb = lp[0];
+  la = lp[1];
+}
+
+__device__ __forceinline__ void points_cat_pair(const PointsArgs &A, int hp, double x, double &lb,
+                                                double &la) {
+  const int64_t sb = 2 * (int64_t)hp;
+  const int K = A.info[sb].K;
+  bool in = x >= 0.0 && x < (double)K;
+  const int64_t c = in ? (int64_t)x : 0;
+  in = in && (double)c == x;
+  const double *tb = reinterpret_cast<const double *>(A.coef + sb * A.kcap);
+  const double *ta = reinterpret_cast<const double *>(A.coef + (sb + 1) * A.kcap);
+  lb = in ? tb[coef_off(c, 0)] : NAN;
+  la = in ? ta[coef_off(c, 0)] : NAN;
+}
+
 }  // namespace tpe

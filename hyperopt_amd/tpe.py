@@ -549,6 +549,81 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     return out + (joint,) if multivariate else out
 
 
+def importances(domain, trials, n_nodes=1024, normalize=True, objectives=None,
+                hypervolume=False, constraints=None, constraint_model='rank',
+                return_curves=False, gamma=_default_gamma,
+                prior_weight=_default_prior_weight, engine=None):
+    """Which hyperparameters matter, read off the fitted Parzen models.
+
+    The history of ``trials`` is synced, pushed and fitted as ``score_configs``
+    does.  Per hp the device then integrates the Pearson divergence between the
+    density ``l`` of the good trials and the model's density of all trials
+    ``q = ghat l + (1 - ghat) g`` (PED-ANOVA) on ``n_nodes`` nodes
+    (a multiple of 64 in [64, 65536]): 0 for an hp whose good trials lie where
+    all trials lie, at most ``1 / ghat - 1``.  A conditional hp is integrated
+    over its own mixtures; an hp without an observation scores 0.  Returns
+    ``{label: importance}`` in ``domain.space.labels`` order, each divided by
+    their sum when ``normalize`` (all 0 stay 0).  The marginal models are what
+    is integrated: there is no ``multivariate``.
+
+    ``objectives``, ``hypervolume``, ``constraints``: as ``score_configs``.
+    ``constraint_model='ctpe'`` (with ``constraints``): one such dict per model,
+    ``{'objective': {...}, 'constraint 0': {...}, ...}`` -- which hp drives the
+    loss, and which drives the feasibility of each constraint.  A constraint
+    every trial satisfies has no model and maps to zeros.
+
+    ``return_curves``: the result is (importances, curves) with
+    ``curves[label] = (x, lpdf_below, lpdf_above, mass)`` (under 'ctpe' one such
+    dict per model): the hp's nodes, the two log densities there, and the mass
+    of q the nodes covered -- 1 up to the quadrature's error when they cover
+    the density.  ValueError: an empty history or one without a finite loss, a
+    bad ``n_nodes``, and ``check_constraint_model``'s."""
+    objectives = check_objectives(objectives)
+    hypervolume = check_hypervolume(hypervolume, objectives)
+    constraints = check_constraints(constraints)
+    cm = check_constraint_model(constraint_model, constraints)
+    cs = domain.space
+    st = _state(domain)
+    with st.lock:
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
+        n = hist.n
+        if n == 0:
+            raise ValueError('importances needs a history: trials holds no usable trial')
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, False, cm)
+        ranked = hist.M is not None or (cm == 'rank' and constraints is not None)
+        column = plan.pareto_get(n)[2] if ranked else hist.losses[:n]
+        if cm == 'ctpe':
+            ghat = ctpe_counts(column, hist.G[:, :n], gamma)[1]
+            live = [int(m) for m in plan.ctpe_info()[0]]
+            names = ['objective'] + ['constraint %d' % c for c in range(hist.G.shape[0])]
+        else:
+            n_c = int(np.isfinite(column).sum())
+            if n_c == 0:
+                raise ValueError('importances needs a complete trial: no loss of the history '
+                                 'is finite')
+            nb = int(max(0.0, min(math.ceil(gamma * math.sqrt(n)), DEFAULT_LF)))
+            ghat, live, names = np.array([min(nb, n_c) / float(n_c)]), [0], None
+        out = plan.importance(n_nodes, ghat[live], want_curves=return_curves)
+    D, norm, mass = out[:3]
+    score = norm if normalize else D
+    imp, curves = [], []
+    for m in range(len(names or [0])):
+        l = live.index(m) if m in live else None
+        imp.append({lab: float(score[l, i]) if l is not None else 0.0
+                    for i, lab in enumerate(cs.labels)})
+        if return_curves and l is not None:
+            ok = ~np.isnan(out[3][l])
+            curves.append({lab: tuple(c[l, i][ok[i]] for c in out[3:]) + (float(mass[l, i]),)
+                           for i, lab in enumerate(cs.labels)})
+        elif return_curves:
+            curves.append({lab: (np.empty(0),) * 3 + (0.0,) for lab in cs.labels})
+    if names is not None:
+        imp, curves = dict(zip(names, imp)), dict(zip(names, curves))
+    else:
+        imp, curves = imp[0], (curves or [None])[0]
+    return (imp, curves) if return_curves else imp
+
+
 class _Pool(object):
     """A candidate pool as columns, with its host-derived activity."""
 

@@ -708,6 +708,69 @@ int tpe_plan_ctpe_get_mixture(tpe_plan_t p, int32_t model, int32_t hp, int32_t s
  * the device.                                                               */
 int tpe_plan_ctpe_info(tpe_plan_t p, int32_t *live, int32_t *feasible_count, int32_t *n_live);
 
+/* ---- importances from the fitted Parzen models --------------
+ * PED-ANOVA's density form.  The live models are those of the c-TPE section:
+ * after tpe_plan_ctpe_fit model 0 and one bank model per live constraint, in
+ * tpe_plan_ctpe_info's order; after a plain tpe_plan_fit model 0 alone
+ * (n_live = 1).  For live model m and hp d let l and g be the fitted below and
+ * above densities -- exp of the lpdfs tpe_plan_score_points takes the
+ * difference of: p_accept included where the lpdf includes it, a density in x
+ * for the log kinds, a probability mass for the quantized and categorical
+ * kinds -- and q = ghat[m] l + (1 - ghat[m]) g the model's density of all
+ * trials.  Then
+ *   D[m][d]    = (1 - ghat)^2 sum_i w_i (l_i - g_i)^2 / q_i,
+ *   mass[m][d] = sum_i w_i q_i,
+ *   norm[m][d] = D[m][d] / sum_d D[m][d]   (d ascending; 0 where the sum is 0)
+ * over the nodes below: D is the Pearson divergence int (l / q - 1)^2 q, >= 0,
+ * at most 1 / ghat - 1, and 0 iff l == g on the nodes; ghat == 1 gives 0
+ * exactly; mass is 1 up to the quadrature's error where the nodes cover the
+ * density.  With a = log l, b = log g, hi = max(a, b) a node adds
+ *   f  = w e^hi (e^(a - hi) - e^(b - hi))^2 / (ghat e^(a - hi) + (1 - ghat) e^(b - hi)),
+ *   qw = w e^hi (ghat e^(a - hi) + (1 - ghat) e^(b - hi))
+ * in plain fp64 (f = qw = 0 when a = b = -inf).  Nodes are taken in tiles of
+ * 256: a tile's values are added in the tree v[t] += v[t + s], s = 128, 64, ..,
+ * 1 (values past the last node are 0), the tiles of an (m, d) in ascending
+ * order, and D = (1 - ghat)^2 times that sum: no number depends on the launch.
+ *
+ * Nodes, G = n_nodes of them at most, generated on the device from the hp
+ * descriptor and never stored unless the curves are asked for:
+ *  - continuous kinds without q: the G midpoints y_i = lo + (i + 0.5) h, h =
+ *    (hi - lo) / G, of [lo, hi] in the fit's space (y for the uniform / normal
+ *    kinds, y = log x for the log kinds).  Bounded kinds: [low, high] of the
+ *    descriptor.  Unbounded kinds: lo = min_mu - 6 prior_sigma, hi = max_mu + 6
+ *    prior_sigma with min_mu / max_mu the first / last component mean of the
+ *    model's two sorted mixtures (the prior is among them; every sigma is
+ *    clipped to prior_sigma, so less than 2e-9 of a component lies outside).
+ *    x = y and w = h, or for the log kinds x = E(y) and w = h x (dx = x dy),
+ *    where E is exp as this fixed sequence of separately rounded fp64
+ *    operations: k = rint(y * 1.4426950408889634), r = (y - k *
+ *    0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33, p = the Horner form
+ *    (..(c13 r + c12) r + ..) r + c0 with c_j = 1 / j!, E = ldexp(p, k);
+ *  - quantized kinds: the lattice values x = q j whose cell [x - q/2, x + q/2]
+ *    meets the same interval taken in x ([exp(lo), exp(hi)] for the log kinds):
+ *    j from ceil(lo / q - 0.5) -- at least 0 for the log kinds -- to floor(hi /
+ *    q + 0.5); for a bounded kind an end value whose cell misses [lo, hi] by a
+ *    rounding (q j + q/2 < lo, or q j - q/2 > hi) is dropped.  w = 1: the lpdf
+ *    is a probability mass, over the cell clipped as the lpdf clips it.  With
+ *    more than G values (at most 2^52 are counted), every s-th one from the
+ *    first with s = ceil(count / G) and w = s;
+ *  - categorical kinds: every option 0 .. upper - 1 with w = 1; with more than
+ *    G options, every s-th one as above.
+ *
+ * n_nodes is a multiple of 64 in [64, 65536].  ghat[n_live] is a host array
+ * (ghat_m of the c-TPE fit; for a plain fit the good side's share of the
+ * complete rows).  D, norm, mass: [n_live][n_hp].  x, lb, la: optional curves
+ * [n_live][n_hp][n_nodes] -- the nodes and the two log densities at them, NaN
+ * past an (m, d)'s last node -- each may be NULL.  on_device != 0: the outputs
+ * are device pointers, stream-ordered, no host synchronisation; else host
+ * buffers, synchronous.  A conditional hp is integrated over its own mixtures
+ * like any other; an hp without an observation has l == g and scores 0.
+ * TPE_E_INVALID: before a fit, an n_nodes outside the rule, a ghat[m] outside
+ * (0, 1], or a null ghat / D / norm / mass.                                  */
+int tpe_plan_importance(tpe_plan_t p, int32_t n_nodes, const double *ghat, double *D,
+                        double *norm, double *mass, double *x, double *lb, double *la,
+                        int32_t on_device, void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
