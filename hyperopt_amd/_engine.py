@@ -57,7 +57,7 @@ EXPORTS = (
     'tpe_plan_set_constraints', 'tpe_plan_constraint_get',
     'tpe_plan_ctpe_fit', 'tpe_plan_ctpe_score_points', 'tpe_plan_ctpe_sample_points',
     'tpe_plan_ctpe_get_mixture', 'tpe_plan_ctpe_info',
-    'tpe_plan_importance',
+    'tpe_plan_importance', 'tpe_plan_group_importance_pairs',
 )
 
 BATCH_MAX = 1024            # tpe_plan_group_batch_points' largest k
@@ -206,6 +206,8 @@ def load_library(path: str = LIB_PATH):
                                                     C.POINTER(i64)]),
             'tpe_plan_ctpe_info': (C.c_int, [vp, vp, vp, C.POINTER(i32)]),
             'tpe_plan_importance': (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+            'tpe_plan_group_importance_pairs': (C.c_int, [vp, i32, dbl, vp, i32, vp, vp, vp, vp, vp,
+                                                          vp, i32, vp]),
             'tpe_plan_last_stats': (C.c_int, [vp, _D, _D]),
             'tpe_plan_profile': (C.c_int, [vp, i32]),
             'tpe_plan_profile_read': (C.c_int, [vp, i32, _D, C.POINTER(i64), _D]),
@@ -850,6 +852,45 @@ class Plan(object):
             e.check(e.lib.tpe_plan_importance(self.p, int(n_nodes), ghat.ctypes.data, D_ptr,
                                               norm_ptr, mass_ptr, x_ptr or None, lb_ptr or None,
                                               la_ptr or None, 1, stream))
+
+    # ---- pairwise importances under the group models
+    # (tpe_plan_group_importance_pairs)
+    def importance_pairs(self, n_nodes, ghat, pairs, want_curves=False, stream=None):
+        """(D, Z_below, Z_above)[n_pairs] of the last ``group_fit``: per pair
+        (a, b) of hp indices, a < b in one group, the Pearson divergence of the
+        pair's joint below density against its density of all trials on the
+        ``n_nodes`` x ``n_nodes`` node grid, and the masses the grid covered on
+        the two sides.  ``ghat``: the good side's share, in (0, 1] -- the one
+        ``importance`` is given for model 0.  ``want_curves``: also
+        (x_a, x_b)[n_pairs, n_nodes] and log_L[n_pairs, 2, n_nodes, n_nodes]
+        (below, above), NaN past a dim's last node.  ValueError without a
+        group fit, for a pair across groups or with a >= b, for ``n_nodes``
+        not a multiple of 16 in [16, 256], a ``ghat`` outside (0, 1], or a
+        workspace past the engine's cap."""
+        e = self.engine
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        n, g = len(pairs), int(n_nodes)
+        D, zb, za = (np.empty(n) for _ in range(3))
+        curves = []
+        if want_curves:
+            curves = [np.empty((n, max(g, 0))), np.empty((n, max(g, 0))),
+                      np.empty((n, 2, max(g, 0), max(g, 0)))]
+        ptr = [c.ctypes.data for c in curves] or [None] * 3
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_importance_pairs(
+                self.p, g, float(ghat), pairs.ctypes.data, n, D.ctypes.data, zb.ctypes.data,
+                za.ctypes.data, ptr[0], ptr[1], ptr[2], 0, stream))
+        return (D, zb, za) + tuple(curves)
+
+    def importance_pairs_device(self, n_nodes, ghat, pairs, D_ptr, zb_ptr, za_ptr, xa_ptr=0,
+                                xb_ptr=0, logl_ptr=0, stream=None):
+        """The same into device memory (``pairs`` a host array).  Stream-ordered."""
+        e = self.engine
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        with e.lock:
+            e.check(e.lib.tpe_plan_group_importance_pairs(
+                self.p, int(n_nodes), float(ghat), pairs.ctypes.data, len(pairs), D_ptr, zb_ptr,
+                za_ptr, xa_ptr or None, xb_ptr or None, logl_ptr or None, 1, stream))
 
     def _live_ghat(self, ghat):
         """``ghat`` as float64 with one entry per live model of the last fit."""

@@ -17,6 +17,7 @@
 #include "tpe_anneal.hpp"
 #include "tpe_ctpe.hpp"
 #include "tpe_importance.hpp"
+#include "tpe_pair_importance.hpp"
 #include "tpe_group_plan.hpp"
 #include "tpe_internal.hpp"
 #include "tpe_level_plan.hpp"
@@ -291,6 +292,14 @@ struct tpe_plan : PlanShape {
   double *d_im_out = nullptr;          // [3][kCtpeModels][P] host-mode staging of D, norm, mass
   double *d_im_curves = nullptr;       // [3][n_live][P][G] host-mode staging of x, lb, la
   size_t im_curves_cap = 0;
+  // pairwise importances (tpe_plan_group_importance_pairs, tpe_pair_importance.hip;
+  // DESIGN 5.22): the call's workspace with the host-mode staging behind it, and
+  // the slot / pair tables
+  double *d_pi_ws = nullptr;
+  size_t pi_ws_cap = 0;
+  int32_t *d_pi_idx = nullptr;         // [n_slot] hps, then [n_pair][2] slots
+  size_t pi_idx_cap = 0;
+  std::vector<int32_t> pi_idx;         // ... on the host (the upload's source)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   std::vector<hipGraphNode_t> fit_nodes, draw_nodes;
@@ -366,7 +375,7 @@ void plan_free_buffers(tpe_plan *p) {
                   p->d_hv_u, p->d_con, p->d_viol, p->d_ct_G, p->d_ct_keys, p->d_ct_mw,
                   p->d_ct_mmu, p->d_ct_msig, p->d_ct_info, p->d_ct_coef, p->d_ct_feas,
                   p->d_ct_terms, p->d_ct_T, p->d_ct_tab, p->d_im_part, p->d_im_out,
-                  p->d_im_curves};
+                  p->d_im_curves, p->d_pi_ws, p->d_pi_idx};
   for (void *b : bufs) dfree(b);
   if (p->h_results) (void)hipHostFree(p->h_results);
   p->h_results = nullptr;
@@ -3383,6 +3392,118 @@ int tpe_plan_group_get_mixture(tpe_plan_t p, int32_t group, int32_t hp, int32_t 
   if (w) CKH(hipMemcpy(w, p->d_gcw + ds, bytes, hipMemcpyDeviceToHost));
   if (mu) CKH(hipMemcpy(mu, p->d_gcmu + ds, bytes, hipMemcpyDeviceToHost));
   if (sigma) CKH(hipMemcpy(sigma, p->d_gcsig + ds, bytes, hipMemcpyDeviceToHost));
+  return TPE_OK;
+}
+
+// ---- pairwise importances under the group models (tpe_pair_importance.hip;
+// DESIGN 5.22).  Reads the group fit only.  Device mode enqueues the table
+// upload and five launches; host mode stages behind the workspace and waits
+// for its own stream only.
+int tpe_plan_group_importance_pairs(tpe_plan_t p, int32_t n_nodes, double ghat,
+                                    const int32_t *pairs, int32_t n_pairs, double *D,
+                                    double *Z_below, double *Z_above, double *x_a, double *x_b,
+                                    double *logL, int32_t on_device, void *stream) {
+  if (!p) return TPE_E_INVALID;
+  tpe_engine *h = p->eng;
+  if (!p->group_ok)
+    return fail(h, TPE_E_INVALID, "importance_pairs: no group fit (tpe_plan_group_fit first)");
+  if (n_nodes < kPairMinNodes || n_nodes > kPairMaxNodes || n_nodes % 16 != 0)
+    return fail(h, TPE_E_INVALID, "importance_pairs: n_nodes must be a multiple of 16 in [16, 256]");
+  if (!(ghat > 0.0 && ghat <= 1.0))
+    return fail(h, TPE_E_INVALID, "importance_pairs: need 0 < ghat <= 1");
+  if (n_pairs < 0 || n_pairs > 65535)
+    return fail(h, TPE_E_INVALID, "importance_pairs: need 0 <= n_pairs <= 65535");
+  if (n_pairs == 0) return TPE_OK;
+  if (!pairs || !D || !Z_below || !Z_above)
+    return fail(h, TPE_E_INVALID, "importance_pairs: pairs, D, Z_below and Z_above must not be null");
+  std::vector<int32_t> slot_of((size_t)p->P, -1);
+  for (int32_t i = 0; i < n_pairs; ++i) {
+    const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+    if (a < 0 || b >= p->P || a >= b)
+      return fail(h, TPE_E_INVALID, "importance_pairs: a pair needs 0 <= a < b < n_hp");
+    if (p->gpart.group_of_hp[(size_t)a] != p->gpart.group_of_hp[(size_t)b])
+      return fail(h, TPE_E_INVALID, "importance_pairs: the hps of a pair are not in one group");
+    slot_of[(size_t)a] = slot_of[(size_t)b] = 0;
+  }
+  std::vector<int32_t> idx;
+  for (int32_t i = 0; i < p->P; ++i)
+    if (slot_of[(size_t)i] == 0) {
+      slot_of[(size_t)i] = (int32_t)idx.size();
+      idx.push_back(i);
+    }
+  const int32_t n_slot = (int32_t)idx.size();
+  for (int32_t i = 0; i < 2 * n_pairs; ++i) idx.push_back(slot_of[(size_t)pairs[i]]);
+  // group 0 holds every row of a side: gkb_max bounds every below K, n + 1 every above K
+  const PairLayout lay = pair_layout(n_nodes, n_slot, n_pairs, p->gkb_max, p->n + 1);
+  const bool dev = on_device != 0;
+  const size_t np = (size_t)n_pairs, G = (size_t)n_nodes;
+  const size_t stage = dev ? 0 : 3 * np + (x_a ? np * G : 0) + (x_b ? np * G : 0) +
+                                     (logL ? 2 * np * G * G : 0);
+  const size_t need = (size_t)lay.total + stage;
+  if ((int64_t)need * 8 > kPairMaxBytes)
+    return fail(h, TPE_E_INVALID,
+                "importance_pairs: the workspace of " + std::to_string(need * 8) + " bytes (" +
+                    std::to_string(n_slot) + " hps x " + std::to_string(lay.fk[0] + lay.fk[1]) +
+                    " components x " + std::to_string(n_nodes) + " nodes of factors, " +
+                    std::to_string(n_pairs) + " pairs of planes) is past the cap of " +
+                    std::to_string(kPairMaxBytes));
+  CKH(hipSetDevice(h->device));
+  hipStream_t st = pick_stream(h, stream);
+  if (need > p->pi_ws_cap || idx.size() > p->pi_idx_cap) {
+    CKH(hipStreamSynchronize(st));  // (an earlier call may still use the old buffers)
+    if (need > p->pi_ws_cap) {
+      dfree(p->d_pi_ws);
+      p->d_pi_ws = nullptr;
+      p->pi_ws_cap = 0;
+      CKH(dalloc(&p->d_pi_ws, need));
+      p->pi_ws_cap = need;
+    }
+    if (idx.size() > p->pi_idx_cap) {
+      dfree(p->d_pi_idx);
+      p->d_pi_idx = nullptr;
+      p->pi_idx_cap = 0;
+      CKH(dalloc(&p->d_pi_idx, idx.size()));
+      p->pi_idx_cap = idx.size();
+    }
+  }
+  p->pi_idx.swap(idx);
+  CKH(hipMemcpyAsync(p->d_pi_idx, p->pi_idx.data(), p->pi_idx.size() * 4, hipMemcpyHostToDevice, st));
+  PairArgs a{};
+  a.hps = p->d_hps;
+  a.info = p->d_info;
+  a.mmu = p->d_mmu;
+  a.pprior = p->d_pprior;
+  a.group_of_hp = p->d_ggroup_of_hp;
+  a.gK = p->d_gcount;
+  a.gw = p->d_gw;
+  a.cmu = p->d_gcmu;
+  a.csig = p->d_gcsig;
+  a.kcap = p->kcap;
+  a.slot_hp = p->d_pi_idx;
+  a.pair_slot = p->d_pi_idx + n_slot;
+  a.lay = lay;
+  a.ghat = ghat;
+  a.ws = p->d_pi_ws;
+  if (dev) {
+    a.D = D; a.Zb = Z_below; a.Za = Z_above;
+    a.xa = x_a; a.xb = x_b; a.logL = logL;
+    CKH(launch_pair_importance(a, st));
+    return TPE_OK;
+  }
+  double *s = p->d_pi_ws + lay.total;
+  a.D = s; a.Zb = s + np; a.Za = s + 2 * np;
+  s += 3 * np;
+  if (x_a) { a.xa = s; s += np * G; }
+  if (x_b) { a.xb = s; s += np * G; }
+  if (logL) a.logL = s;
+  CKH(launch_pair_importance(a, st));
+  CKH(hipMemcpyAsync(D, a.D, np * 8, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(Z_below, a.Zb, np * 8, hipMemcpyDeviceToHost, st));
+  CKH(hipMemcpyAsync(Z_above, a.Za, np * 8, hipMemcpyDeviceToHost, st));
+  if (x_a) CKH(hipMemcpyAsync(x_a, a.xa, np * G * 8, hipMemcpyDeviceToHost, st));
+  if (x_b) CKH(hipMemcpyAsync(x_b, a.xb, np * G * 8, hipMemcpyDeviceToHost, st));
+  if (logL) CKH(hipMemcpyAsync(logL, a.logL, 2 * np * G * G * 8, hipMemcpyDeviceToHost, st));
+  CKH(hipStreamSynchronize(st));
   return TPE_OK;
 }
 

@@ -71,6 +71,40 @@ __host__ __device__ inline ImpNodes importance_nodes(const tpe_hp &H, int kind, 
   return n;
 }
 
+// exp(y) of a continuous log-kind node as a fixed sequence of fp64 operations
+// (each rounded on its own), so that a node has the same bits wherever the
+// rule is restated: k = rint(y log2 e), r = (y - k ln2_hi) - k ln2_lo (|r| <=
+// 0.35, k ln2_hi exact: ln2_hi has 21 trailing zero bits), the degree-13 Taylor
+// polynomial of exp(r) by Horner's rule (truncation below 4e-18), then an
+// exact ldexp.  Within 2 ulp of exp(y): the node is the rule's x, and its
+// weight h x is taken at that x.
+__device__ __forceinline__ double node_exp(double y) {
+#pragma clang fp contract(off)
+  constexpr double c[14] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0,
+                            1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0, 1.0 / 3628800.0,
+                            1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0};
+  const double k = rint(y * 1.4426950408889634);
+  const double r = (y - k * 0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33;
+  double p = c[13];
+#pragma unroll
+  for (int j = 12; j >= 0; --j) p = p * r + c[j];
+  return ldexp(p, (int)fmin(fmax(k, -2200.0), 2200.0));
+}
+
+// node i < N.count of the rule above and its weight
+__device__ __forceinline__ void importance_node(const ImpNodes &N, const tpe_hp &H, int kind, int i,
+                                                double &x, double &w) {
+#pragma clang fp contract(off)
+  if (kind == KIND_LSE_G || kind == KIND_LSE_L) {
+    const double y = N.lo + ((double)i + 0.5) * N.h;
+    x = kind == KIND_LSE_L ? node_exp(y) : y;
+    w = kind == KIND_LSE_L ? N.h * x : N.h;
+  } else {
+    x = (kind == KIND_CAT ? 1.0 : H.q) * (N.j0 + (double)i * N.s);
+    w = N.s;
+  }
+}
+
 struct ImportanceArgs {
   PointsArgs P;               // hps, n_hp, kcap and model 0's info / coef; the rest unused
   const MixInfo *bk_info;     // the bank (live positions l >= 1 at l - 1; tpe_ctpe.hpp)

@@ -552,7 +552,7 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
 def importances(domain, trials, n_nodes=1024, normalize=True, objectives=None,
                 hypervolume=False, constraints=None, constraint_model='rank',
                 return_curves=False, gamma=_default_gamma,
-                prior_weight=_default_prior_weight, engine=None):
+                prior_weight=_default_prior_weight, engine=None, pairs=None, pair_nodes=64):
     """Which hyperparameters matter, read off the fitted Parzen models.
 
     The history of ``trials`` is synced, pushed and fitted as ``score_configs``
@@ -577,19 +577,36 @@ def importances(domain, trials, n_nodes=1024, normalize=True, objectives=None,
     dict per model): the hp's nodes, the two log densities there, and the mass
     of q the nodes covered -- 1 up to the quadrature's error when they cover
     the density.  ValueError: an empty history or one without a finite loss, a
-    bad ``n_nodes``, and ``check_constraint_model``'s."""
+    bad ``n_nodes``, and ``check_constraint_model``'s.
+
+    ``pairs``: also the pairwise importances under the group models (DESIGN
+    5.22), which see an interaction that no marginal shows.  ``True``: every
+    pair of labels inside a group of ``hp_groups``; or a sequence of
+    ``(label, label)``, each put in hp order.  The history is then also fitted
+    as ``multivariate='groups'`` does, and the pair's joint densities are
+    integrated on a ``pair_nodes`` x ``pair_nodes`` grid (a multiple of 16 in
+    [16, 256]) with the same ``ghat``.  The result gains an element
+    ``{(label_a, label_b): D_ab}`` behind those above -- always the raw
+    divergence, comparable with the per-hp ones under ``normalize=False`` --
+    and with ``return_curves`` one more, ``{(label_a, label_b): (x_a, x_b,
+    log_l[G_a, G_b], log_g[G_a, G_b], Z_below, Z_above)}``.  ValueError: an
+    unknown label, a label paired with itself, a pair across groups, a bad
+    ``pair_nodes``, ``constraint_model='ctpe'`` (the constraint models are
+    marginal), and ``multivariate='groups'``'s own."""
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
     constraints = check_constraints(constraints)
     cm = check_constraint_model(constraint_model, constraints)
     cs = domain.space
+    pair_ids = None if pairs is None or pairs is False else _pair_indices(cs, pairs, cm)
     st = _state(domain)
     with st.lock:
         hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
         n = hist.n
         if n == 0:
             raise ValueError('importances needs a history: trials holds no usable trial')
-        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, False, cm)
+        plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma,
+                        False if pair_ids is None else 'groups', cm)
         ranked = hist.M is not None or (cm == 'rank' and constraints is not None)
         column = plan.pareto_get(n)[2] if ranked else hist.losses[:n]
         if cm == 'ctpe':
@@ -604,6 +621,8 @@ def importances(domain, trials, n_nodes=1024, normalize=True, objectives=None,
             nb = int(max(0.0, min(math.ceil(gamma * math.sqrt(n)), DEFAULT_LF)))
             ghat, live, names = np.array([min(nb, n_c) / float(n_c)]), [0], None
         out = plan.importance(n_nodes, ghat[live], want_curves=return_curves)
+        if pair_ids is not None:
+            pout = plan.importance_pairs(pair_nodes, ghat[0], pair_ids, want_curves=return_curves)
     D, norm, mass = out[:3]
     score = norm if normalize else D
     imp, curves = [], []
@@ -621,7 +640,44 @@ def importances(domain, trials, n_nodes=1024, normalize=True, objectives=None,
         imp, curves = dict(zip(names, imp)), dict(zip(names, curves))
     else:
         imp, curves = imp[0], (curves or [None])[0]
-    return (imp, curves) if return_curves else imp
+    if pair_ids is None:
+        return (imp, curves) if return_curves else imp
+    keys = [(cs.labels[a], cs.labels[b]) for a, b in pair_ids]
+    pimp = {k: float(d) for k, d in zip(keys, pout[0])}
+    if not return_curves:
+        return imp, pimp
+    pcurves = {}
+    for j, k in enumerate(keys):
+        xa, xb = pout[3][j], pout[4][j]
+        oa, ob = ~np.isnan(xa), ~np.isnan(xb)
+        pcurves[k] = (xa[oa], xb[ob], pout[5][j, 0][np.ix_(oa, ob)], pout[5][j, 1][np.ix_(oa, ob)],
+                      float(pout[1][j]), float(pout[2][j]))
+    return imp, curves, pimp, pcurves
+
+
+def _pair_indices(cs, pairs, cm):
+    """``importances``' ``pairs=`` as [(a, b)] hp indices, a < b in one group."""
+    if cm == 'ctpe':
+        raise ValueError("pairs needs the plain fit: the constraint models of "
+                         "constraint_model='ctpe' are marginal")
+    index = {lab: i for i, lab in enumerate(cs.labels)}
+    groups = hp_groups(cs)
+    if pairs is True:
+        return [(index[a], index[b]) for g in groups for i, a in enumerate(g) for b in g[i + 1:]]
+    group_of = {lab: g for g, labs in enumerate(groups) for lab in labs}
+    out = []
+    for pair in pairs:
+        a, b = pair
+        for lab in (a, b):
+            if lab not in index:
+                raise ValueError('pairs: unknown hyperparameter label %r' % (lab,))
+        if a == b:
+            raise ValueError('pairs: %r is paired with itself' % (a,))
+        if group_of[a] != group_of[b]:
+            raise ValueError('pairs: %r and %r are not in one group of hp_groups, so no joint '
+                             'model holds them both' % (a, b))
+        out.append((min(index[a], index[b]), max(index[a], index[b])))
+    return out
 
 
 class _Pool(object):

@@ -771,6 +771,48 @@ int tpe_plan_importance(tpe_plan_t p, int32_t n_nodes, const double *ghat, doubl
                         double *norm, double *mass, double *x, double *lb, double *la,
                         int32_t on_device, void *stream);
 
+/* ---- pairwise importances under the group models ------------
+ * The marginal importances above cannot see an interaction of two hps.  For a
+ * pair (a, b), a < b in hp order, of hps of one group of tpe_plan_group_fit,
+ * and side s of that group's fit -- weights w_k and per-dim kernels kappa_dk,
+ * component 0 the prior, no truncation normaliser -- the pair density on the
+ * node grid is
+ *   L_s[i][j] = sum_k w_k kappa_ak(x_a,i) kappa_bk(x_b,j),
+ * with the nodes x and weights w of each dim those of the section above for
+ * this call's n_nodes.  The kernels are evaluated in plain fp64 in the linear
+ * domain: a continuous dim's normal density exp(-z^2 / 2) / (sqrt(2 pi) sigma),
+ * z = (y - mu) / max(sigma, EPS), at the node in the fit's space (a log kind:
+ * y = log x and the density in x, divided by max(sigma, EPS) x, against the
+ * node weight h x); a quantized dim's cell mass Phi(ub) - Phi(lb) on the
+ * quantized lpdf's bounds, taken in the complement of the nearer tail; a
+ * categorical dim's ((c == o) + a pi[c]) / (1 + a), the prior component pi[c].
+ * Underflow to 0 is left as it is.  With W_ij = w_a,i w_b,j:
+ *   Z_s = sum_ij W_ij L_s[i][j],  l = L_below / Z_below,  g = L_above / Z_above,
+ *   q = ghat l + (1 - ghat) g,  D_ab = (1 - ghat)^2 sum_ij W_ij (l - g)^2 / q;
+ * a node where both are 0 adds 0, ghat == 1 gives exactly 0.  ghat is the one
+ * share the marginal call is given for model 0, so that D_ab compares with D_a
+ * and D_b.  Sums run per 64 x 64 tile of the grid in a fixed order, then over
+ * the tiles in ascending order; L_s sums k ascending on the fp64 matrix cores:
+ * a pair's numbers depend on the fit and n_nodes alone, not on the other pairs.
+ *
+ * n_nodes is a multiple of 16 in [16, 256].  pairs[n_pairs][2] is a host array
+ * of hp indices.  D, Z_below, Z_above: [n_pairs]; the Z are the masses the
+ * nodes covered.  Optional x_a, x_b [n_pairs][n_nodes] and logL
+ * [n_pairs][2][n_nodes][n_nodes] (log L_below, then log L_above; i the slower
+ * index), NaN past a dim's last node; each may be NULL.  on_device and stream
+ * as above.  The workspace is the factors, 8 n_nodes (K_below + K_above) bytes
+ * per hp named by a pair with K the largest group's component counts padded to
+ * 4, and 16 n_nodes^2 bytes per pair, with the host outputs' staging; a call
+ * past 1 GiB is refused.  TPE_E_INVALID: no group fit, a pair across groups or
+ * with a >= b, an n_nodes or ghat outside the rule, more than 65535 pairs, a
+ * null pairs / D / Z_below / Z_above, or a workspace past the cap (the message
+ * names the sizes).                                                          */
+int tpe_plan_group_importance_pairs(tpe_plan_t p, int32_t n_nodes, double ghat,
+                                    const int32_t *pairs, int32_t n_pairs, double *D,
+                                    double *Z_below, double *Z_above, double *x_a,
+                                    double *x_b, double *logL, int32_t on_device,
+                                    void *stream);
+
 /* Device time (ms) of the last tpe_plan_suggest, from HIP events on the
  * plan's stream (recorded only while tpe_plan_profile is on, else NaN: an
  * event record drains the pipeline between launches); and the (candidate,
