@@ -787,6 +787,7 @@ FitArgs fit_args(tpe_plan *p, int32_t n_below, double prior_weight, int32_t lf,
   a.ld = p->ncap;
   a.n_below = n_below;
   a.lf = lf;
+  a.window = switches().fit_window ? 1 : 0;
   a.prior_weight = prior_weight;
   a.pprior = p->d_pprior;
   a.mw = p->d_mw;

@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "tpe_device.hpp"
+#include "tpe_fit_window.hpp"
 
 #pragma clang fp contract(off)
 
@@ -56,7 +57,7 @@ constexpr int kPreN = 12 * kFitThreads;      // histories whose values k_fit pre
 constexpr int kOffKeys = 0;                               // u64 [kSortCap]
 constexpr int kOffPosA = kOffKeys + 8 * kSortCap;         // u16 [kSortCap]
 constexpr int kOffPosB = kOffPosA + 2 * kSortCap;         // u16 [kSortCap]
-constexpr int kOffCnt = kOffPosB + 2 * kSortCap;          // u32 [256][16]
+constexpr int kOffCnt = kOffPosB + 2 * kSortCap;          // u32 [16][256]
 constexpr int kOffRun = kOffCnt + 4 * kDigits * kFitWaves;  // u32 [16][256]
 constexpr int kFitLds = kOffRun + 4 * kDigits * kFitWaves;  // 155,648 B
 static_assert(4 * 8 * kMixStride <= kFitLds, "LDS mixture arrays");
@@ -449,11 +450,10 @@ __device__ __forceinline__ PosT *block_sort_perm(const uint64_t *keys, PosT *a, 
     // fallback: its two key buffers, b the positions)
     uint64_t *bk = reinterpret_cast<uint64_t *>(cnt);
     // the 32-bit window: from the lowest varying bit, or up to the highest
-    const int hb = 63 - __builtin_clzll(vary | 1ull), lb = vary ? __builtin_ctzll(vary) : 0;
-    const int shift = max(lb, hb - 31);
+    const FitWindow W = fit_window(vary);
     uint32_t *kb = reinterpret_cast<uint32_t *>(cnt);
     uint16_t *pb = reinterpret_cast<uint16_t *>(kb + 2 * kFitThreads);
-    if (merge_sort_packed<1>(keys, n, shift, shift > lb, reinterpret_cast<uint16_t *>(a), kb,
+    if (merge_sort_packed<1>(keys, n, W.shift, W.lossy, reinterpret_cast<uint16_t *>(a), kb,
                              kb + kFitThreads, pb, pb + kFitThreads))
       return a;
     uint16_t *bp = reinterpret_cast<uint16_t *>(b);
@@ -481,9 +481,8 @@ __device__ __forceinline__ PosT *block_sort_perm(const uint64_t *keys, PosT *a, 
     static_assert(8 * 4 * kMergeMax + 12 * 4 * kMergeMax <= kOffPosB, "merge buffers below b");
     uint32_t *kb = reinterpret_cast<uint32_t *>(const_cast<uint64_t *>(keys) + 4 * kMergeMax);
     uint16_t *pb = reinterpret_cast<uint16_t *>(kb + 8 * kMergeMax);
-    const int hb = 63 - __builtin_clzll(vary | 1ull), lb = vary ? __builtin_ctzll(vary) : 0;
-    const int shift = max(lb, hb - 31);
-    if (merge_sort_packed<4>(keys, n, shift, shift > lb, reinterpret_cast<uint16_t *>(b), kb,
+    const FitWindow W = fit_window(vary);
+    if (merge_sort_packed<4>(keys, n, W.shift, W.lossy, reinterpret_cast<uint16_t *>(b), kb,
                              kb + 4 * kMergeMax, pb, pb + 4 * kMergeMax))
       return b;
   }
@@ -497,6 +496,147 @@ __device__ __forceinline__ PosT *block_sort_perm(const uint64_t *keys, PosT *a, 
     PosT *t = a; a = b; b = t;
   }
   return a;
+}
+
+// ------------------------------------------------------------------------
+// 4 kMergeMax < n <= kSortCap, continuous hp: the same stable LSD sort on a
+// 32-bit window of the keys (tpe_fit_window.hpp: the window merge_sort_packed
+// takes), at most 4 passes instead of one per varying byte of the 64-bit key.
+// The window keys replace the full keys in the key region (two arrays of
+// kSortCap words: the passes alternate between them, as the positions do
+// between a and b), so a pass carries (window key, position) pairs and reads
+// its input in order, where radix_pass gathers keys[a[r]].  The full keys stay
+// available as sort_key(ob[position]).
+// ------------------------------------------------------------------------
+constexpr int kWinRows = (kSortCap + kFitThreads - 1) / kFitThreads;  // 64-rows per wave, words per thread
+static_assert(2 * 4 * kSortCap <= kOffPosA - kOffKeys, "two window key arrays in the key region");
+
+// one pass: (sk, sp) -> (dk, dp), stable on digit (key >> shift) & 255.  A wave
+// keeps its pairs, and each lane's rank among the equal digits of its row, in
+// registers between the count and the scatter.  (Inline in window_sort_perm's
+// loop, its one call: as a function of its own it makes window_sort_perm a
+// caller, whose saved return address costs k_fit a 16-byte stack frame.)
+__device__ __forceinline__ void radix_pass_win(const uint32_t *sk, const uint16_t *sp, uint32_t *dk,
+                                        uint16_t *dp, int n, int shift, uint32_t *cnt,
+                                        uint32_t *run) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int per = ((n + kFitWaves * 64 - 1) / (kFitWaves * 64)) * 64;  // slots per wave
+  const int r0 = w * per, r1 = min(n, r0 + per);
+  const uint64_t lt = lanemask_lt();
+  uint32_t *mycnt = cnt + w * kDigits;  // wave-private row while counting
+  for (int d = lane; d < kDigits; d += 64) mycnt[d] = 0;
+  uint32_t k[kWinRows];
+  // position | rank among the row's equal digits << 16 | their number << 22 | valid << 29
+  uint32_t pk[kWinRows];
+#pragma unroll
+  for (int q = 0; q < kWinRows; ++q) {
+    k[q] = 0u;
+    pk[q] = 0u;
+    if (q * 64 >= per) continue;  // (block-uniform)
+    const int r = r0 + q * 64 + lane;
+    const bool v = r < r1;
+    k[q] = v ? sk[r] : 0u;
+    const uint32_t d = (k[q] >> shift) & 255u;
+    const uint64_t mt = match8(d, v);
+    const uint32_t rank = __popcll(mt & lt), c = __popcll(mt);  // (c <= 64)
+    if (v && rank == 0) mycnt[d] += c;
+    pk[q] = v ? ((uint32_t)sp[r] | rank << 16 | c << 22 | 1u << 29) : 0u;
+  }
+  __syncthreads();
+  // this wave's base for every digit: exclusive prefix over (digit, wave).
+  // Lane l owns digits 4l..4l+3: one conflict-free 16-byte read per wave row.
+  uint32_t tot[4] = {0u, 0u, 0u, 0u}, mine[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 2
+  for (int i = 0; i < kFitWaves; ++i) {
+    const uint4 c = *reinterpret_cast<const uint4 *>(cnt + i * kDigits + 4 * lane);
+    const uint32_t below = (i < w) ? 1u : 0u;
+    tot[0] += c.x; tot[1] += c.y; tot[2] += c.z; tot[3] += c.w;
+    mine[0] += below * c.x; mine[1] += below * c.y; mine[2] += below * c.z; mine[3] += below * c.w;
+  }
+  const uint32_t ls = tot[0] + tot[1] + tot[2] + tot[3];
+  uint32_t acc = wave_excl_scan_u32(ls);
+  uint32_t *myrun = run + w * kDigits;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    myrun[4 * lane + q] = acc + mine[q];
+    acc += tot[q];
+  }
+  // stable scatter (wave-private running bases, LDS ops in program order)
+#pragma unroll
+  for (int q = 0; q < kWinRows; ++q) {
+    if (q * 64 >= per) continue;
+    const bool v = (pk[q] >> 29) & 1u;
+    const uint32_t d = (k[q] >> shift) & 255u;
+    const uint32_t rank = (pk[q] >> 16) & 63u, c = (pk[q] >> 22) & 127u;
+    const uint32_t bs = v ? myrun[d] : 0u;
+    if (v) {
+      dk[bs + rank] = k[q];
+      dp[bs + rank] = (uint16_t)pk[q];
+    }
+    if (v && rank == 0) myrun[d] = bs + c;
+  }
+  __syncthreads();
+}
+
+// The sorted permutation of the n observations ob[] whose keys stand in the
+// key region, or null (block-uniform) when the window cannot prove its result:
+// the full keys are then back in place for the sort over all their bytes.
+// A lossy window's result -- short runs of equal window keys ranked by their
+// full keys first -- is checked pair by pair (fit_window_pair_sorted); a
+// window that holds every varying bit needs neither.
+__device__ NOINLINE const uint16_t *window_sort_perm(unsigned char *lds, const double *ob, int n,
+                                                     uint64_t vary) {
+  const FitWindow W = fit_window(vary);
+  uint64_t *lk = reinterpret_cast<uint64_t *>(lds + kOffKeys);
+  uint32_t *k0 = reinterpret_cast<uint32_t *>(lds + kOffKeys), *k1 = k0 + kSortCap;
+  uint16_t *p0 = reinterpret_cast<uint16_t *>(lds + kOffPosA);
+  uint16_t *p1 = reinterpret_cast<uint16_t *>(lds + kOffPosB);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(lds + kOffCnt);
+  uint32_t *run = reinterpret_cast<uint32_t *>(lds + kOffRun);
+  {
+    uint32_t wk[kWinRows];  // a word lies inside its own or an earlier element's key: read all first
+#pragma unroll
+    for (int q = 0; q < kWinRows; ++q) {
+      const int i = q * kFitThreads + threadIdx.x;
+      wk[q] = i < n ? fit_window_key(lk[i], W.shift) : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kWinRows; ++q) {
+      const int i = q * kFitThreads + threadIdx.x;
+      if (i < n) { k0[i] = wk[q]; p0[i] = (uint16_t)i; }
+    }
+    __syncthreads();
+  }
+  STAMP(38);
+  for (int b = 0; b < 4; ++b) {
+    if (!((fit_window_bytes(W.vary) >> b) & 1)) continue;
+    radix_pass_win(k0, p0, k1, p1, n, 8 * b, cnt, run);
+    STAMP(39);
+    uint32_t *tk = k0; k0 = k1; k1 = tk;
+    uint16_t *tp = p0; p0 = p1; p1 = tp;
+  }
+  if (!W.lossy) return p0;
+  // A run of equal window keys stands in position order: its elements are
+  // ranked by their full keys into the other position array (the window keys
+  // of a run are equal, so k0 stays right place by place).  As in
+  // merge_sort_packed, a run of more than kFitWindowRunMax is left as it is
+  // (fit_window_place).
+  const auto full = [&](uint32_t p) { return sort_key(ob[p]); };
+  for (int r = threadIdx.x; r < n; r += kFitThreads)
+    p1[fit_window_place(r, n, [&](int i) { return k0[i]; },
+                        [&](int i) { return (uint32_t)p0[i]; }, full)] = p0[r];
+  __syncthreads();
+  STAMP(42);
+  // the proof: every adjacent pair ascends in (full key, position)
+  bool bad = false;
+  for (int r = threadIdx.x; r + 1 < n; r += kFitThreads)
+    bad |= !fit_window_pair_sorted(k0[r], p1[r], k0[r + 1], p1[r + 1], full);
+  STAMP(43);
+  if (!__syncthreads_or(bad)) return p1;
+  for (int i = threadIdx.x; i < n; i += kFitThreads) lk[i] = sort_key(ob[i]);
+  __syncthreads();
+  return nullptr;
 }
 
 // ------------------------------------------------------------------------
@@ -893,14 +1033,24 @@ __device__ __forceinline__ void prep_slot(const tpe_hp *Hg, int64_t slot, int K,
 // (a4) adaptive_parzen_normal on the m observations ob[] (tid order) after
 // the sort; nlt = #{obs < prior_mu} = searchsorted(sorted, prior_mu, 'left')
 // ------------------------------------------------------------------------
-template <bool MIXLDS, typename PosT, int QN = 4>  // QN: observations per thread (m <= QN * 1024)
+// MULDS (the LDS-sorted sides past kMixLds, QN = kWinRows): the sorted means
+// alone stay in LDS, over the sort's dead key region (the other three arrays
+// do not fit beside them), and go to the plan's array in the same pass: the
+// neighbour sigma and clip, the truncation terms and the tables read them
+// there, and sigma and the weights are written in order without a read of a
+// global array behind a store to it.  (Recomputing sigma and the raw weight
+// in the normalising loop, which would spare its two global loads, was tried:
+// it costs k_fit 16 B of scratch.)
+template <bool MIXLDS, typename PosT, int QN = 4, bool MULDS = false>  // QN: observations per thread (m <= QN * 1024)
 __device__ __forceinline__ void fit_continuous(const FitArgs &A, const FitCtx &C, FitShared &sm, const tpe_hp &H,
                                int64_t slot, const double *ob, const PosT *perm, int m, int nlt) {
   const double pm = H.prior_mu, ps = H.prior_sigma;
   const int K = m + 1;
   double *lm = reinterpret_cast<double *>(C.lds);
   double *gw = A.mw + slot * A.kcap, *gm = A.mmu + slot * A.kcap, *gs = A.msig + slot * A.kcap;
-  double *mu = MIXLDS ? lm : gm;
+  static_assert(!(MIXLDS && MULDS), "one LDS form");
+  static_assert(!MULDS || 8 * (kSortCap + 1) <= kFitLds, "sorted means in LDS");
+  double *mu = (MIXLDS || MULDS) ? lm : gm;
   double *w = MIXLDS ? lm + kMixStride : gw;
   double *sg = MIXLDS ? lm + 2 * kMixStride : gs;
   double *tmp = MIXLDS ? lm + 3 * kMixStride : A.tmp + slot * A.kcap;
@@ -911,7 +1061,36 @@ __device__ __forceinline__ void fit_continuous(const FitArgs &A, const FitCtx &C
   const bool lfw = A.lf && A.lf < m;            // tpe.py:440
   const LfRamp lr = lf_ramp(m, A.lf);
   // place the sorted observations around the prior (tpe.py:429-432, 441-445)
-  if (MIXLDS) {
+  if constexpr (MULDS) {
+    // two halves of QN / 2 rows: the first writes means below byte 8 (QN / 2
+    // * 1024 + 1), clear of perm; only the last mean of a full side (byte
+    // 8 kSortCap) lies over perm's first words, which the rows of the first
+    // half read -- hence the barrier between the halves and none elsewhere
+    static_assert(QN % 2 == 0 && 8 * (QN / 2 * kFitThreads + 1) <= kOffPosA, "first half clear of perm");
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      double v[QN / 2];
+      int ee[QN / 2];
+#pragma unroll
+      for (int q = 0; q < QN / 2; ++q) {
+        const int r = threadIdx.x + (h * (QN / 2) + q) * kFitThreads;
+        ee[q] = r < m ? (int)perm[r] : 0;
+        v[q] = r < m ? ob[ee[q]] : 0.0;
+      }
+      if (h == 1) __syncthreads();
+#pragma unroll
+      for (int q = 0; q < QN / 2; ++q) {
+        const int r = threadIdx.x + (h * (QN / 2) + q) * kFitThreads;
+        if (r < m) {
+          const int o = r + (r >= pos ? 1 : 0);
+          mu[o] = v[q];
+          gm[o] = v[q];
+          w[o] = lfw ? lf_weight(lr, ee[q]) : 1.0;
+        }
+      }
+    }
+    if (threadIdx.x == 0) gm[pos] = pm;
+  } else if (MIXLDS) {
     double v[4], wt[4];
 #pragma unroll
     for (int q = 0; q < QN; ++q) {
@@ -946,7 +1125,7 @@ __device__ __forceinline__ void fit_continuous(const FitArgs &A, const FitCtx &C
   // neighbour sigma (tpe.py:433-439), clip (456-460), prior sigma (461)
   const double hi = ps / 1.0;
   const double lo = ps / fmin(100.0, 1.0 + (double)K);
-  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+  const auto sigma_at = [&](int k) {
     double s;
     if (m == 0) s = ps;
     else if (m == 1) s = (k == pos) ? ps : ps * .5;
@@ -954,9 +1133,9 @@ __device__ __forceinline__ void fit_continuous(const FitArgs &A, const FitCtx &C
     else if (k == K - 1) s = mu[K - 1] - mu[K - 2];
     else s = np_maximum(mu[k] - mu[k - 1], mu[k + 1] - mu[k]);
     s = np_minimum(np_maximum(s, lo), hi);
-    if (k == pos) s = ps;
-    sg[k] = s;
-  }
+    return k == pos ? ps : s;
+  };
+  for (int k = threadIdx.x; k < K; k += blockDim.x) sg[k] = sigma_at(k);
   STAMP(5);
   const double tot = block_np_sum(w, K, sm);  // tpe.py:468 (its barriers cover sg too)
   // normalise, and the truncation-mass terms of the same component
@@ -1354,14 +1533,20 @@ __device__ __forceinline__ void fit_slot(const FitArgs &A, unsigned char *dyn_ld
   }
   if (done) {
   } else if (lds_sort) {
-    const uint16_t *perm = block_sort_perm<uint16_t, SMALL>(
-        lk, reinterpret_cast<uint16_t *>(dyn_lds + kOffPosA),
-        reinterpret_cast<uint16_t *>(dyn_lds + kOffPosB), m, vary, cnt, run, sm);
+    const uint16_t *perm = nullptr;
+    if constexpr (!SMALL) {
+      // (m > 4096: n > kMergeMax, ob is the slot's global scratch)
+      if (A.window && !cat && m > 4 * kMergeMax) perm = window_sort_perm(dyn_lds, ob, m, vary);
+    }
+    if (!perm)
+      perm = block_sort_perm<uint16_t, SMALL>(
+          lk, reinterpret_cast<uint16_t *>(dyn_lds + kOffPosA),
+          reinterpret_cast<uint16_t *>(dyn_lds + kOffPosB), m, vary, cnt, run, sm);
     STAMP(3);
     if (cat) fit_categorical<uint16_t>(A, C, sm, H, slot, lk, perm, m);
     else if (SMALL) fit_continuous<true, uint16_t, 1>(A, C, sm, H, slot, ob, perm, m, nlt);
     else if (m + 1 <= kMixLds) fit_continuous<true, uint16_t>(A, C, sm, H, slot, ob, perm, m, nlt);
-    else fit_continuous<false, uint16_t>(A, C, sm, H, slot, ob, perm, m, nlt);
+    else fit_continuous<false, uint16_t, kWinRows, true>(A, C, sm, H, slot, ob, perm, m, nlt);
   } else if (!SMALL) {
     const uint32_t *perm =
         block_sort_perm<uint32_t>(C.gkeys, C.gpa, C.gpb, m, vary, cnt, run, sm);

@@ -433,7 +433,7 @@ struct FitArgs {
   int64_t ld;                // row stride of vals / active (the plan's trial capacity)
   int32_t n_below;
   int32_t lf;
-  int32_t pad0;
+  int32_t window;            // sides of 4097..10000 observations sort on a key window (Switches::fit_window)
   double prior_weight;
   const double *pprior;
   double *mw, *mmu, *msig;   // [2P][kcap] fitted mixtures

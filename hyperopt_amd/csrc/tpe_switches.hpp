@@ -41,6 +41,10 @@ struct Switches {
   // fixed form alone, the slot's state once per persistent block); 0:
   // k_score_wave_tie (the same bytes)
   bool tie_lean;
+  // k_fit sorts a continuous side of 4097..10000 observations on a 32-bit
+  // window of its keys, with a check that proves the result; 0:
+  // the radix passes over every varying byte of the 64-bit keys (the same bytes)
+  bool fit_window;
   // value-bucketed, pruned log-sum-exp slots on small draws: opt-in.  Measured
   // at config 2 (4096 candidates): the skip drops 80 % of the pairs and k_score
   // from 33 to 23 us, but the extra k_bucket launch costs more (70 -> 78 us)
@@ -146,6 +150,7 @@ inline const SwitchDef *switch_table(int *n) {
       {"TPE_TABLE_SCALAR", R::OffIfNonEmptyZero, 1, &S::table_scalar, nullptr, 0, 0},
       {"TPE_TABLE_LEAN", R::OffIfNonEmptyZero, 1, &S::table_lean, nullptr, 0, 0},
       {"TPE_TIE_LEAN", R::OffIfNonEmptyZero, 1, &S::tie_lean, nullptr, 0, 0},
+      {"TPE_FIT_WINDOW", R::OffIfNonEmptyZero, 1, &S::fit_window, nullptr, 0, 0},
       {"TPE_SMALL_SORT", R::OnIfNonZero, 0, &S::small_sort, nullptr, 0, 0},
       {"TPE_SIDE_STREAMS", R::OnIfSet, 0, &S::side_streams, nullptr, 0, 0},
       {"TPE_GRAPH", R::OnIfSet, 0, &S::graph, nullptr, 0, 0},

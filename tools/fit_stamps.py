@@ -65,7 +65,7 @@ def main(cfg, slots):
            21: 'ms.load', 22: 'ms.bitonic64', 23: 'ms.bar|L64', 24: 'ms.L64|256', 25: 'ms.L128|1024',
            26: 'ms.L256|fix', 27: 'ms.L512|or', 28: 'np.plan', 29: 'np.leaves', 30: 'np.end',
            31: 'k.zero', 32: 'k.load', 33: 'k.wred', 34: 'k.bar', 35: 'g.load', 36: 'g.scan', 37: 'g.write',
-           38: 'rs.init', 39: 'rs.pass', 40: 'cat.seg', 41: 'cat.lfw'}
+           38: 'rs.init', 39: 'rs.pass', 40: 'cat.seg', 41: 'cat.lfw', 42: 'rs.rank', 43: 'rs.check'}
     slowest = int(np.argmax(st[:2 * P, 10] - st[:2 * P, 0]))
     extra = {int(v) for v in os.environ.get('TPE_STAMPS_DETAIL', '').split(',') if v}
     for slot in sorted(set(range(min(2 * P, 4))) | {slowest} | {e for e in extra if e < 2 * P}):
