@@ -612,8 +612,10 @@ class Plan(object):
         length) finite floats is the reference point of the greedy hypervolume
         subset selection inside the Pareto front, ``n_pick`` rounds,
         ``n_samples`` Monte-Carlo samples per row from the Philox stream of
-        ``seed``; ``method`` 0 auto (exact with two objectives), 1 exact,
-        2 Monte-Carlo."""
+        ``seed``; ``method`` 0 auto (exact with two objectives, Monte-Carlo
+        with more), 1 exact (two objectives: the area), 2 Monte-Carlo, 3 exact
+        (three objectives: the slab sweep over the picks).  An exact method
+        with another number of objectives is a ValueError."""
         e = self.engine
         with e.lock:
             if ref is None:

@@ -246,7 +246,8 @@ struct tpe_plan : PlanShape {
   int32_t hv_M = 0, hv_n_pick = 0, hv_S = 0, hv_method = 0;
   uint64_t hv_seed = 0;
   double hv_ref[TPE_MAX_OBJ] = {};
-  int32_t *d_hv_i32 = nullptr;  // [2][ncap] state, cnt; then picks, counts [kHvMaxPick], R
+  int32_t *d_hv_i32 = nullptr;  // [2][ncap] state, cnt (M = 3 exact: the row list); then picks,
+                                // counts [kHvMaxPick], R, the list's length
   double *d_hv_f64 = nullptr;   // [3][ncap] vol, right, top; then keys [kHvMaxPick]
   uint64_t *d_hv_alive = nullptr;  // [hv_words_cap][ncap] alive words (Monte-Carlo)
   int64_t hv_words_cap = 0;
@@ -1617,7 +1618,7 @@ int hv_rank(tpe_engine *h, tpe_plan *p, int64_t n, int32_t M, const int32_t *by,
   if (!hp.ok) return fail(h, TPE_E_INVALID, "set_objectives: the hypervolume setting is out of range");
   const size_t cap = (size_t)p->ncap;
   if (!p->d_hv_i32) {
-    CKH(dalloc(&p->d_hv_i32, 2 * cap + 2 * (size_t)kHvMaxPick + 1));
+    CKH(dalloc(&p->d_hv_i32, 2 * cap + 2 * (size_t)kHvMaxPick + 2));
     CKH(dalloc(&p->d_hv_f64, 3 * cap + (size_t)kHvMaxPick));
   }
   if (!hp.exact) {
@@ -1641,6 +1642,7 @@ int hv_rank(tpe_engine *h, tpe_plan *p, int64_t n, int32_t M, const int32_t *by,
   a.state = p->d_hv_i32; a.cnt = p->d_hv_i32 + cap;
   a.picks = p->d_hv_i32 + 2 * cap; a.counts = a.picks + kHvMaxPick;
   a.n_picked = a.counts + kHvMaxPick;
+  a.list = a.cnt; a.n_list = a.n_picked + 1;
   a.vol = p->d_hv_f64; a.right = p->d_hv_f64 + cap; a.top = p->d_hv_f64 + 2 * cap;
   a.keys = p->d_hv_f64 + 3 * cap;
   a.alive = p->d_hv_alive; a.u = p->d_hv_u;
@@ -1675,10 +1677,13 @@ int tpe_plan_set_hv(tpe_plan_t p, int32_t mode, const double *ref, int32_t n_obj
     return fail(h, TPE_E_INVALID, "set_hv: need 1 <= n_pick <= 256");
   if (n_samples < kHvMinSamples || n_samples > kHvMaxSamples || n_samples % kHvWord != 0)
     return fail(h, TPE_E_INVALID, "set_hv: n_samples is a multiple of 64 in [64, 4096]");
-  if (method != kHvAuto && method != kHvExact && method != kHvMc)
-    return fail(h, TPE_E_INVALID, "set_hv: method is 0 (auto), 1 (exact) or 2 (Monte-Carlo)");
+  if (method != kHvAuto && method != kHvExact && method != kHvMc && method != kHvExact3)
+    return fail(h, TPE_E_INVALID,
+                "set_hv: method is 0 (auto), 1 (exact), 2 (Monte-Carlo) or 3 (exact, n_obj = 3)");
   if (method == kHvExact && n_obj != 2)
     return fail(h, TPE_E_INVALID, "set_hv: the exact method needs n_obj = 2");
+  if (method == kHvExact3 && n_obj != 3)
+    return fail(h, TPE_E_INVALID, "set_hv: method 3 needs n_obj = 3");
   p->hv_mode = 1;
   p->hv_M = n_obj;
   p->hv_n_pick = n_pick;

@@ -11,6 +11,9 @@
 //                   y_p[0] above y_i[0]) and from the top (the smallest y_p[1]
 //                   above y_i[1]); front rows are mutually nondominated, so the
 //                   clipped box is the area gain.  A row equal to a pick is dead.
+//   exact (M = 3)   the box minus what the picks dominate, by a sweep over the
+//                   picks: slabs along objective 2, a staircase area in each
+//                   (k_hv_round_exact3 below; O(t^2) per row and round)
 //   Monte-Carlo     S samples z = y + u * w per row from one table u[S][M] of
 //                   Philox uniforms (draw4, stream kHvStream); a sample is alive
 //                   until a pick lies below it in every objective; the gain is
@@ -26,11 +29,15 @@
 //                  lane reads the same address (a broadcast); killed samples
 //                  leave cnt[row] by an integer atomic, so the counts do not
 //                  depend on the launch shape.  Exact: one lane per row.
+//   k_hv_init_exact3 / k_hv_round_exact3   the three-objective exact path: the
+//                  participating rows compacted into a list, one lane per list
+//                  entry, the picks staged sorted in LDS by every block
 //   k_hv_pick      one block: the largest (key bits, lower row) is pick t
 //   k_hv_loss<M>   the surrogate column s = dominated_by (n + 1) + sec
 // Keys are non-negative doubles compared as integers; z is formed by a rounded
 // product and a rounded sum (no fused multiply-add), so every quantity is the
-// one tests/hv_oracle.py computes in numpy.
+// one tests/hv_oracle.py (three objectives exact: tests/hv3_oracle.py)
+// computes in numpy.
 #include <math.h>
 
 #include "tpe_device.hpp"
@@ -174,6 +181,122 @@ __global__ __launch_bounds__(kHvTile) void k_hv_round_exact(
   gain[i] = (rt - y0) * (tp - y1);
 }
 
+// ---- exact gains for three objectives: a slab sweep over the picks
+// Row i's gain given the picks p_0 .. p_{t-1} is the volume of its box [y_i, r]
+// that no pick dominates.  A pick clipped into the box is c_p = max(y_p, y_i).
+// Cut the box along objective 2 at the clipped picks (Z order): inside slab j
+// only the j picks of lowest objective 2 reach, and what they leave of the
+// (objective 0, objective 1) rectangle is the area under a staircase, walked
+// in X order.  key = sum_j h_j A_j, slabs ascending, every difference and
+// product as written (tests/hv3_oracle.py states the same in numpy).
+
+// the rows that take part, compacted: the round kernel's waves are full
+// however thin the front is.  The order inside the list is that of the
+// atomics; no result depends on it (a row's key is written to vol[row]).
+__global__ __launch_bounds__(kHvTile) void k_hv_init_exact3(
+    const double *__restrict__ Y, int64_t ld, int64_t n, HvRef<3> ref,
+    const int32_t *__restrict__ dominated_by, int32_t *__restrict__ state,
+    double *__restrict__ vol, int32_t *__restrict__ list, int32_t *__restrict__ n_list,
+    int32_t *__restrict__ n_picked) {
+  const int64_t i = (int64_t)blockIdx.x * kHvTile + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *n_picked = 0;
+  bool part = false;
+  if (i < n) {
+    double y[3], w[3];
+    part = hv_row<3>(Y, ld, i, ref, dominated_by[i], y, w);
+    state[i] = part ? kHvLive : kHvOut;
+    vol[i] = part ? (w[0] * w[1]) * w[2] : 0.0;  // round 0's key
+  }
+  const uint64_t m = __ballot(part);  // (every lane of the wave arrives here)
+  if (m == 0) return;
+  const int lane = threadIdx.x & 63;
+  int32_t base = 0;
+  if (lane == __ffsll((long long)m) - 1) base = atomicAdd(n_list, __popcll(m));
+  base = __shfl(base, __ffsll((long long)m) - 1);
+  if (part) list[base + __popcll(m & ((1ull << lane) - 1))] = (int32_t)i;  // (< n entries in all)
+}
+
+struct Hv3Pick {  // a pick in X order
+  double y0, y1;
+  int32_t zrank, pad;
+};
+static_assert(sizeof(Hv3Pick) == 24, "the LDS layout of the plan header");
+
+// round t >= 1: every live row of the list against the picks p_0 .. p_{t-1}.
+// Each block sorts the picks for itself: thread k places pick k by counting the
+// picks that come before it in X (objective 0, then pick round) and in Z
+// (objective 2, then pick round), so nothing sorted lives between rounds.
+// The walk reads LDS at addresses that do not depend on the lane.
+__global__ __launch_bounds__(kHvTile) void k_hv_round_exact3(
+    const double *__restrict__ Y, int64_t ld, HvRef<3> ref, int32_t t,
+    const int32_t *__restrict__ picks, const int32_t *__restrict__ state,
+    const int32_t *__restrict__ list, const int32_t *__restrict__ n_list,
+    double *__restrict__ gain) {
+  __shared__ Hv3Pick sx[kHvMaxPick];  // X order
+  __shared__ double sz[kHvMaxPick];   // objective 2, Z order
+  __shared__ double raw0[kHvMaxPick], raw2[kHvMaxPick];  // by pick round
+  static_assert(sizeof(sx) + sizeof(sz) + sizeof(raw0) + sizeof(raw2) == kHv3LdsBytes,
+                "the LDS the plan header states");
+  if (picks[t - 1] < 0) return;  // the selection has ended (1 <= t < kHvMaxPick)
+  const int32_t L = *n_list;
+  if ((int64_t)blockIdx.x * kHvTile >= L) return;  // (the grid covers n rows, the list L <= n)
+  const int k = threadIdx.x;
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+  if (k < t) {
+    const int32_t p = picks[k];  // (>= 0: picks[t - 1] is)
+    p0 = Y[p];
+    p1 = Y[ld + p];
+    p2 = Y[2 * ld + p];
+    raw0[k] = p0;
+    raw2[k] = p2;
+  }
+  __syncthreads();
+  if (k < t) {
+    int xr = 0, zr = 0;
+    for (int q = 0; q < t; ++q) {
+      const double q0 = raw0[q], q2 = raw2[q];
+      xr += (q0 < p0 || (q0 == p0 && q < k)) ? 1 : 0;
+      zr += (q2 < p2 || (q2 == p2 && q < k)) ? 1 : 0;
+    }
+    sx[xr].y0 = p0;
+    sx[xr].y1 = p1;
+    sx[xr].zrank = zr;
+    sz[zr] = p2;
+  }
+  __syncthreads();
+  const int64_t at = (int64_t)blockIdx.x * kHvTile + k;
+  if (at >= L) return;
+  const int32_t i = list[at];
+  if (state[i] != kHvLive) return;
+  const double y0 = Y[i], y1 = Y[ld + i], y2 = Y[2 * ld + i];
+  const double h1 = ref.r[1] - y1;
+  double key = 0.0, lo = y2;
+  for (int j = 0; j <= t; ++j) {
+    double hi = ref.r[2];
+    if (j < t) {
+      const double z = sz[j];
+      hi = z > y2 ? z : y2;
+    }
+    const double h = hi - lo;
+    lo = hi;
+    if (__ballot(h > 0.0) == 0) continue;  // no lane of the wave has a slab here
+    double cur_x = y0, cur_h = h1, A = 0.0;
+    for (int a = 0; a < t; ++a) {
+      if (__builtin_amdgcn_readfirstlane(sx[a].zrank) >= j) continue;  // (the same in every lane)
+      const double q0 = sx[a].y0, q1 = sx[a].y1;
+      const double c0 = q0 > y0 ? q0 : y0;
+      const double c1 = q1 > y1 ? q1 : y1;
+      A = A + (c0 - cur_x) * cur_h;
+      cur_x = c0;
+      const double d = c1 - y1;
+      cur_h = d < cur_h ? d : cur_h;
+    }
+    A = A + (ref.r[0] - cur_x) * cur_h;
+    if (h > 0.0) key = key + h * A;
+  }
+  gain[i] = key;
+}
+
 // a larger key wins, then the lower row
 __device__ __forceinline__ bool hv_less(uint64_t ka, int32_t ra, uint64_t kb, int32_t rb) {
   return ka != kb ? ka < kb : ra > rb;
@@ -261,13 +384,25 @@ hipError_t select_m(const HvArgs &a, hipStream_t st) {
   const unsigned tiles = (unsigned)((a.n + kHvTile - 1) / kHvTile);
   const unsigned words = a.exact ? 1u : (unsigned)(a.S / kHvWord);
   if (!a.exact && a.make_u) k_hv_uniforms<<<words, kHvWord, 0, st>>>(a.seed, M, a.u);
-  k_hv_init<M><<<dim3(tiles, words), kHvTile, 0, st>>>(a.Y, a.ld, a.n, ref, a.dominated_by, a.S,
-                                                       a.exact, a.state, a.cnt, a.vol, a.right,
-                                                       a.top, a.alive, a.n_picked);
+  if constexpr (M == 3) {
+    if (a.exact) {  // (the list's counter is cleared on the stream, ahead of the atomics)
+      hipError_t e = hipMemsetAsync(a.n_list, 0, sizeof(int32_t), st);
+      if (e != hipSuccess) return e;
+      k_hv_init_exact3<<<tiles, kHvTile, 0, st>>>(a.Y, a.ld, a.n, ref, a.dominated_by, a.state,
+                                                  a.vol, a.list, a.n_list, a.n_picked);
+    }
+  }
+  if (!(M == 3 && a.exact))
+    k_hv_init<M><<<dim3(tiles, words), kHvTile, 0, st>>>(a.Y, a.ld, a.n, ref, a.dominated_by, a.S,
+                                                         a.exact, a.state, a.cnt, a.vol, a.right,
+                                                         a.top, a.alive, a.n_picked);
   hipError_t e = hipGetLastError();
   for (int t = 0; t < a.n_pick && e == hipSuccess; ++t) {
     if (t > 0) {
       if (a.exact) {
+        if constexpr (M == 3)
+          k_hv_round_exact3<<<tiles, kHvTile, 0, st>>>(a.Y, a.ld, ref, t, a.picks, a.state, a.list,
+                                                       a.n_list, a.vol);
         if constexpr (M == 2)
           k_hv_round_exact<<<tiles, kHvTile, 0, st>>>(a.Y, a.ld, a.n, a.picks + (t - 1), a.state,
                                                       a.vol, a.right, a.top);
@@ -289,7 +424,8 @@ hipError_t select_m(const HvArgs &a, hipStream_t st) {
 }  // namespace
 
 hipError_t launch_hv_select(const HvArgs &a, hipStream_t st) {
-  const HvPlan hp = hv_plan(a.n, a.M, a.n_pick, a.S, a.exact ? kHvExact : kHvMc);
+  const HvPlan hp = hv_plan(a.n, a.M, a.n_pick, a.S,
+                            !a.exact ? kHvMc : a.M == 3 ? kHvExact3 : kHvExact);
   if (!hp.ok || a.n > a.ld) return hipErrorInvalidValue;
   switch (a.M) {
     case 2: return select_m<2>(a, st);

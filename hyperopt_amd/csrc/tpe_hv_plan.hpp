@@ -3,7 +3,8 @@
 // (n, M, n_pick, S, method) -- history rows, objectives, greedy rounds,
 // Monte-Carlo samples per row, estimator -- to the grids of k_hv_init /
 // k_hv_round (tpe_hv.hip), the LDS a round block stages its uniforms in and
-// the sizes of the per-row state.  What is selected is a
+// the sizes of the per-row state.  The exact three-objective
+// path (k_hv_round_exact3) stages the picks instead: kHv3LdsBytes per block.  What is selected is a
 // function of (Y, r, n_pick, S, seed, method) alone; the plan only decides how
 // the rows and the sample words are spread over blocks.
 #pragma once
@@ -27,6 +28,10 @@ constexpr size_t kHvLdsLimit = 4 * 1024;     // the staged uniforms, [M][64] dou
 constexpr int kHvAuto = 0;   // exact when M == 2, Monte-Carlo when M >= 3
 constexpr int kHvExact = 1;  // M == 2 only
 constexpr int kHvMc = 2;     // any M >= 2
+constexpr int kHvExact3 = 3; // M == 3 only: the slab sweep over the picks
+// k_hv_round_exact3 stages per pick (y0, y1, zrank) in X order [24 bytes], y2
+// in Z order and the unsorted (y0, y2) it ranks them by
+constexpr size_t kHv3LdsBytes = (size_t)kHvMaxPick * (24 + 8 + 16);
 
 struct HvPlan {
   bool ok = false;       // the arguments are in range
@@ -34,7 +39,8 @@ struct HvPlan {
   int32_t M = 0;
   int32_t n_pick = 0;
   int32_t S = 0;
-  bool exact = false;    // the M == 2 area gain; otherwise the Monte-Carlo count
+  bool exact = false;    // the M == 2 area gain or the M == 3 slab sweep; otherwise the
+                         // Monte-Carlo count
   int64_t tiles = 0;     // ceil(n / tile): grid.x of k_hv_init / k_hv_round / k_hv_loss
   int64_t words = 0;     // grid.y: S / 64 sample words (1 on the exact path)
   size_t lds_bytes = 0;  // uniforms a round block stages (0 on the exact path)
@@ -59,13 +65,15 @@ inline HvPlan hv_plan(int64_t n, int32_t M, int32_t n_pick, int32_t S, int32_t m
   if (n < 1 || n > kParetoMaxN || M < 2 || M > kParetoMaxObj) return p;
   if (n_pick < 1 || n_pick > kHvMaxPick) return p;
   if (S < kHvMinSamples || S > kHvMaxSamples || S % kHvWord != 0) return p;
-  if (method != kHvAuto && method != kHvExact && method != kHvMc) return p;
+  if (method != kHvAuto && method != kHvExact && method != kHvMc && method != kHvExact3)
+    return p;
   if (method == kHvExact && M != 2) return p;
+  if (method == kHvExact3 && M != 3) return p;
   p.n = n;
   p.M = M;
   p.n_pick = n_pick;
   p.S = S;
-  p.exact = method == kHvExact || (method == kHvAuto && M == 2);
+  p.exact = method == kHvExact || method == kHvExact3 || (method == kHvAuto && M == 2);
   p.tiles = (n + kHvTile - 1) / kHvTile;
   p.words = p.exact ? 1 : S / kHvWord;
   p.lds_bytes = p.exact ? 0 : (size_t)M * kHvWord * sizeof(double);

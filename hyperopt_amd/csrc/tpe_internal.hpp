@@ -1039,12 +1039,14 @@ struct HvArgs {
   int32_t M;
   double ref[8];                // the reference point
   int32_t n_pick, S;
-  bool exact;                   // the M = 2 area gain, otherwise Monte-Carlo
+  bool exact;                   // the M = 2 area gain or the M = 3 slab sweep, otherwise
+                                // Monte-Carlo
   uint64_t seed;
   bool make_u;                  // write the sample table first (Monte-Carlo)
   const int32_t *dominated_by, *dominates;
   int32_t *state;               // [ld] the round a row was picked in, < 0 otherwise
   int32_t *cnt;                 // [ld] alive samples (Monte-Carlo)
+  int32_t *list, *n_list;       // [ld], [1] the participating rows (M = 3 exact)
   double *vol;                  // [ld] the box volume; exact: the current gain
   double *right, *top;          // [ld] the clipped box (exact)
   uint64_t *alive;              // [S / 64][ld] (Monte-Carlo)

@@ -116,6 +116,22 @@ def check_hypervolume(hypervolume, objectives):
     return tuple(float(v) for v in ref)
 
 
+def check_hv_method(hv_method, hypervolume, objectives):
+    """``hv_method=`` checked against the checked ``hypervolume`` and
+    ``objectives``: 'auto' (the default: ``HV_METHOD``), 'mc' (Monte-Carlo
+    gains) or 'exact' (exact gains: the area with two objectives, the slab
+    sweep with three; no other M has an exact path).  Anything but 'auto'
+    needs ``hypervolume``."""
+    if not isinstance(hv_method, str) or hv_method not in ('auto', 'mc', 'exact'):
+        raise ValueError("hv_method must be 'auto', 'mc' or 'exact', got %r" % (hv_method,))
+    if hv_method != 'auto' and hypervolume is False:
+        raise ValueError('hv_method=%r needs hypervolume' % hv_method)
+    if hv_method == 'exact' and objectives not in (2, 3):
+        raise ValueError("hv_method='exact' needs objectives=2 or objectives=3, got %r"
+                         % (objectives,))
+    return hv_method
+
+
 def default_reference(Y):
     """The default reference point of ``Y[M, n]``: per objective, over the
     finite values of complete rows (no NaN, no +inf), ``hi + 0.1 (hi - lo)``, or
@@ -138,6 +154,8 @@ def default_reference(Y):
 
 # tpe_plan_set_hv's defaults (include/tpe_engine.h)
 HV_N_PICK, HV_N_SAMPLES, HV_SEED, HV_METHOD = 32, 1024, 0, 0
+# its method codes for hv_method 'mc' and 'exact' (by the number of objectives)
+HV_METHOD_MC, HV_METHOD_EXACT = 2, {2: 1, 3: 3}
 
 
 def _objectives_of(doc, M, tid, key='objectives'):
@@ -173,6 +191,7 @@ class TrialHistory(object):
         self.M = None           # objectives of the last sync (None: the scalar loss)
         self.Y = None           # [M][cap] objective store beside losses (NaN: pending)
         self.hv = False         # hypervolume= of the last sync: False, True or the reference point
+        self.hv_method = 'auto'  # hv_method= of the last sync
         self.C = None           # constraints of the last sync (None: unconstrained)
         self.G = None           # [C][cap] constraint store (NaN: not an ok trial)
         self.cmodel = 'rank'    # constraint_model of the last sync
@@ -272,13 +291,14 @@ class TrialHistory(object):
 
     # -- sync ----------------------------------------------------------------
     def sync(self, trials, objectives=None, hypervolume=False, constraints=None,
-             constraint_model='rank'):
+             constraint_model='rank', hv_method='auto'):
         """Bring the columns up to date with ``trials.trials``.  ``objectives``
         = M: also the objective store ``Y[M][cap]``, from every ok trial's
         ``result['objectives']`` (ValueError naming the tid where an ok trial
         has none, or not M of them); ``push`` then ranks the device history by
         Pareto dominance instead of by the loss.  ``hypervolume``: the front
-        is ordered by hypervolume subset selection (``check_hypervolume``).
+        is ordered by hypervolume subset selection (``check_hypervolume``),
+        its gains estimated as ``hv_method`` says (``check_hv_method``).
         ``constraints`` = C: also the constraint store ``G[C][cap]``, from every
         ok trial's ``result['constraints']`` under the same rules (NaN for any
         other trial); ``push`` then ranks by constrained dominance, over the
@@ -289,6 +309,7 @@ class TrialHistory(object):
         constraints = check_constraints(constraints)
         self.cmodel = check_constraint_model(constraint_model, constraints)
         self.hv = check_hypervolume(hypervolume, objectives)
+        self.hv_method = check_hv_method(hv_method, self.hv, objectives)
         view = trials.trials
         store = getattr(trials, '_store', None)
         journal = store.journal if store is not None else None
@@ -499,13 +520,17 @@ class TrialHistory(object):
             mode = self.M if self.hv is False else (self.M, self.hv)
             if C is not None:
                 mode = ('loss' if self.M is None else self.M, self.hv, C)
+            method = HV_METHOD
+            if self.hv_method != 'auto':
+                method = HV_METHOD_MC if self.hv_method == 'mc' else HV_METHOD_EXACT[self.M]
+                mode = (mode, self.hv_method)
             same = self._dev_mode == mode
             o0 = min(self._obj_dirty, self.n) if same else 0
             # the setting goes before the ranking that reads it; a plan that
             # never saw one is off (Plan._hv_on), and is not told so again
             ref = self.reference()
             if ref is not None:
-                plan.set_hv(ref, self.M, HV_N_PICK, HV_N_SAMPLES, HV_SEED, HV_METHOD)
+                plan.set_hv(ref, self.M, HV_N_PICK, HV_N_SAMPLES, HV_SEED, method)
             elif getattr(plan, '_hv_on', False):
                 plan.set_hv(None)
             # the constraints go before the ranking that reads them too

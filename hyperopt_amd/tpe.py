@@ -38,7 +38,7 @@ import numpy as np
 from . import _engine as E
 from . import rand, rstream
 from .history import (TrialHistory, check_objectives, check_hypervolume, check_constraints,
-                      check_constraint_model, HV_N_SAMPLES)
+                      check_constraint_model, check_hv_method, HV_N_SAMPLES)
 
 logger = logging.getLogger(__name__)
 
@@ -151,7 +151,7 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             rng_stream='philox', startup_stream='numpy', engine=None, objectives=None,
-            hypervolume=False, constraints=None, constraint_model='rank'):
+            hypervolume=False, constraints=None, constraint_model='rank', hv_method='auto'):
     """hyperopt/tpe.py:804-897 on the GPU, one document per id in
     ``new_ids``.  ``linear_forgetting`` is accepted and, as in the reference
     (tpe.py:809), not used: LF is fixed at 25.  The first ``n_startup_jobs``
@@ -181,6 +181,16 @@ def suggest(new_ids, domain, trials, seed,
     ``hypervolume`` without ``objectives``, is a ValueError.  With M = 1 the
     setting is ignored.
 
+    ``hv_method`` (with ``hypervolume``): how a front trial's gain is measured.
+    'auto' (default): the exact area with two objectives, a Monte-Carlo
+    estimate from 1024 samples with more; 'mc': the estimate for any M;
+    'exact': exact gains -- the area with two objectives, with three a sweep
+    over the picks (slabs along the third objective, a staircase area in
+    each), which keeps the late picks meaningful when a trial's gain is a
+    small share of its box.  'exact' with another M, an unknown string, or
+    anything but 'auto' without ``hypervolume``, is a ValueError.  Calls with
+    different methods may alternate on one domain.
+
     ``constraints=C`` (constrained TPE): every ok trial also
     reports ``result['constraints']``, a sequence of C numbers known only after
     it ran, feasible when every one is <= 0 (an ok trial without it, or with
@@ -196,6 +206,7 @@ def suggest(new_ids, domain, trials, seed,
     this per-hp argmax cannot use -- ``suggest_joint`` takes 'ctpe'."""
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    hv_method = check_hv_method(hv_method, hypervolume, objectives)
     constraints = check_constraints(constraints)
     if check_constraint_model(constraint_model, constraints) == 'ctpe':
         raise ValueError("tpe.suggest picks every hp by its own argmax and cannot rank a joint "
@@ -208,7 +219,8 @@ def suggest(new_ids, domain, trials, seed,
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints,
+                                               hv_method=hv_method)
         startup = hist.n < n_startup_jobs
     if startup:
         # the reference's RandomState prior stream (numpy), or device prior
@@ -216,9 +228,10 @@ def suggest(new_ids, domain, trials, seed,
         return rand.suggest(new_ids, domain, trials, seed, rng_stream=startup_stream)
     with st.lock:
         engine = engine or E.default_engine()
-        if hist.M != objectives or hist.hv != hypervolume or hist.C != constraints:
+        if hist.M != objectives or hist.hv != hypervolume or hist.hv_method != hv_method or \
+                hist.C != constraints:
             # (another thread's call in between)
-            hist.sync(trials, objectives, hypervolume, constraints)
+            hist.sync(trials, objectives, hypervolume, constraints, hv_method=hv_method)
         plan = st.plan_for(domain, hist.n, engine)
         hist.push(plan)
         seeds = batch_seeds(seed, len(new_ids))
@@ -462,7 +475,8 @@ def _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate
 
 def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
                   gamma=_default_gamma, engine=None, return_terms=False, multivariate=False,
-                  objectives=None, hypervolume=False, constraints=None, constraint_model='rank'):
+                  objectives=None, hypervolume=False, constraints=None, constraint_model='rank',
+                  hv_method='auto'):
     """What the fitted TPE model thinks of configurations the caller holds.
 
     The history of ``trials`` is synced, pushed and fitted as ``suggest``
@@ -495,7 +509,8 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
 
     ``objectives=M``: the model is fitted on the Pareto ranking of the
     trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
-    hypervolume order inside the front (``suggest``).  ``constraints=C``: the
+    hypervolume order inside the front, its gains by ``hv_method``
+    (``suggest``).  ``constraints=C``: the
     history is ranked by constrained dominance over the trials'
     ``result['constraints']`` (``suggest``).
 
@@ -513,6 +528,7 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    hv_method = check_hv_method(hv_method, hypervolume, objectives)
     constraints = check_constraints(constraints)
     cm = _cmodel(constraint_model, constraints, multivariate)
     cs = domain.space
@@ -520,7 +536,8 @@ def score_configs(configs, domain, trials, prior_weight=_default_prior_weight,
     vals, present = config_columns(cs, configs)
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm,
+                                               hv_method=hv_method)
         if hist.n == 0:
             raise ValueError('score_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate, cm)
@@ -754,7 +771,7 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
                       n_startup_jobs=_default_n_startup_jobs,
                       gamma=_default_gamma, skip_seen=True, engine=None, multivariate=False,
                       objectives=None, hypervolume=False, constraints=None,
-                      constraint_model='rank'):
+                      constraint_model='rank', hv_method='auto'):
     """``algo=`` for a constrained or discrete search: the next trials are the
     ``len(new_ids)`` configurations of ``pool`` the fitted model scores
     highest (``score_configs``' EI), distinct, ties to the lower pool index,
@@ -769,13 +786,15 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     (True or 'groups'): the pool is ranked by ``score_configs`` with that
     argument.  ``objectives=M``: the model is fitted on the Pareto ranking of
     the trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with
-    the hypervolume order inside the front (``suggest``).  ``constraints=C``: the
+    the hypervolume order inside the front, its gains by ``hv_method``
+    (``suggest``).  ``constraints=C``: the
     history is ranked by constrained dominance over the trials'
     ``result['constraints']`` (``suggest``); ``constraint_model='ctpe'``: the pool
     is ranked by c-TPE's acquisition instead (``score_configs``)."""
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    hv_method = check_hv_method(hv_method, hypervolume, objectives)
     constraints = check_constraints(constraints)
     cm = _cmodel(constraint_model, constraints, multivariate)
     new_ids = list(new_ids)
@@ -788,7 +807,8 @@ def suggest_from_pool(new_ids, domain, trials, seed, pool=None,
     k = len(new_ids)
     with st.lock:
         pl = _pool_for(st, cs, pool)
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm,
+                                               hv_method=hv_method)
         if hist.n < n_startup_jobs:
             if pl.m < k:
                 raise ValueError('the pool holds %d configurations, %d asked for' % (pl.m, k))
@@ -819,7 +839,7 @@ STARTUP_ROUNDS = 100        # suggest_joint's prior rounds under a predicate
 def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
                    gamma=_default_gamma, engine=None, begin=0, as_dicts=False,
                    multivariate=False, objectives=None, hypervolume=False, constraints=None,
-                   constraint_model='rank'):
+                   constraint_model='rank', hv_method='auto'):
     """``n`` whole configurations drawn from the fitted model's *below*
     mixtures, each with its joint EI (``score_configs``' total of it).
 
@@ -843,7 +863,8 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     ``score_configs(..., multivariate='groups')``'s
     (tpe_plan_group_sample_points).  ``objectives=M``: the model is fitted on
     the Pareto ranking of the trials' ``result['objectives']`` (``suggest``);
-    ``hypervolume``: with the hypervolume order inside the front (``suggest``).
+    ``hypervolume``: with the hypervolume order inside the front, its gains by
+    ``hv_method`` (``suggest``).
     ``constraints=C``: the history is ranked by constrained dominance over the
     trials' ``result['constraints']`` (``suggest``).  ``constraint_model='ctpe'``
     (``score_configs``): configuration ``begin + j`` is drawn from the below
@@ -855,12 +876,14 @@ def sample_configs(n, domain, trials, seed, prior_weight=_default_prior_weight,
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    hv_method = check_hv_method(hv_method, hypervolume, objectives)
     constraints = check_constraints(constraints)
     cm = _cmodel(constraint_model, constraints, multivariate)
     cs = domain.space
     st = _state(domain)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm,
+                                               hv_method=hv_method)
         if hist.n == 0:
             raise ValueError('sample_configs needs a history: trials holds no usable trial')
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate, cm)
@@ -1002,7 +1025,8 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
                   skip_seen=True, prior_weight=_default_prior_weight,
                   n_startup_jobs=_default_n_startup_jobs, gamma=_default_gamma,
                   startup_stream='numpy', engine=None, multivariate=False, batch='topk',
-                  objectives=None, hypervolume=False, constraints=None, constraint_model='rank'):
+                  objectives=None, hypervolume=False, constraints=None, constraint_model='rank',
+                  hv_method='auto'):
     """``algo=`` that ranks whole configurations: one fit, one draw of
     ``n_configs`` configurations from the fitted model (``sample_configs``)
     and the ``len(new_ids)`` distinct ones of highest joint EI -- a branch is
@@ -1049,7 +1073,8 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
 
     ``objectives=M``: the model is fitted on the Pareto ranking of the
     trials' ``result['objectives']`` (``suggest``); ``hypervolume``: with the
-    hypervolume order inside the front (``suggest``).  ``constraints=C``: the
+    hypervolume order inside the front, its gains by ``hv_method``
+    (``suggest``).  ``constraints=C``: the
     history is ranked by constrained dominance over the trials'
     ``result['constraints']`` (``suggest``).  ``constraint_model='ctpe'``: the
     draw and its ranking are ``sample_configs``' with that argument (c-TPE,
@@ -1057,6 +1082,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     multivariate = _mode(multivariate)
     objectives = check_objectives(objectives)
     hypervolume = check_hypervolume(hypervolume, objectives)
+    hv_method = check_hv_method(hv_method, hypervolume, objectives)
     constraints = check_constraints(constraints)
     if batch not in ('topk', 'pending'):
         raise ValueError("batch must be 'topk' or 'pending', got %r" % (batch,))
@@ -1073,7 +1099,8 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
     k = len(new_ids)
     n = int(n_configs)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints, cm,
+                                               hv_method=hv_method)
         startup = hist.n < n_startup_jobs
     if startup:
         if feasible is None:
@@ -1083,10 +1110,10 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
         raise ValueError('n_configs = %d configurations drawn, %d asked for' % (n, k))
     P = len(cs.labels)
     with st.lock:
-        if hist.M != objectives or hist.hv != hypervolume or hist.C != constraints or \
-                hist.cmodel != cm:
+        if hist.M != objectives or hist.hv != hypervolume or hist.hv_method != hv_method or \
+                hist.C != constraints or hist.cmodel != cm:
             # (another thread's call in between)
-            hist.sync(trials, objectives, hypervolume, constraints, cm)
+            hist.sync(trials, objectives, hypervolume, constraints, cm, hv_method=hv_method)
         plan = _fit_for(st, domain, trials, hist, engine, prior_weight, gamma, multivariate, cm)
         d_vals, d_total, d_mask, d_idx, d_cols = _joint_buffers(st, plan.engine, P, n)
         draw = (plan.ctpe_sample_points_device if cm == 'ctpe' else
@@ -1131,7 +1158,7 @@ def suggest_joint(new_ids, domain, trials, seed, n_configs=_default_n_configs, f
 # multi-objective TPE: the Pareto ranking the split reads
 # --------------------------------------------------------------------------
 def _pareto(domain, trials, objectives, engine, hypervolume=False, want_hv=False,
-            constraints=None, want_v=False):
+            constraints=None, want_v=False, hv_method='auto'):
     """(docs, tids, dominated_by, dominates, surrogate) of the synced history,
     ranked on the device; ``want_hv``: and ``Plan.hv_get``'s tuple; ``want_v``:
     and the violations (``Plan.constraint_get``)."""
@@ -1140,10 +1167,12 @@ def _pareto(domain, trials, objectives, engine, hypervolume=False, want_hv=False
     if objectives is None and constraints is None:
         raise ValueError('the Pareto ranking needs objectives=M or constraints=C')
     hypervolume = check_hypervolume(hypervolume, objectives)
+    hv_method = check_hv_method(hv_method, hypervolume, objectives)
     st = _state(domain)
     none = (np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0, dtype=np.int32), 0)
     with st.lock:
-        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints)
+        hist = st.history(domain, trials).sync(trials, objectives, hypervolume, constraints,
+                                               hv_method=hv_method)
         if hist.n == 0:
             out = [], [], np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
             out = out + (none,) if want_hv else out
@@ -1156,7 +1185,7 @@ def _pareto(domain, trials, objectives, engine, hypervolume=False, want_hv=False
 
 
 def pareto_ranks(domain, trials, objectives=None, engine=None, hypervolume=False,
-                 constraints=None):
+                 constraints=None, hv_method='auto'):
     """(tids, dominated_by, dominates, surrogate) of the history of
     ``trials`` under ``objectives=M``, read back from the device
     (tpe_plan_pareto_get): per trial in tid order the number of complete
@@ -1170,18 +1199,19 @@ def pareto_ranks(domain, trials, objectives=None, engine=None, hypervolume=False
     With ``constraints=C`` the counts and the surrogate are those of
     constrained dominance (``constraint_ranks``; ``objectives`` may then be
     None: the single objective is the loss)."""
-    return _pareto(domain, trials, objectives, engine, hypervolume, constraints=constraints)[1:]
+    return _pareto(domain, trials, objectives, engine, hypervolume, hv_method=hv_method,
+                   constraints=constraints)[1:]
 
 
 def pareto_front(domain, trials, objectives=None, engine=None, hypervolume=False,
-                 constraints=None):
+                 constraints=None, hv_method='auto'):
     """The trial documents on the Pareto front of ``result['objectives']``
     -- complete trials no complete trial dominates -- in tid order
     (``hypervolume`` orders the front's rows in the split and leaves the front
     as it is).  With ``constraints=C``: the feasible trials no feasible trial
     dominates; none when no trial is feasible."""
-    out = _pareto(domain, trials, objectives, engine, hypervolume, constraints=constraints,
-                  want_v=constraints is not None)
+    out = _pareto(domain, trials, objectives, engine, hypervolume, hv_method=hv_method,
+                  constraints=constraints, want_v=constraints is not None)
     docs, by, s = out[0], out[2], out[4]
     keep = (by == 0) & np.isfinite(s)
     if constraints is not None:
@@ -1189,18 +1219,22 @@ def pareto_front(domain, trials, objectives=None, engine=None, hypervolume=False
     return [docs[r] for r in np.flatnonzero(keep)]
 
 
-def hv_picks(domain, trials, objectives=None, hypervolume=True, engine=None, constraints=None):
+def hv_picks(domain, trials, objectives=None, hypervolume=True, engine=None, constraints=None,
+             hv_method='auto'):
     """(tids, gains, alive) of the hypervolume subset selection inside the
     Pareto front of ``trials`` (tpe_plan_hv_get), in pick order:
     the tids picked, what each added to the hypervolume given the picks
     before it -- the exact area with two objectives, the Monte-Carlo estimate
-    ``vol * alive / S`` with more -- and its alive samples (-1: exact).  At most
+    ``vol * alive / S`` with more, or as ``hv_method`` says (``suggest``;
+    'exact' with three objectives: the exact volume) -- and its alive samples
+    (-1: exact).  At most
     32 picks; fewer when the front inside the reference point is smaller;
     none with ``objectives=1``, ``hypervolume=False`` or no complete trial.
     With ``constraints=C`` the front is that of constrained dominance: the
     feasible front, or without a feasible trial the trials of least violation."""
     _, tids, _, _, _, (picks, keys, counts, R) = _pareto(domain, trials, objectives, engine,
-                                                       hypervolume, want_hv=True,
+                                                       hypervolume, hv_method=hv_method,
+                                                       want_hv=True,
                                                        constraints=constraints)
     picks, keys, counts = picks[:R], keys[:R].copy(), counts[:R]
     mc = counts >= 0

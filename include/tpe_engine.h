@@ -578,6 +578,14 @@ int tpe_plan_pareto_shape(tpe_plan_t p, int64_t n, int32_t n_obj, int64_t force_
  *   exact (two objectives): key = (right - y[0]) * (top - y[1]), right the
  *     smallest y_p[0] > y[0] over the picks p (ref[0] without one), top the
  *     same in objective 1; 0 once a pick equals the row in both objectives.
+ *   exact (three objectives, method 3): the volume of the row's box that no
+ *     pick dominates, by a sweep over the picks clipped into the box,
+ *     c_p[m] = max(y_p[m], y[m]): slabs along objective 2 between the clipped
+ *     picks in ascending order (ties by pick round), in slab j the area the
+ *     j picks of lowest objective 2 leave of the (objective 0, objective 1)
+ *     rectangle, walked in ascending objective 0 (ties by pick round);
+ *     key = sum of height * area over the slabs of height > 0, in ascending
+ *     order.  0 once a pick equals the row.  Round 0's key is vol.
  *   Monte-Carlo: key = vol * alive, alive the number of the row's n_samples
  *     samples z[m] = y[m] + u[s][m] * w[m] with no pick p below them
  *     (y_p[m] <= z[m] for every m); u[s][m] is uniform m % 4 of the Philox
@@ -590,12 +598,12 @@ int tpe_plan_pareto_shape(tpe_plan_t p, int64_t n, int32_t n_obj, int64_t force_
  * stays in [0, n]: a dominates b still implies s[a] < s[b].  Every value is a
  * function of (Y, ref, n_pick, n_samples, seed, method) alone: products and
  * differences as written, no fused multiply-add, keys compared as integers.
- * method: 0 exact with two objectives and Monte-Carlo with more, 1 exact,
- * 2 Monte-Carlo.  With n_obj = 1 the setting is accepted and ignored (the
+ * method: 0 exact with two objectives and Monte-Carlo with more, 1 exact
+ * (two objectives), 2 Monte-Carlo, 3 exact (three objectives).  With n_obj = 1 the setting is accepted and ignored (the
  * ranking is total).  TPE_E_INVALID: a mode other than 0 / 1, a null or
  * non-finite ref, n_obj outside [1, TPE_MAX_OBJ], n_pick outside [1, 256],
  * n_samples not a multiple of 64 in [64, 4096], an unknown method, method 1
- * with n_obj != 2; a tpe_plan_set_objectives with another n_obj fails with
+ * with n_obj != 2, method 3 with n_obj != 3; a tpe_plan_set_objectives with another n_obj fails with
  * TPE_E_INVALID while the mode is on.  Mode 0 ignores the other arguments,
  * adds no launch and allocates nothing.                                      */
 int tpe_plan_set_hv(tpe_plan_t p, int32_t mode, const double *ref, int32_t n_obj,

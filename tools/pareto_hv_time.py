@@ -9,9 +9,12 @@ the device (obj0 = n: no upload), in one session and alternating,
           the cost of one further round;
   fit     ``tpe_plan_fit`` on the same plan and history, the yardstick;
 at n = 1e3, 1e4, 1e5 trials and M = 2 (the exact path), 4, 8 (Monte-Carlo)
-objectives, on a space of 8 uniform hps.  The objectives are a trade-off (a
+objectives, on a space of 8 uniform hps.  ``--method`` names the estimators to
+time (auto, mc, exact; several alternate in the one session, each with its own
+``on`` / ``on/1`` lines), ``--n-pick`` the rounds.  The objectives are a trade-off (a
 front of many rows); the line ``front`` gives its size and the picks made.
 usage: python tools/pareto_hv_time.py [--n 1000 10000 100000] [--m 2 4 8] [--reps N] [--out FILE]
+       [--method auto|mc|exact ...] [--n-pick K]
 """
 import argparse
 import os
@@ -21,7 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 N_HP = 8
-N_PICK, N_SAMPLES = 32, 1024
+N_SAMPLES = 1024
+METHODS = {'auto': lambda M: 0, 'mc': lambda M: 2, 'exact': lambda M: {2: 1, 3: 3}[M]}
 
 
 def main():
@@ -29,8 +33,11 @@ def main():
     ap.add_argument('--n', nargs='+', type=int, default=[1000, 10000, 100000])
     ap.add_argument('--m', nargs='+', type=int, default=[2, 4, 8])
     ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--method', nargs='+', choices=sorted(METHODS), default=['auto'])
+    ap.add_argument('--n-pick', type=int, default=32)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'pareto_hv_time.txt'))
     args = ap.parse_args()
+    N_PICK = args.n_pick
     import numpy as np
     from hyperopt_amd import _engine as E
     E.load_library()                 # (before torch: one HIP runtime, _share_hip_runtime)
@@ -64,6 +71,8 @@ def main():
     eng = E.default_engine()
     say('hypervolume subset selection inside the front: %d uniform hps, n_pick = %d, S = %d, '
         'device time per tpe_plan_set_objectives' % (N_HP, N_PICK, N_SAMPLES))
+    if args.method != ['auto']:
+        say('methods timed alternating in one session: %s' % ', '.join(args.method))
     for n in args.n:
         rng = np.random.RandomState(n)
         plan = E.Plan(eng, hps, conds, pprior, max_trials=n)
@@ -86,43 +95,45 @@ def main():
                 plan.set_hv(None)
                 rank()
 
-            def on():
-                plan.set_hv(ref, n_pick=N_PICK, n_samples=N_SAMPLES)
-                rank()
-
-            def on1():
-                plan.set_hv(ref, n_pick=1, n_samples=N_SAMPLES)
-                rank()
+            def on_with(method, n_pick):
+                def on():
+                    plan.set_hv(ref, n_pick=n_pick, n_samples=N_SAMPLES, method=METHODS[method](M))
+                    rank()
+                return on
 
             def fit():
                 plan.fit(stream=sp)
 
-            fns = [off, on, on1, fit]
+            ons = [(m, on_with(m, N_PICK), on_with(m, 1)) for m in args.method]
+            fns = [off] + [f for _, a, b in ons for f in (a, b)] + [fit]
             times = {f: [] for f in fns}
             for r in range(args.reps + 3):
-                order = fns[r % 4:] + fns[:r % 4]
+                k = r % len(fns)
+                order = fns[k:] + fns[:k]
                 for f in order:
                     t = timed(f)
                     if r >= 3:
                         times[f].append(t)
-            on()
-            torch.cuda.synchronize()
-            by = plan.pareto_get(n)[0]
-            picks, _, counts, R = plan.hv_get()
-            plan.set_hv(None)
-            tag = 'n=%-6d M=%d' % (n, M)
-            m_off, m_on, m_on1, m_fit = (np.median(times[f]) for f in fns)
-            say('%s  front %d rows, %d picks, %s, %d reps'
-                % (tag, int((by == 0).sum()), R, 'exact' if M == 2 else 'Monte-Carlo',
-                   len(times[on])))
-            say('%s  off    %s' % (tag, stats(times[off])))
-            say('%s  on     %s' % (tag, stats(times[on])))
-            say('%s  on/1   %s' % (tag, stats(times[on1])))
-            say('%s  fit    %s' % (tag, stats(times[fit])))
-            say('%s  selection %.3f ms = on - off; one further round %.4f ms; on / off = %.2f; '
-                'selection / fit = %.2f'
-                % (tag, m_on - m_off, (m_on - m_on1) / (N_PICK - 1), m_on / m_off,
-                   (m_on - m_off) / m_fit))
+            m_off, m_fit = np.median(times[off]), np.median(times[fit])
+            for method, on, on1 in ons:
+                on()
+                torch.cuda.synchronize()
+                by = plan.pareto_get(n)[0]
+                picks, _, counts, R = plan.hv_get()
+                plan.set_hv(None)
+                tag = 'n=%-6d M=%d' % (n, M) + ('' if args.method == ['auto'] else ' %-5s' % method)
+                m_on, m_on1 = np.median(times[on]), np.median(times[on1])
+                say('%s  front %d rows, %d picks, %s, %d reps'
+                    % (tag, int((by == 0).sum()), R,
+                       'exact' if R and counts[0] < 0 else 'Monte-Carlo', len(times[on])))
+                say('%s  off    %s' % (tag, stats(times[off])))
+                say('%s  on     %s' % (tag, stats(times[on])))
+                say('%s  on/1   %s' % (tag, stats(times[on1])))
+                say('%s  fit    %s' % (tag, stats(times[fit])))
+                say('%s  selection %.3f ms = on - off; one further round %.4f ms; on / off = %.2f; '
+                    'selection / fit = %.2f'
+                    % (tag, m_on - m_off, (m_on - m_on1) / max(N_PICK - 1, 1), m_on / m_off,
+                       (m_on - m_off) / m_fit))
         plan.close()
 
 
